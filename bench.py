@@ -11,7 +11,9 @@ path; --shard-frames exercises the frame-sharded ViT + RCCL all-gather of config
 Launch:  python bench.py --gpus 1 --steps 3 --warmup 1
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
                 bench.py --gpus N --steps K --warmup W
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the headline (`value`, `ms_per_step`, ...);
+--full adds the phase breakdown, the roofline and per-kernel figures, the CPU baseline and the checks of the parallel modes, all
+measured after the timed steps.  --dump-outputs DIR writes what the last timed step returned (DIR/tokens.npy).
 """
 import argparse
 import ctypes as C
@@ -313,7 +315,11 @@ def main():
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--shard-frames", action="store_true", help="C4 mode: one conversation, ViT frames sharded over ranks + all-gather")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: phase breakdown, roofline and "
+                    "per-kernel figures, the CPU baseline, the frame-sharding check and timings, the RCCL communicator check of N > 1 replicas")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned to "
+                    "DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"], help="16-bit storage / compute format: bf16 = BASELINE.json's headline; "
                     "fp16 = the reference's own inference dtype (builder.py:105), same kernels on v_mfma_*_f16 / v_dot2_f32_f16")
@@ -328,6 +334,8 @@ def main():
     ap.add_argument("--tune", action="append", default=[], help="key=value set in the engine's teo_tune block (perf knobs only)")
     ap.add_argument("--rope-in-attn", type=int, default=None, choices=[0, 1], help="A/B of the engine option: RoPE + KV append inside the decode attention kernel (1) or in the QKV GEMV epilogue (0, the single-conversation default); same values")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1: ms_per_step is the time of one timed step")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the N ranks here.  This parent has not touched the GPU (importing
@@ -369,7 +377,6 @@ def main():
         raise SystemExit(f"rank {rank}: TEO_BENCH_FAIL_RANK set")
     if world > 1 and dist.get_world_size() != args.gpus:
         raise SystemExit(f"{dist.get_world_size()} ranks joined the process group, --gpus says {args.gpus}")
-    from teochat_amd import _lib as L
     from teochat_amd.builder import load_pretrained_model
     T, n_text, n_out = args.frames, args.prompt, args.new
     Lseq = n_text - T + 256 * T
@@ -400,8 +407,9 @@ def main():
     # The library's own RCCL communicator (teo_ctx_create over all ranks): the data path of the frame-sharded tower, and for the
     # data-parallel replicas a once-per-run proof that N ranks really hold one communicator over xGMI (`rccl_ranks` below) plus
     # one checked teo_allgather_visual of a C4-sized block (2 frames x 256 x 1024 bf16 = 1 MiB per rank), outside the timed region.
+    # The replicas do not need it for their headline: without --full only the frame-sharded tower builds it.
     comm, rccl_info, th = None, None, None
-    if world > 1 and args.dist_backend == "nccl":
+    if world > 1 and args.dist_backend == "nccl" and (args.shard_frames or args.full):
         from teochat_amd.parallel import TeoComm
         import threading
         box = {}
@@ -451,6 +459,7 @@ def main():
         # (teo_allgather_visual, no torch collective on the data path); gloo only for the one-GPU plumbing test
         tower = model.get_model().image_tower
         tower.shard_frames(comm)
+    if args.shard_frames and args.full:
         # outside the timed region: the gathered features of THIS rank equal the unsharded encode of all T frames bit for bit, in
         # chronological order (rank order = frame order: `cur_image_idx` consumption, llava_arch.py:284-285) -- on every rank
         pix_all = torch.stack(frames)
@@ -539,6 +548,91 @@ def main():
         per_rank = sorted(box, key=lambda e: e["rank"])
     convs = args.steps * (1 if args.shard_frames else world) * B
     value = convs * n_out / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    if args.full:
+        phases, roofline = full_figures(args, model, frames, ids, batch_in if B > 1 else None, dt, device, dtype)
+
+    result = {
+        "metric": "end-to-end tokens/sec (prefill+decode), T=8 frames, LLaMA-2-7B",
+        "value": round(value, 2), "unit": "tokens/s", "n_gpus": (dist.get_world_size() if world > 1 else 1), "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.dtype if args.weights == "bf16" else ("bf16 activations / fp8-e4m3 weights (decode: fp8 weight stream; prefill: "
+                                                       + ("w8a8 on the fp8 MFMA)" if prefill_fp8 else "bf16 MFMA on the dequantised weights)")), "data": "synthetic",
+        "config": {"workload": f"{workload_label(T, n_text, n_out, B, args.shard_frames, args.weights)}: T={T} frames 224x224 -> CLIP-ViT-L/14 (23 layers) -> mlp2x_gelu -> splice of a "
+                               f"{n_text}-token prompt (L={Lseq}) -> LLaMA-2-7B prefill -> {n_out} forced greedy tokens; "
+                               f"value = generated tokens / total time",
+                   "frames": T, "prompt_tokens": n_text, "sequence_len": Lseq, "new_tokens": n_out,
+                   "parallelism": ("frame-sharded ViT + all-gather, replicated LLM" if args.shard_frames
+                                   else f"dp{world} ({B} conversation{'s' if B > 1 else ''} per GPU, no collective)"),
+                   "weights": "random N(0,0.02^2) at LLaMA-2-7B / ViT-L/14 shapes"},
+        "total_tokens_per_s_incl_prompt": round(convs * (Lseq + n_out) / dt, 1),
+    }
+    if args.full:
+        result.update(phases=phases, roofline=roofline)
+    result["setup_s"] = round(setup_s, 2)
+    if per_rank is not None:
+        own_tokens = args.steps * B * n_out          # what ONE rank generated in its own `seconds` (the sharded-tower run: the same conversation on every rank)
+        vals = [own_tokens / e["seconds"] for e in per_rank]
+        slow = max(range(world), key=lambda r_: per_rank[r_]["seconds"])
+        result["per_rank"] = {"tokens_per_s": [round(v, 2) for v in vals], "ms_per_step": [round(e["seconds"] / args.steps * 1e3, 2) for e in per_rank],
+                              "setup_s": [round(e["setup_s"], 2) for e in per_rank],
+                              "min_tokens_per_s": round(min(vals), 2), "max_tokens_per_s": round(max(vals), 2), "straggler_rank": slow,
+                              "spread": round(max(vals) / min(vals) - 1.0, 4),
+                              "note": "each rank's own clock between the two barriers of the timed region; `value` uses the slowest rank's"}
+    if args.shard_frames and args.full:
+        result["shard_frames_check"] = shard_check
+        result["shard_frames"] = shard_times
+    result["rccl_ranks"] = rccl_info["rccl_ranks"] if rccl_info else (1 if world == 1 else None)
+    if rccl_info:
+        result["rccl"] = rccl_info
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline:
+        result["cpu_baseline"] = cpu_baseline(T, n_text, n_out)
+    elif rank == 0 and args.full and world > 1:
+        # measured at N = 1 only (the contract: rank 0, N = 1); an N > 1 line points at the committed N = 1 line instead of carrying null
+        ref_line = None
+        for name in ("r06_bench.json", "r05_bench.json", "r04_bench.json"):
+            path = os.path.join(ROOT, "profiles", name)
+            if os.path.exists(path):
+                try:
+                    cb = json.load(open(path)).get("cpu_baseline")
+                    if cb:
+                        ref_line = dict(cb, measured_at="n_gpus = 1", from_profiles="profiles/" + name,
+                                        note="not re-measured in this N > 1 run: the oracle is timed on rank 0 at N = 1 only")
+                        break
+                except Exception:  # noqa: BLE001
+                    pass
+        result["cpu_baseline"] = ref_line
+    elif rank == 0 and args.full:
+        result["cpu_baseline"] = None
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if world > 1:
+        stuck = th is not None and th.is_alive()         # the communicator check never came back: do not wait for it at exit either
+        if stuck:
+            sys.stdout.flush()
+            os._exit(0)
+        with deadline("destroy_process_group"):
+            dist.destroy_process_group()
+
+
+def dump_outputs(dirname, out):
+    """--dump-outputs: what the timed path's last step handed its caller -- the token ids of generate() / generate_batch(), prompt
+    (sentinels included) + generated tokens, one row per conversation -- as DIR/tokens.npy in float64 (ids are exact there)."""
+    import numpy as np
+    arr = out.detach().cpu().to(torch.float64).numpy()
+    assert arr.nbytes <= 64 << 20, arr.shape
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "tokens.npy"), arr)
+
+
+def full_figures(args, model, frames, ids, batch_in, dt, device, dtype):
+    """--full: what the line carries beyond the headline, all measured after the timed steps: the phase breakdown of one more step,
+    the product-default and sampled calls, and the roofline of the dominant decode kernel.  Returns (phases, roofline)."""
+    from teochat_amd import _lib as L
+    eng = model.engine
+    T, n_text, n_out, B = args.frames, args.prompt, args.new, args.batch
+    Lseq = n_text - T + 256 * T
 
     # ---- untimed: phase breakdown of one more step
     phases = {}
@@ -666,8 +760,8 @@ def main():
         except Exception as e:  # noqa: BLE001
             chain_ms, chain_note = None, f"chain microbenchmark skipped: {e}"
             print(chain_note, file=sys.stderr)
-    # HBM traffic comes from PMC counters, which need their own rocprofv3 --pmc passes (MI355X_MICROARCH.md section HBM:
-    # FETCH_SIZE x2 on gfx950 + WRITE_SIZE); it is NOT measured inside this run: the numbers below are read from the committed
+    # HBM traffic comes from PMC counters, which need their own rocprofv3 --pmc passes (read bytes on gfx950:
+    # FETCH_SIZE x2 + WRITE_SIZE); it is NOT measured inside this run: the numbers below are read from the committed
     # summary of those passes (tools/pmc_traffic.sh) and labelled with the file and the commit they were taken at.
     traffic, traffic_src, traffic_all = None, None, None
     try:
@@ -804,68 +898,7 @@ def main():
     t_meas_s = dt / args.steps                       # one step = B conversations prepared and decoded together
     roofline["t_min_ms"] = round(t_min_s * 1e3, 3)
     roofline["end_to_end_frac"] = round(t_min_s / t_meas_s, 4)
-
-    result = {
-        "metric": "end-to-end tokens/sec (prefill+decode), T=8 frames, LLaMA-2-7B",
-        "value": round(value, 2), "unit": "tokens/s", "n_gpus": (dist.get_world_size() if world > 1 else 1), "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": args.dtype if args.weights == "bf16" else ("bf16 activations / fp8-e4m3 weights (decode: fp8 weight stream; prefill: "
-                                                       + ("w8a8 on the fp8 MFMA)" if prefill_fp8 else "bf16 MFMA on the dequantised weights)")), "data": "synthetic",
-        "config": {"workload": f"{workload_label(T, n_text, n_out, B, args.shard_frames, args.weights)}: T={T} frames 224x224 -> CLIP-ViT-L/14 (23 layers) -> mlp2x_gelu -> splice of a "
-                               f"{n_text}-token prompt (L={Lseq}) -> LLaMA-2-7B prefill -> {n_out} forced greedy tokens; "
-                               f"value = generated tokens / total time",
-                   "frames": T, "prompt_tokens": n_text, "sequence_len": Lseq, "new_tokens": n_out,
-                   "parallelism": ("frame-sharded ViT + all-gather, replicated LLM" if args.shard_frames
-                                   else f"dp{world} ({B} conversation{'s' if B > 1 else ''} per GPU, no collective)"),
-                   "weights": "random N(0,0.02^2) at LLaMA-2-7B / ViT-L/14 shapes"},
-        "total_tokens_per_s_incl_prompt": round(convs * (Lseq + n_out) / dt, 1),
-        "phases": phases,
-        "roofline": roofline,
-    }
-    result["setup_s"] = round(setup_s, 2)
-    if per_rank is not None:
-        own_tokens = args.steps * B * n_out          # what ONE rank generated in its own `seconds` (the sharded-tower run: the same conversation on every rank)
-        vals = [own_tokens / e["seconds"] for e in per_rank]
-        slow = max(range(world), key=lambda r_: per_rank[r_]["seconds"])
-        result["per_rank"] = {"tokens_per_s": [round(v, 2) for v in vals], "ms_per_step": [round(e["seconds"] / args.steps * 1e3, 2) for e in per_rank],
-                              "setup_s": [round(e["setup_s"], 2) for e in per_rank],
-                              "min_tokens_per_s": round(min(vals), 2), "max_tokens_per_s": round(max(vals), 2), "straggler_rank": slow,
-                              "spread": round(max(vals) / min(vals) - 1.0, 4),
-                              "note": "each rank's own clock between the two barriers of the timed region; `value` uses the slowest rank's"}
-    if args.shard_frames:
-        result["shard_frames_check"] = shard_check
-        result["shard_frames"] = shard_times
-    result["rccl_ranks"] = rccl_info["rccl_ranks"] if rccl_info else (1 if world == 1 else None)
-    if rccl_info:
-        result["rccl"] = rccl_info
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        result["cpu_baseline"] = cpu_baseline(T, n_text, n_out)
-    elif rank == 0 and world > 1:
-        # measured at N = 1 only (the contract: rank 0, N = 1); an N > 1 line points at the committed N = 1 line instead of carrying null
-        ref_line = None
-        for name in ("r06_bench.json", "r05_bench.json", "r04_bench.json"):
-            path = os.path.join(ROOT, "profiles", name)
-            if os.path.exists(path):
-                try:
-                    cb = json.load(open(path)).get("cpu_baseline")
-                    if cb:
-                        ref_line = dict(cb, measured_at="n_gpus = 1", from_profiles="profiles/" + name,
-                                        note="not re-measured in this N > 1 run: the oracle is timed on rank 0 at N = 1 only")
-                        break
-                except Exception:  # noqa: BLE001
-                    pass
-        result["cpu_baseline"] = ref_line
-    elif rank == 0:
-        result["cpu_baseline"] = None
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        stuck = th is not None and th.is_alive()         # the communicator check never came back: do not wait for it at exit either
-        if stuck:
-            sys.stdout.flush()
-            os._exit(0)
-        with deadline("destroy_process_group"):
-            dist.destroy_process_group()
+    return phases, roofline
 
 
 if __name__ == "__main__":

@@ -1,5 +1,6 @@
 """The bench.py contract the driver depends on: one JSON line on stdout with the agreed keys (a short run on the real
-7B-shaped synthetic model: T=2 frames, 32-token prompt, 8 new tokens)."""
+7B-shaped synthetic model: T=2 frames, 32-token prompt, 8 new tokens).  The tests that read the phase breakdown, the roofline,
+the CPU baseline or the parallel-mode checks run the benchmark with --full."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-                        "--frames", "2", "--prompt", "32", "--new", "8", "--no-cpu-baseline"],
+                        "--frames", "2", "--prompt", "32", "--new", "8", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -51,7 +52,7 @@ def test_bench_variant_line_names_the_kernel_that_dominated_that_run():
     picked from the profiled batched step (a batched-decode kernel, not the single-conversation gate/up GEMV), its share of the
     step is stated, and end_to_end_frac / the batched step's HBM fraction exist for B > 1 (VERDICT r03 weak #9)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--frames", "2",
-                        "--prompt", "32", "--new", "8", "--no-cpu-baseline", "--batch", "8", "--weights", "fp8"],
+                        "--prompt", "32", "--new", "8", "--no-cpu-baseline", "--batch", "8", "--weights", "fp8", "--full"],
                        capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][0])
@@ -73,7 +74,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1",
-                        "--warmup", "1", "--frames", "2", "--prompt", "32", "--new", "8", "--dist-backend", "gloo", "--same-gpu"],
+                        "--warmup", "1", "--frames", "2", "--prompt", "32", "--new", "8", "--dist-backend", "gloo", "--same-gpu", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -115,7 +116,7 @@ def test_bench_eight_ranks_c4_partition_on_one_gpu():
     bench.py itself checks, on every rank, that the gathered features equal the unsharded tower's bit for bit.  No scaling number is
     claimed from this: eight ranks share one GPU."""
     r, lines = _bench(["--gpus", "8", "--same-gpu", "--dist-backend", "gloo", "--shard-frames", "--frames", "16", "--new", "8",
-                       "--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
+                       "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--full"])
     assert r.returncode == 0, r.stderr[-4000:]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
@@ -137,7 +138,7 @@ def test_bench_eight_data_parallel_ranks_on_one_gpu():
     can take it: eight ranks, eight different conversations, barrier + max-over-ranks time, whole-job value, and the N = 1 cpu_baseline
     carried by reference instead of null."""
     r, lines = _bench(["--gpus", "8", "--same-gpu", "--dist-backend", "gloo", "--batch", "1", "--frames", "2", "--prompt", "32", "--new", "8",
-                       "--steps", "1", "--warmup", "1"])
+                       "--steps", "1", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-4000:]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
@@ -182,6 +183,30 @@ def test_a_failing_rank_fails_the_whole_bench():
                        "--warmup", "0", "--no-cpu-baseline"], timeout=900, extra_env={"TEO_BENCH_FAIL_RANK": "1"})
     assert r.returncode != 0
     assert not lines, r.stdout[-1000:]
+
+
+def test_plain_line_is_lean_and_two_runs_dump_the_same_outputs(tmp_path):
+    """Without --full the line carries the headline and nothing measured beside it; --dump-outputs writes what the last timed step
+    returned (the token ids generate() hands its caller), and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        out_dir = tmp_path / f"run{i}"
+        r, lines = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "2", "--prompt", "32", "--new", "8",
+                           "--dump-outputs", str(out_dir)], timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["unit"] == "tokens/s" and d["higher_is_better"] is True and d["dtype"] == "bf16" and d["steps"] == 2
+        assert d["metric"].startswith("end-to-end tokens/sec") and d["ms_per_step"] > 0
+        assert abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) < 0.02 * d["value"]
+        for k in ("phases", "roofline", "cpu_baseline"):
+            assert k not in d, k
+        tok = np.load(out_dir / "tokens.npy")
+        assert tok.dtype == np.float64 and tok.shape == (1, 32 + 8)
+        assert ((tok[0, 32:] >= 0) & (tok[0, 32:] < 32000)).all() and (tok == np.round(tok)).all()
+        dumps.append(tok)
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 def test_bench_refuses_more_ranks_than_gpus():

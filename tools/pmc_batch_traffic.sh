@@ -10,9 +10,9 @@ mkdir -p $ROOT/gpurun_out/r06p
 cd /tmp && export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE TCC_EA0_RDREQ_sum; do
   rm -rf /tmp/pmcb8_$C
-  timeout 900 rocprofv3 --kernel-trace --pmc $C -d /tmp/pmcb8_$C -o p -- python3 $ROOT/bench.py --steps 1 --warmup 0 --new 12 --no-cpu-baseline --no-graph --batch 8 --weights fp8 > /tmp/pmcb8_$C.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --pmc $C -d /tmp/pmcb8_$C -o p -- python3 $ROOT/bench.py --full --steps 1 --warmup 0 --new 12 --no-cpu-baseline --no-graph --batch 8 --weights fp8 > /tmp/pmcb8_$C.log 2>&1
 done
-python3 - "$COMMIT" <<'PY'
+python3 - "$COMMIT" "$ROOT" <<'PY'
 import glob, json, os, sqlite3, sys
 B, CTX = 8, 2178          # 12 new tokens after a 2168-token prompt: mean context of the sampled launches
 KERNELS = {   # name -> (test on the kernel name, algorithmic HBM bytes per launch)
@@ -31,8 +31,8 @@ for c in ("FETCH_SIZE", "WRITE_SIZE", "TCC_EA0_RDREQ_sum"):
     cur = sqlite3.connect(dbs[0]).cursor()
     rows = list(cur.execute("select kernel_name, count(*), avg(value) from counters_collection where counter_name = ? group by kernel_name", (c,)))
     raw[c] = {r[0]: (r[1], r[2]) for r in rows}
-out = {"source": "tools/pmc_batch_traffic.sh: three separate rocprofv3 --kernel-trace --pmc passes over `python3 bench.py --steps 1 --warmup 0 --new 12 --no-cpu-baseline --no-graph --batch 8 --weights fp8`",
-       "commit": sys.argv[1], "csrc_sha16": __import__("subprocess").check_output(["python3", os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/tools/src_hash.py"]).decode().strip(),
+out = {"source": "tools/pmc_batch_traffic.sh: three separate rocprofv3 --kernel-trace --pmc passes over `python3 bench.py --full --steps 1 --warmup 0 --new 12 --no-cpu-baseline --no-graph --batch 8 --weights fp8`",
+       "commit": sys.argv[1], "csrc_sha16": __import__("subprocess").check_output(["python3", os.path.join(sys.argv[2], "tools", "src_hash.py")]).decode().strip(),
        "correction": "gfx950: read bytes = 2 * FETCH_SIZE * 1024 (128-B requests tallied at 64 B) + WRITE_SIZE * 1024; cross-check TCC_EA0_RDREQ_sum * 128 B",
        "kernels": {}, "all_teo_kernels": sorted(n[:120] for n in raw.get("FETCH_SIZE", {}) if "teo::" in n and ("skinny" in n or "attn_decode" in n))}
 for key, (match, alg) in KERNELS.items():

@@ -13,7 +13,7 @@ i=0
 for P in "$P1" "$P2"; do
   i=$((i+1))
   rm -rf /tmp/pmcb_$i
-  timeout 900 rocprofv3 --kernel-trace --pmc $P -d /tmp/pmcb_$i -o p -- python3 $ROOT/bench.py --steps 1 --warmup 0 --new 12 --no-cpu-baseline --no-graph > /tmp/pmcb_$i.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --pmc $P -d /tmp/pmcb_$i -o p -- python3 $ROOT/bench.py --full --steps 1 --warmup 0 --new 12 --no-cpu-baseline --no-graph > /tmp/pmcb_$i.log 2>&1
   DB=$(find /tmp/pmcb_$i -name "*.db" | head -1)
   echo "--- pass $i: $P" >> $OUT
   if [ -n "$DB" ]; then

@@ -7,7 +7,7 @@ OUT=$ROOT/gpurun_out/r06p
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 prof() { name=$1; shift; rm -rf /tmp/prof_$name
-  timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o bench -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline "$@" > $OUT/prof_$name.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o bench -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "$@" > $OUT/prof_$name.log 2>&1
   DB=$(find /tmp/prof_$name -name "*.db" | head -1)
   if [ -n "$DB" ]; then python3 $ROOT/tools/prof_summary.py $DB $OUT/bench_${name}_kernel_stats.md > /dev/null; head -14 $OUT/bench_${name}_kernel_stats.md; fi; }
 prof frames16 --frames 16
