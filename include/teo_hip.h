@@ -54,6 +54,12 @@ const char* teo_last_error(void);
  * "gemm_big_hybrid_cohort", "gemm_narrow_64", "gemm_narrow_128", "gemm_narrow_128w8", "gemm_pipe_64x64", "gemm_pipe_64", "gemm_pipe_64_r4", "gemm_pipe_128x96",
  * "gemm_pipe_128", "gemm_quad_160", "gemm_quad_160_w4", "attn_flash32", "attn_simple").  Lets the parity tests state which production kernel they checked. */
 const char* teo_last_kernel(void);
+/* The family name teo_gemm_ws / teo_gemm_fp8_ws would note for this problem under the calling thread's tune block, on a device of
+ * cu_count CUs, with (with_ws = 1) or without a stream-K workspace; nothing is launched.  Dense operands (lda = K, ldc = N, or N / 2
+ * with TEO_GEMM_SWIGLU16) and aligned pointers are assumed.  The choice itself is gemm_plan.hip's.  teo_gemm_fp8_plan returns ""
+ * for a shape the w8a8 kernels do not take. */
+const char* teo_gemm_plan(int M, int N, int K, unsigned flags, int act, int dtype, int out_dtype, int with_ws, int cu_count);
+const char* teo_gemm_fp8_plan(int M, int N, int K, unsigned flags, int out_dtype, int with_ws, int cu_count);
 /* Size of a struct of this header as the LIBRARY was built with it (0 for an unknown name): a binding checks its own layout against it
  * at load time -- "teo_vit_desc", "teo_proj_desc", "teo_llama_desc", "teo_decode_state", "teo_decode_batch_state", "teo_attn_args". */
 size_t teo_sizeof(const char* struct_name);
@@ -96,8 +102,8 @@ size_t teo_sizeof(const char* struct_name);
  *                   heads make whole rounds of the CUs (a multiple of the CU count, or at least 7/4 rounds), 2 whenever the shape allows; bit-identical to the split + combine pair at the same chunk)
  *   batched GEMM  : "skinny_tiles" (0 auto, 1/2/4/8), "skinny_nt", "skinny_stream" (0 off, 1 auto, 2 whenever eligible), "skinny_ring"
  *                   (weight tiles in flight of the streaming form: 0 default, 1 one more), "skinny_unr" (tile kernel steps per register
- *                   set: 0 auto, 4, 8), "skinny_waves" (tile kernel waves per workgroup: 0 auto = 8, 8, 16 -- measured and lost in round 6,
- *                   kept for the A/B), "skinny_grid" (persistent workgroups per CU of the streaming form: 0 auto = 1, 1..3 -- likewise) --
+ *                   set: 0 auto, 4, 8), "skinny_waves" (tile kernel waves per workgroup: 0 and 8 = 8, 16 forced only --
+ *                   measured and lost, kept for the A/B), "skinny_grid" (persistent workgroups per CU of the streaming form: 0 auto = 1, 1..3 -- likewise) --
  *                   bit-identical at K = 4096, fp32 order elsewhere
  * teo_tune_set returns TEO_ERR_ARG for an unknown key or a value outside the key's set (message in teo_last_error). */
 typedef struct teo_tune teo_tune;

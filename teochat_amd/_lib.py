@@ -94,6 +94,8 @@ _SIGS = {
     "teo_version": (C.c_int, []),
     "teo_last_error": (C.c_char_p, []),
     "teo_last_kernel": (C.c_char_p, []),
+    "teo_gemm_plan": (C.c_char_p, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "teo_gemm_fp8_plan": (C.c_char_p, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int]),
     "teo_sizeof": (C.c_size_t, [C.c_char_p]),
     "teo_tune_create": (C.c_void_p, []),
     "teo_tune_destroy": (C.c_int, [C.c_void_p]),

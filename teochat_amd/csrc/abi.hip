@@ -98,6 +98,16 @@ extern "C" {
 int teo_version(void) { return TEO_ABI_VERSION; }
 const char* teo_last_error(void) { return g_err; }
 const char* teo_last_kernel(void) { return teo::g_last_kernel; }
+const char* teo_gemm_plan(int M, int N, int K, unsigned flags, int act, int dtype, int out_dtype, int with_ws, int cu_count) {
+    const int ldc = (flags & TEO_GEMM_SWIGLU16) ? N / 2 : N;
+    const bool ok = teo::gemm_mfma_ok(M, N, K, K, ldc, dtype, flags, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return teo::plan_gemm({M, N, K, K, ldc, act, flags, dtype, out_dtype, ok}, teo::tune(), cu_count, with_ws != 0).name;
+}
+const char* teo_gemm_fp8_plan(int M, int N, int K, unsigned flags, int out_dtype, int with_ws, int cu_count) {
+    const int ldc = (flags & TEO_GEMM_SWIGLU16) ? N / 2 : N;
+    const bool ok = teo::gemm_fp8_ok(M, N, K, K, ldc, flags, nullptr, nullptr, nullptr, nullptr);
+    return teo::plan_gemm_fp8({M, N, K, K, ldc, TEO_ACT_NONE, flags, TEO_F32, out_dtype, ok}, teo::tune(), cu_count, with_ws != 0).name;
+}
 
 teo_tune* teo_tune_create(void) { return new (std::nothrow) teo_tune(); }
 int teo_tune_destroy(teo_tune* t) {

@@ -99,8 +99,6 @@ __global__ __launch_bounds__(256) void gemm_simple_kernel(const T* __restrict__ 
 // MFMA kernel
 // ------------------------------------------------------------------------------------------------
 constexpr int BM = 128, BN = 128, BK = 64;
-constexpr double GEMM_WIDE_ROUND_COST = 0.88;  // one round of 256 wide tiles (one per CU) / one round of 512 128 x 128 tiles (two per CU):
-                                               // 62-69 us against 71-83 us at K = 4096 (tools/bench_kernels.py gemm_wide)
 constexpr int TILE_BYTES = BM * BK * 2;   // 16 KiB per operand tile
 
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
@@ -544,13 +542,8 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma_bf16_sk_kernel(const bf16_t*
 }
 
 // ------------------------------------------------------------------------------------------------
-// host dispatch
+// host side: the choice of family is gemm_plan.hip's; the helpers below launch what the plan says
 // ------------------------------------------------------------------------------------------------
-constexpr double GEMM_BIG_ROUND_COST = 1.75;  // measured: 100 us per round of 256 x 256 tiles vs 58 us per round of 128 x 256 (gate/up at M = 17344; 8192^3: 195 vs 111)
-// tune().gemm_big (default 1): 256 x 256 LDS-DMA kernel (gemm_big.hip): 0 off, 1 auto (rounds model), 2 forced
-// tune().gemm_wide (default 1): wide-tile LDS-DMA kernel (gemm_wide.hip): 0 off, 1 auto, 2 forced wherever its shape constraints hold
-// tune().gemm_sk (default 1): 1: stream-K kernel when a workspace is given and the static tiling would leave a ragged last round
-constexpr int SK_MAX_GRID = 512;   // 256 CUs x 2 resident workgroups (64 KiB LDS, <= 256 VGPRs each)
 // slabs of every stream-K form share the first GEMM_SK_SLAB_BYTES (512 x 64 KB here, 256 x 128 KB in gemm_wide.hip / gemm_fp8.hip,
 // 256 x 256 KB in gemm_big.hip); the hand-off flags live behind them
 size_t gemm_sk_workspace_bytes() { return GEMM_SK_SLAB_BYTES + GEMM_SK_FLAG_INTS * sizeof(int); }
@@ -566,12 +559,6 @@ int gemm_sk_workspace_status(const void* ws, int* host_flag, hipStream_t st) {
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     return e == hipSuccess ? TEO_OK : hip_fail(e, "gemm_sk_workspace_status");
 }
-// the persistent forms assume the MI355X's 256 CUs (grids of 256 / 512 resident workgroups): elsewhere the plain kernels run
-static bool sk_grid_fits_device() {
-    return device_cu_count() == 256;
-}
-// tune().gemm_depth (default 0): 0 = auto: 2-deep register prefetch, 1-deep for the SwiGLU epilogue (register budget)
-// tune().gemm_bm (default 0): 0 = auto (by wave quantisation over the resident workgroup slots), 64 or 128
 
 bool gemm_mfma_ok(int M, int N, int K, int lda, int ldc, int dtype, unsigned flags, const void* A, const void* W,
                   const void* bias, const void* res, const void* C) {
@@ -584,228 +571,25 @@ bool gemm_mfma_ok(int M, int N, int K, int lda, int ldc, int dtype, unsigned fla
     return al(A, 16) && al(W, 16) && al(bias, 8) && al(res, 8) && al(C, 16);
 }
 
-int gemm_wide_sk_launch(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda, int ldc,
-                        int act, bool of32, bool f16, void* sk_ws, size_t flags_offset, hipStream_t st);          // gemm_wide.hip
-
-// 128 x 256 tiles on 256 slots (one 8-wave workgroup per CU) against 128 x 128 tiles on 512 slots: rounds of equal-length tiles
-static bool gemm_wide_wins(int M, int N, int K, bool forced, bool swiglu) {
-    if (K < 2 * BK) return false;
-    const long long t_wide = (long long)cdiv(M, 128) * cdiv(N, 256), t_plain = (long long)cdiv(M, 128) * cdiv(N, 128);
-    if (forced) return true;
-    // not enough tiles to fill the chip once (240 at M = 638, N = 12288: 57 vs 79 us); with a short K loop (K <= 1024: the tower's
-    // qkv at M = 2056, 204 wide tiles) the single round of wide tiles wins from 192 on (23.9 vs 29.6 us, tools/vit_gemm_probe.py)
-    // a long K loop on half a round of wide tiles still beats a whole round of 128 x 128 ones (the tower's fc2 at T = 16: M = 4112, N = 1024,
-    // K = 4096, 132 wide tiles: 52.6 us against 61-65 us on either 128 x 128 kernel; tools/vit_gemm_probe.py, round 5)
-    if (K >= 4096 && t_wide >= 128 && t_wide <= 256) return true;
-    // round 6 (tools/dispatch_monotone.py): gate/up below one round of wide tiles (M <= 256: 68.7 us at M = 128 against 78.4 on the 128 x 128 tile --
-    // the SwiGLU epilogue has no narrow family), and the short-K shapes from 144 wide tiles on (the tower's fc1 / the projector at T = 4 .. 5:
-    // 26.1-26.9 us against 27.7-28.7 on 128 x 128 tiles)
-    if (swiglu && t_wide >= 64 && t_wide <= 256) return true;
-    if (t_wide < 208 && !(K <= 1024 && t_wide >= 144)) return false;
-    // cost in rounds of the plain kernel; its ragged last round runs faster when it leaves one workgroup per CU (x 0.66, measured)
-    const long long rem = t_plain % 512;
-    const double plain = (double)(t_plain / 512) + (rem == 0 ? 0.0 : (rem <= 256 ? 0.66 : 1.0));
-    const double wide = (double)cdiv(t_wide, 256) * GEMM_WIDE_ROUND_COST;
-    return wide < plain;
-}
-
 template <typename T, typename TO>
-static void launch_simple(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N,
-                          int K, int lda, int ldc, int act, bool swiglu, hipStream_t st) {
-    dim3 grid(cdiv(N, 64), cdiv(M, 64));
-    if (swiglu)
-        gemm_simple_kernel<T, TO, true><<<grid, 256, 0, st>>>((const T*)A, (const T*)W, (const T*)bias,
-                                                              (const T*)res, (TO*)C, M, N, K, lda, ldc, act);
-    else
-        gemm_simple_kernel<T, TO, false><<<grid, 256, 0, st>>>((const T*)A, (const T*)W, (const T*)bias,
-                                                               (const T*)res, (TO*)C, M, N, K, lda, ldc, act);
+static void launch_simple(const GemmArgs& a, hipStream_t st) {
+    dim3 grid(cdiv(a.N, 64), cdiv(a.M, 64));
+    with_flags([&](auto sw) {
+        gemm_simple_kernel<T, TO, sw><<<grid, 256, 0, st>>>((const T*)a.A, (const T*)a.W, (const T*)a.bias, (const T*)a.res, (TO*)a.C, a.M, a.N,
+                                                            a.K, a.lda, a.ldc, a.act);
+    }, a.swiglu);
 }
 
-// the 128 x 128 (or 64 x 128) tile kernel, one workgroup per tile
-static int gemm_plain_launch(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda, int ldc,
-                             int act, bool swiglu, bool of32, bool f16, int bm, hipStream_t st) {
-    const int tiles_n = cdiv(N, BN), tiles_m = cdiv(M, bm);
-    const int nwg = tiles_m * tiles_n;
-    const size_t lds = 4 * TILE_BYTES;
-#define TEO_GEMM_KF(SW, OF, DP, MFV, FV)                                                                              \
-    gemm_mfma_bf16_kernel<SW, OF, DP, MFV, FV><<<nwg, 256, lds, st>>>((const bf16_t*)A, (const bf16_t*)W, (const bf16_t*)bias, \
-                                                                      (const bf16_t*)res, C, M, N, K, lda, ldc, act, tiles_m, \
-                                                                      tiles_n)
-#define TEO_GEMM_K(SW, OF, DP, MFV) do { if (f16) TEO_GEMM_KF(SW, OF, DP, MFV, true); else TEO_GEMM_KF(SW, OF, DP, MFV, false); } while (0)
-#define TEO_GEMM_LAUNCH(SW, OF)                                                                                      \
-    if (bm == 64) { TEO_GEMM_K(SW, OF, 2, 2); }                                                                       \
-    else if ((tune().gemm_depth == 0 && !(SW)) || tune().gemm_depth == 2) { TEO_GEMM_K(SW, OF, 2, 4); }                         \
-    else { TEO_GEMM_K(SW, OF, 1, 4); }
-        if (swiglu) { if (of32) { TEO_GEMM_LAUNCH(true, true) } else { TEO_GEMM_LAUNCH(true, false) } }
-        else        { if (of32) { TEO_GEMM_LAUNCH(false, true) } else { TEO_GEMM_LAUNCH(false, false) } }
-#undef TEO_GEMM_K
-#undef TEO_GEMM_KF
-#undef TEO_GEMM_LAUNCH
-        note_kernel(bm == 64 ? "gemm_mfma_64" : "gemm_mfma_128");
-    TEO_LAUNCH_CHECK("gemm_mfma_bf16");
-    return TEO_OK;
-}
-
-int gemm(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda,
-         int ldc, int act, unsigned flags, int dtype, int out_dtype, hipStream_t st, void* sk_ws) {
-    if (M == 0 || N == 0) return TEO_OK;
-    if (sk_ws && !sk_grid_fits_device()) sk_ws = nullptr;        // stream-K / hybrid grids are sized for 256 CUs
-    const bool swiglu = flags & TEO_GEMM_SWIGLU16;
-    if (swiglu && (bias || res || act != TEO_ACT_NONE || N % 32 != 0)) {
-        set_error("teo_gemm: SWIGLU16 needs N %% 32 == 0 and no bias/residual/act");
-        return TEO_ERR_ARG;
-    }
-    const bool f16 = dtype == TEO_F16;                       // the 16-bit format of this call, handed to the launch helper of every tile family
-    if (gemm_mfma_ok(M, N, K, lda, ldc, dtype, flags, A, W, bias, res, C)) {
-        // tile height: 128 rows; 64 rows only for small problems whose 128-row tiling leaves more than half of the 512
-        // resident workgroup slots empty (ViT o / fc2: 136 tiles; +7 % there).  Measured at M = 2168: 64-row tiles lose
-        // 10-25 % on every LLaMA shape (half the weight reuse per tile), wave quantisation notwithstanding.
-        const int tiles_n = cdiv(N, BN);
-        int bm = tune().gemm_bm;
-        if (bm == 0) bm = (cdiv(M, 128) * tiles_n <= 256 && !swiglu) ? 64 : 128;
-        const int tiles_m = cdiv(M, bm);
-        const int nwg = tiles_m * tiles_n;
-        const size_t lds = 4 * TILE_BYTES;
-        const bool of32 = out_dtype == TEO_F32;
-        // narrow LDS-DMA tiles (gemm_narrow.hip, round 5): forced here; the automatic rule sits below, after the families it competes with
-        if (tune().gemm_narrow == 2 && tune().gemm_narrow_pipe == 2 && swiglu)          // forced: the software-pipelined small tiles with the SwiGLU epilogue
-            return gemm_pipe_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, tune().gemm_narrow_bm == 128 ? 128 : 64, tune().gemm_pipe_bn,
-                                    tune().gemm_pipe_stages, st, true);
-        if (tune().gemm_narrow == 2 && !swiglu)
-            return gemm_narrow_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, tune().gemm_narrow_bm == 128 ? 128 : 64, st,
-                                      tune().gemm_narrow_bm == 128 && tune().gemm_narrow_waves == 8);
-        // gate/up + SwiGLU at M <= 128 (a text-only prompt): one or two row tiles of 128 x 256 leave two thirds of the CUs idle (86 / 172 tiles: 66-68 us);
-        // the software-pipelined small tiles carry the SwiGLU epilogue too -- 64 x 128 at M <= 64 (344 tiles: 42 us), 128 x 128 at M <= 128 (172
-        // tiles: 50 us); from M = 129 on the 128 x 256 / 256 x 256 tiles are ahead again (tools/dispatch_monotone.py, round 6)
-        if (swiglu && M <= 128 && K >= 2048 && tune().gemm_narrow == 1 && tune().gemm_narrow_pipe == 1 && tune().gemm_bm == 0 && tune().gemm_wide == 1 &&
-            tune().gemm_big == 1)
-            return gemm_pipe_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, M <= 64 ? 64 : 128, 128, 4, st, true);
-        if (tune().gemm_quad == 2 && !swiglu) return gemm_quad_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, st);      // forced (its rule: below)
-        // automatic: wherever the 64-row register-staged kernel was the choice (few tiles: the tower's out_proj / fc2, every tower GEMM and
-        // the LLaMA o / down projections of config C2) the 64 x 128 LDS-DMA tile runs instead -- tools/vit_gemm_probe.py (round 5, us):
-        // fc2 47.1 -> 36.5, out_proj 17.2 -> 14.6 (T = 8); at T = 2: fc2 42.6 -> 32.6, fc1 23.0 -> 18.6, LLaMA o 60.8 -> 39.2, down 148 -> 93
-        // round 6: with 192 .. 256 tiles of 128 x 128 (one per CU, three quarters of the chip or more), a long K loop and a wide N -- LLaMA
-        // o / down at M = 641 .. 1024 -- the EIGHT-wave 128 x 128 tile (two waves per SIMD on one tile per CU) beats the two four-wave 64 x 128
-        // tiles per CU: o 41.5-43.1 vs 53.2-55.0 us, down 107-109 vs 134-136 (tools/vit_gemm_probe.py); it loses at 160 tiles (M = 638: 41.0 /
-        // 103.4 vs 39.9 / 93.0) and on the tower's N = 1024 shapes (fc2 39.8 vs 37.0), which stay on the 64 x 128 tile
-        // round 6, late: the software-pipelined K loop on tiles sized for about ONE workgroup per CU (gemm_quad.hip gemm_pipe_launch; every
-        // candidate on every shape, weights from HBM: profiles/r06_pipe_candidates.txt; us, against the LDS-DMA tiles of gemm_narrow.hip).
-        // t64 / t128 / t96 / tq: tiles of 64 x 64 / 64 x 128 / 128 x 96 / 128 x 128.
-        //   t64 <= 288 (more with a short K loop): 64 x 64 -- LLaMA o / down at M <= 256 20 / 55 against 34 / 86; the tower at T <= 4: fc2 32-33 ->
-        //       15-18, out_proj 10.8 -> 6.3-6.6, qkv 11 -> 6.1-8.7, fc1 16 -> 9-11.6;
-        //   t128 <= 256: 64 x 128, ring of 4 (one per CU) for a long K loop -- o / down at M = 257 .. 512 28-31 / 79 against 35 / 86; fc2 at
-        //       T = 5 .. 7 27-31 against 33-35; out_proj at T = 5 .. 7 and qkv at T = 2 9.1-11.5 against 11.2-12.7;
-        //   t96 <= 256: 128 x 96 -- the tower's fc2 / out_proj at T = 8 .. 11 (187 .. 253 tiles) 31-36 / 12.4-13.4 against 41-43 / 15.3-16.1, qkv
-        //       at T = 3 .. 4 11 against 13.5-14; LLaMA o / down at M = 513 .. 640 (215 tiles, ring of 4) 30-36 / 77-90 against 41 / 90-92;
-        //   else, wide N and long K from 192 tiles of 128 x 128 on (o / down at M = 641 .. 1024): 128 x 128 -- 39-42 / 94-102 against 43-44 /
-        //       97-104 on the eight-wave LDS-DMA tile.
-        //   Not taken: a short K loop with an activation epilogue and more than 256 tiles of 64 x 128 (fc1 + GELU at T = 3 .. 4: one wave per
-        //   SIMD evaluates its 64-128 erf alone; the old 64 x 128 kernel's two workgroups per CU alternate: 18-19 against 20-25), and the
-        //   tower's N = 1024 shapes beyond 256 tiles of 128 x 96 (T >= 12: within 5 % either way).
-        if (tune().gemm_narrow == 1 && tune().gemm_narrow_pipe == 1 && tune().gemm_bm == 0 && tune().gemm_narrow_waves == 0 && bm == 64) {
-            const long long cm64 = cdiv(M, 64), cm128 = cdiv(M, 128);
-            const long long t64 = cm64 * cdiv(N, 64), t128 = cm64 * cdiv(N, 128), t96 = cm128 * cdiv(N, 96), tq = cm128 * tiles_n;
-            const bool long_wide = K >= 2048 && N >= 2048;
-            if (t64 <= 288 || (K <= 1024 && (t64 <= 384 || (N >= 2048 && t64 <= 512))))
-                return gemm_pipe_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, 64, 64, 4, st);
-            if (t128 <= 256)
-                return gemm_pipe_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, 64, 128, K >= 2048 ? 4 : 3, st);
-            if (!(K <= 1024 && act != TEO_ACT_NONE)) {
-                if (t96 <= 256)
-                    return gemm_pipe_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, 128, 96, long_wide ? 4 : 3, st);
-                if (long_wide && tq >= 192)
-                    return gemm_pipe_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, 128, 128, 3, st);
-            }
-        }
-        if (tune().gemm_narrow == 1 && tune().gemm_bm == 0 && tune().gemm_narrow_waves != 4 && bm == 64 && K >= 2048 && N >= 2048 &&
-            (long long)cdiv(M, 128) * tiles_n >= 192)
-            return gemm_narrow_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, 128, st, true);
-        if (tune().gemm_narrow == 1 && tune().gemm_bm == 0 && bm == 64)
-            return gemm_narrow_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, 64, st);
-        const long long t_wide_ = (long long)cdiv(M, 128) * cdiv(N, 256), t_big = gemm_big_tile_count(M, N, K);  // (counts a ragged last row block as 128 x 512 tiles)
-        // 256 x 160 tiles (gemm_quad.hip, round 5): automatic, and only while no other family is forced, where the problem is ONE round of
-        // them but more than one round of 128 x 256 tiles: M = 2056 .. 2304 against N = 4096 (272 wide tiles, 234 of these): LLaMA o / down at
-        // config C3, the tower's fc1.  tools/vit_gemm_probe.py (us, real epilogues): o 79.7 -> 71.3, down 178.6 -> 170.7, fc1 + GELU 39.5 -> 34.2
-        // on the eight-wave form (the default); the four-wave form (one wave per SIMD) ties it on o / down and loses 17 us on fc1 + GELU
-        const bool one_round_160 = !swiglu && tune().gemm_quad == 1 && tune().gemm_bm == 0 && tune().gemm_wide == 1 && tune().gemm_big == 1 &&
-                                   tune().gemm_sk == 1 && tune().gemm_narrow == 1 && K >= 8 * BK && t_wide_ > 256 &&
-                                   (long long)cdiv(M, 256) * cdiv(N, 160) <= std::min(device_cu_count(), 256);
-        if (one_round_160) return gemm_quad_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, st);
-        // just over one round of wide tiles -- or, for a short K loop (K <= 1024: the tower's fc1 at T = 16, 528 tiles), just over two:
-        // there a ragged third round costs a third of the launch (wide 86.7 us, its stream-K form 65.5; tools/vit_gemm_probe.py, round 5)
-        // round 6 (tools/shape_sweep.py, tools/dispatch_probe.py over M = 767 .. 3328): with a LONG K loop (K >= 2048: the LLaMA shapes) the
-        // stream-K form keeps winning up to 1.375 tiles per workgroup -- o / down at M = 2305 .. 2816 (304 .. 352 wide tiles) 86-97 / 208-242 us
-        // against 113-136 / 298-343 us on the 128 x 128 tiles the rounds model fell back to, qkv at M = 769 .. 896 (336 tiles) 93-95 vs 128-132
-        const long long sk_wide_rem = K >= 2048 ? 96 : 256 / 6;
-        const long long sk_wide_max = K <= 1024 ? 2 * 256 + 256 / 6 : 256 + sk_wide_rem;
-        const bool sk_wide_fit = t_wide_ > 256 && t_wide_ <= sk_wide_max && (t_wide_ % 256) != 0 && (t_wide_ % 256) <= sk_wide_rem;
-        const bool sk_wide_shape = sk_ws && tune().gemm_sk && tune().gemm_wide && !swiglu && sk_wide_fit;
-        // 256 x 256 tiles: a round of them costs GEMM_BIG_ROUND_COST rounds of the 128 x 256 kernel for twice the area (measured
-        // 1.45-1.7 us against 0.875 us per K tile); taken when that beats the wide kernel's round count and the chip is filled
-        // (with a workspace its hybrid form has no ragged last round: fractional rounds + a hand-off allowance)
-        const double big_rounds = (sk_ws && t_big > 256 && t_big % 256 != 0 && gemm_big_hybrid_fits(M, N, K)) ? (double)t_big / 256.0 + 0.12
-                                                                                                                 : (double)cdiv(t_big, 256);
-        // round 6: three quarters of a round of 256 x 256 tiles already beats the alternatives when the K loop is long (K >= 2048): qkv at
-        // M = 897 .. 1024 (192 tiles) 97-99 us vs 137-139 on 128 x 128 tiles, o / down at M = 2817 .. 3328 (192 / 208 tiles) 102-108 / 252-257 vs
-        // 122-142 / 300-365; and at EQUAL modelled cost the 256 x 256 tile is the one that measures ahead (gate/up at M = 2305 .. 2560: four
-        // rounds of them 393 us, seven rounds of 128 x 256 tiles 434-443) -- hence <=
-        // (tools/dispatch_monotone.py, round 6: a GEMM with more rows cannot be faster -- every inversion it found was a threshold here.)  192 tiles for
-        // every K (the tower's qkv at T = 15 / 16: 32.8 vs 37.6 us; fc1 / the projector at T = 12: 46.8 vs 52.1, 48.2 vs 50.0); 160 for the SwiGLU
-        // epilogue, whose only other families are the 128 x 256 tile and the register-staged 128 x 128 one (gate/up at M = 257 .. 512, 172 tiles:
-        // 92-94 us against 103-150)
-        // (late round 6, weights from HBM: 156 for the other epilogues too -- the tower's fc1 at T = 10 .. 11 (160 / 176 tiles) 47 us against 49-53 on the
-        // two-stage 128 x 128 LDS-DMA tile, qkv at T = 13 .. 15 (156 .. 180 tiles of 256 x 256: 13-15 x 12) 32-33 against 33-35)
-        const long long t_big_min = swiglu ? 160 : 156;
-        if (bm == 128 && K >= 2 * BK && (tune().gemm_big == 2 || (tune().gemm_big == 1 && tune().gemm_wide == 1 && t_big >= t_big_min && !sk_wide_shape &&
-                                                               big_rounds * GEMM_BIG_ROUND_COST <= (double)cdiv(t_wide_, 256))))
-            return gemm_big_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, swiglu, of32, f16, st, sk_ws, GEMM_SK_SLAB_BYTES);
-        {   // just over one round of WIDE tiles (272 on 256 CUs: o / down at M = 2168): the stream-K form of the wide kernel
-            const long long t_wide = (long long)cdiv(M, 128) * cdiv(N, 256);
-            if (sk_ws && tune().gemm_sk && tune().gemm_wide && bm == 128 && !swiglu && K >= 2 * BK && t_wide > 256 &&
-                (tune().gemm_sk == 2 || sk_wide_fit))
-                return gemm_wide_sk_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, sk_ws, GEMM_SK_SLAB_BYTES, st);
-        }
-        if (tune().gemm_wide && bm == 128 && gemm_wide_wins(M, N, K, tune().gemm_wide == 2, swiglu))
-            return gemm_wide_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, swiglu, of32, f16, st);
-        // stream-K where it was measured to win: just over ONE round of tiles (544 tiles on 512 slots at M = 2168, N = 4096:
-        // o 114 -> 93 us, down 297 -> 250 us).  With several tiles per workgroup the contiguous ranges spread an XCD's
-        // concurrent tiles over three times as many W panels as the plain kernel's rolling window does and the L2 misses
-        // cost more than the idle tail of the last round saves (qkv, 3.19 rounds: 255 -> 330 us; 1.5 rounds: 118 -> 130 us).
-        if (sk_ws && tune().gemm_sk && bm == 128 && nwg > SK_MAX_GRID &&
-            (tune().gemm_sk == 2 || (nwg < 2 * SK_MAX_GRID && (nwg % SK_MAX_GRID) <= SK_MAX_GRID / 6))) {
-            const int nk = K / BK;
-            const long long total = (long long)nwg * nk;
-            const int per = (int)((total + SK_MAX_GRID - 1) / SK_MAX_GRID);          // >= nk because nwg > SK_MAX_GRID
-            float* slabs = (float*)sk_ws;
-            int* flg = (int*)((unsigned char*)sk_ws + GEMM_SK_SLAB_BYTES);
-#define TEO_SK_LAUNCH_F(SW, OF, FV)                                                                                   \
-    gemm_mfma_bf16_sk_kernel<SW, OF, FV><<<SK_MAX_GRID, 256, lds, st>>>((const bf16_t*)A, (const bf16_t*)W, (const bf16_t*)bias,  \
-                                                                         (const bf16_t*)res, C, M, N, K, lda, ldc, act, tiles_m, \
-                                                                         tiles_n, per, slabs, flg)
-#define TEO_SK_LAUNCH(SW, OF) do { if (f16) TEO_SK_LAUNCH_F(SW, OF, true); else TEO_SK_LAUNCH_F(SW, OF, false); } while (0)
-            if (swiglu) { if (of32) TEO_SK_LAUNCH(true, true); else TEO_SK_LAUNCH(true, false); }
-            else { if (of32) TEO_SK_LAUNCH(false, true); else TEO_SK_LAUNCH(false, false); }
-#undef TEO_SK_LAUNCH
-#undef TEO_SK_LAUNCH_F
-            note_kernel("gemm_mfma_128_sk");
-            TEO_LAUNCH_CHECK("gemm_mfma_bf16_sk");
-            return TEO_OK;
-        }
-        // what no other family took: the 128 x 128 LDS-DMA tile instead of the register-staged one (the tower's fc2 / out_proj at T = 16:
-        // 75.5 -> 59.0 us, 25.8 -> 23.8); the register-staged kernel keeps the SwiGLU epilogue and stays the reference form of the tests
-        if (tune().gemm_narrow == 1 && tune().gemm_bm == 0 && bm == 128 && !swiglu)
-            return gemm_narrow_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, 128, st);
-        return gemm_plain_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, swiglu, of32, f16, bm, st);
-    }
+static int gemm_simple_launch(const GemmArgs& a, int dtype, int out_dtype, hipStream_t st) {
     if (dtype == TEO_F32) {
         if (out_dtype != TEO_F32) { set_error("teo_gemm: f32 inputs need f32 output"); return TEO_ERR_UNSUPPORTED; }
-        launch_simple<float, float>(A, W, bias, res, C, M, N, K, lda, ldc, act, swiglu, st);
+        launch_simple<float, float>(a, st);
     } else if (dtype == TEO_BF16) {
-        if (out_dtype == TEO_F32) launch_simple<bf16_t, float>(A, W, bias, res, C, M, N, K, lda, ldc, act, swiglu, st);
-        else launch_simple<bf16_t, bf16_t>(A, W, bias, res, C, M, N, K, lda, ldc, act, swiglu, st);
+        if (out_dtype == TEO_F32) launch_simple<bf16_t, float>(a, st);
+        else launch_simple<bf16_t, bf16_t>(a, st);
     } else if (dtype == TEO_F16) {
-        if (out_dtype == TEO_F32) launch_simple<f16_t, float>(A, W, bias, res, C, M, N, K, lda, ldc, act, swiglu, st);
-        else launch_simple<f16_t, f16_t>(A, W, bias, res, C, M, N, K, lda, ldc, act, swiglu, st);
+        if (out_dtype == TEO_F32) launch_simple<f16_t, float>(a, st);
+        else launch_simple<f16_t, f16_t>(a, st);
     } else {
         set_error("teo_gemm: unknown dtype %d", dtype);
         return TEO_ERR_UNSUPPORTED;
@@ -813,6 +597,69 @@ int gemm(const void* A, const void* W, const void* bias, const void* res, void* 
     note_kernel("gemm_simple");
     TEO_LAUNCH_CHECK("gemm_simple");
     return TEO_OK;
+}
+
+// the 128 x 128 (or 64 x 128) tile kernel, one workgroup per tile; register prefetch depth g.depth (the 64-row tile: 2)
+static int gemm_plain_launch(const GemmPlan& g, const GemmArgs& a, hipStream_t st) {
+    const int tiles_n = cdiv(a.N, BN), tiles_m = cdiv(a.M, g.bm);
+    const int nwg = tiles_m * tiles_n;
+    const size_t lds = 4 * TILE_BYTES;
+    with_flags([&](auto sw, auto of, auto fv) {
+        const auto one = [&](auto dp, auto mf) {
+            gemm_mfma_bf16_kernel<sw, of, decltype(dp)::value, decltype(mf)::value, fv><<<nwg, 256, lds, st>>>(
+                (const bf16_t*)a.A, (const bf16_t*)a.W, (const bf16_t*)a.bias, (const bf16_t*)a.res, a.C, a.M, a.N, a.K, a.lda, a.ldc, a.act, tiles_m, tiles_n);
+        };
+        if (g.bm == 64) one(int_c<2>{}, int_c<2>{});
+        else if (g.depth == 2) one(int_c<2>{}, int_c<4>{});
+        else one(int_c<1>{}, int_c<4>{});
+    }, a.swiglu, a.of32, a.f16);
+    note_kernel(g.bm == 64 ? "gemm_mfma_64" : "gemm_mfma_128");
+    TEO_LAUNCH_CHECK("gemm_mfma_bf16");
+    return TEO_OK;
+}
+
+// 128 x 128 stream-K: SK_MAX_GRID persistent workgroups, each over `per` consecutive k-tiles of the flattened (tile, k) sequence
+static int gemm_plain_sk_launch(const GemmArgs& a, hipStream_t st) {
+    const int tiles_n = cdiv(a.N, BN), tiles_m = cdiv(a.M, BM);
+    const int nwg = tiles_m * tiles_n;
+    const size_t lds = 4 * TILE_BYTES;
+    const int nk = a.K / BK;
+    const long long total = (long long)nwg * nk;
+    const int per = (int)((total + SK_MAX_GRID - 1) / SK_MAX_GRID);          // >= nk because nwg > SK_MAX_GRID
+    float* slabs = (float*)a.sk_ws;
+    int* flg = (int*)((unsigned char*)a.sk_ws + GEMM_SK_SLAB_BYTES);
+    with_flags([&](auto sw, auto of, auto fv) {
+        gemm_mfma_bf16_sk_kernel<sw, of, fv><<<SK_MAX_GRID, 256, lds, st>>>((const bf16_t*)a.A, (const bf16_t*)a.W, (const bf16_t*)a.bias,
+                                                                          (const bf16_t*)a.res, a.C, a.M, a.N, a.K, a.lda, a.ldc, a.act, tiles_m,
+                                                                          tiles_n, per, slabs, flg);
+    }, a.swiglu, a.of32, a.f16);
+    note_kernel("gemm_mfma_128_sk");
+    TEO_LAUNCH_CHECK("gemm_mfma_bf16_sk");
+    return TEO_OK;
+}
+
+int gemm(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda,
+         int ldc, int act, unsigned flags, int dtype, int out_dtype, hipStream_t st, void* sk_ws) {
+    if (M == 0 || N == 0) return TEO_OK;
+    const bool swiglu = flags & TEO_GEMM_SWIGLU16;
+    if (swiglu && (bias || res || act != TEO_ACT_NONE || N % 32 != 0)) {
+        set_error("teo_gemm: SWIGLU16 needs N %% 32 == 0 and no bias/residual/act");
+        return TEO_ERR_ARG;
+    }
+    const GemmProblem p{M, N, K, lda, ldc, act, flags, dtype, out_dtype, gemm_mfma_ok(M, N, K, lda, ldc, dtype, flags, A, W, bias, res, C)};
+    const GemmPlan g = plan_gemm(p, tune(), device_cu_count(), sk_ws != nullptr);
+    const GemmArgs a{A, W, bias, res, C, M, N, K, lda, ldc, act, swiglu, out_dtype == TEO_F32, dtype == TEO_F16, g.workspace ? sk_ws : nullptr};
+    switch (g.family) {
+    case GemmFamily::Plain: return gemm_plain_launch(g, a, st);
+    case GemmFamily::PlainSk: return gemm_plain_sk_launch(a, st);
+    case GemmFamily::Narrow: return gemm_narrow_launch(g, a, st);
+    case GemmFamily::Pipe: return gemm_pipe_launch(g, a, st);
+    case GemmFamily::Quad: return gemm_quad_launch(g, a, st);
+    case GemmFamily::Wide: return gemm_wide_launch(g, a, st);
+    case GemmFamily::WideSk: return gemm_wide_sk_launch(g, a, st);
+    case GemmFamily::Big: return gemm_big_launch(g, a, st);
+    default: return gemm_simple_launch(a, dtype, out_dtype, st);
+    }
 }
 
 }  // namespace teo

@@ -223,88 +223,28 @@ __global__ __launch_bounds__(512) void gemm_mfma_bf16_big_kernel(const bf16_t* _
     }   // segments
 }
 
-// tune().gemm_big_group (default 0): N panels per tile group (0: from the tile grid)
-// tune().gemm_big_cohort (default -1): stream-K part in XCD-local cohorts of this many workgroups: -1 auto (16 behind data-parallel rounds, else linear), 0 linear ranges, 8 / 16 / 32
-// tune().gemm_big_hybrid (default 1): data-parallel rounds + stream-K remainder when a workspace is given (1: if it fits MALL, 2: always)
-// ... or there are at most 1.5 tiles per workgroup (a pure stream-K grid whose workgroups mostly stay on one tile: down at M = 4208,
-// 272 tiles, 183 MB: 311 us against 421 us for three ragged rounds of 128 x 256 tiles)
-// tune().gemm_big_ragged (default 1): a last row block of <= 128 rows as 128 x 512 tiles (round 6): 0 = never (a padded 256-row tile), 1 = auto,
-// 2 = whenever the shape allows.  Auto = only where it turns the problem into ONE round of tiles: gate/up at M = 638 (config C2) is 258
-// padded tiles = a round and two tiles, 215 with the ragged form -- 104.9 us against 119.3 (hybrid) / 173.5 (two rounds).  Elsewhere the
-// tile count drops by 5.6 % but not the number of rounds, and a 128 x 512 tile moves 80 KB per K step instead of 64: measured
-// (tools/dispatch_probe.py, M = 2168 / 4208) qkv 193.8 vs 193.8 / 348 vs 356, gate/up 340-372 vs 333 / 620 vs 604 us -- a wash or a loss,
-// because the hybrid form's stream-K part grows when a data-parallel round disappears (731 tiles = 1 round + 475 instead of 2 + 262).
-// (bytes / tile-count rule of the hybrid form: see gemm_big_hybrid_fits below)
-static bool gb_hybrid_rule(long long T, long long bytes) { return bytes <= (160ll << 20) || T <= 384 || (T <= 800 && bytes <= (208ll << 20)); }
-// K > 0 adds the second automatic case: the ragged form saves a whole ROUND of the plain (non-hybrid) kernel where the hybrid form does not
-// apply to the padded problem anyway -- gate/up at M = 4353 .. 4480 (1548 -> 1505 tiles: seven rounds -> six; 637 us against 654 padded, 710 on
-// the 128 x 256 tile the rounds model fell back to)
-int gemm_big_ragged_tiles(int M, int N, int K) {
-    const int rows = M % GB_BM, tiles_n = (N + GB_BN - 1) / GB_BN, mode = tune().gemm_big_ragged;
-    if (!(mode && rows > 0 && rows <= GB_BM / 2 && tiles_n % 2 == 0 && M >= GB_BM)) return 0;
-    const long long t_rag = (long long)(M / GB_BM) * tiles_n + tiles_n / 2, t_full = (long long)(M / GB_BM + 1) * tiles_n;
-    bool take = mode == 2 || (t_rag <= 256 && t_full > 256);
-    if (!take && K > 0 && (t_rag + 255) / 256 < (t_full + 255) / 256) {
-        const bool hybrid_would_run = t_full > 256 && t_full % 256 != 0 && gb_hybrid_rule(t_full, ((long long)M + N) * K * 2);
-        take = !hybrid_would_run;
-    }
-    return take ? tiles_n / 2 : 0;
-}
-long long gemm_big_tile_count(int M, int N, int K) {
-    const int rt = gemm_big_ragged_tiles(M, N, K);
-    return (long long)(rt ? M / GB_BM : (M + GB_BM - 1) / GB_BM) * ((N + GB_BN - 1) / GB_BN) + rt;
-}
-
-bool gemm_big_hybrid_fits(int M, int N, int K) {
-    const long long T = gemm_big_tile_count(M, N, K);
-    const long long bytes = ((long long)M + N) * K * 2;
-    // round 3 (tools/split_probe.py): gate/up at M = 2168 (198 MB, 774 tiles = 3.02 rounds) runs 337 / 342 us (warm / cold weights) in
-    // the hybrid form against 358 / 363 on the 128 x 256 kernel -- with only three rounds the ragged one costs more than the
-    // unshared stream-K part; at M = 4208 (214 MB, 5.7 rounds) the hybrid form loses (712 vs 580 us)
-    return gb_hybrid_rule(T, bytes);
-}
-
-int gemm_big_launch(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda, int ldc,
-                    int act, bool swiglu, bool of32, bool f16, hipStream_t st, void* sk_ws, size_t flags_offset) {
-    const int tiles_n = cdiv(N, GB_BN);
-    const int rag_tiles = gemm_big_ragged_tiles(M, N, K);  // > 0: the last M % 256 <= 128 rows as tiles_n / 2 tiles of 128 x 512 (see the kernel)
-    const int tiles_m = rag_tiles ? M / GB_BM : cdiv(M, GB_BM);
-    const int T = tiles_m * tiles_n + rag_tiles, nk = K / GB_BK;
+// geometry from the plan (gemm_plan.hip: ragged tiles, group, hybrid form, data-parallel rounds, cohort)
+int gemm_big_launch(const GemmPlan& g, const GemmArgs& a, hipStream_t st) {
+    const int tiles_n = cdiv(a.N, GB_BN);
+    const int rag_tiles = g.ragged_tiles;  // > 0: the last M % 256 <= 128 rows as tiles_n / 2 tiles of 128 x 512 (see the kernel)
+    const int tiles_m = rag_tiles ? a.M / GB_BM : cdiv(a.M, GB_BM);
+    const int T = tiles_m * tiles_n + rag_tiles, nk = a.K / GB_BK;
     const size_t lds = rag_tiles ? 2 * (size_t)GB_RAG_STAGE : 2 * (size_t)GB_STAGE;
-    const int group = tune().gemm_big_group ? tune().gemm_big_group : (tiles_m >= 16 ? 4 : 1);
-    // hybrid form when the tile count is not a whole number of rounds -- and the operands fit the 256 MB Infinity Cache: the
-    // stream-K part has every workgroup at its own (tile, k), nothing is shared through L2, and once A + W no longer sit in MALL its
-    // K tiles take twice as long as the data-parallel ones (measured: gate/up at M = 4208, 214 MB: 712 us vs 580; at M = 2168 qkv,
-    // 118 MB: 195 vs 203; gemm_big_hybrid = 2 forces it)
-    const bool hybrid = sk_ws && tune().gemm_big_hybrid && T > 256 && T % 256 != 0 && (tune().gemm_big_hybrid == 2 || gemm_big_hybrid_fits(M, N, K));
-    const int dp_rounds = hybrid ? T / 256 - 1 : 0;
-    // cohort form: columns of `cohort` tiles, 256 / cohort chain links; a link's range must cover a whole tile (per >= nk), else linear.
-    // Measured (tools/bench_kernels.py gemm_cohort, cold weights, us; linear / 8 / 16 / 32): gate/up at M = 2168 (2 rounds + 262 tiles)
-    // 342.9 / 324.9 / 322.1 / 329.4, qkv at M = 4208 (2 + 304) 392.6 / 366.1 / 360.7 / 369.4, gate/up at M = 4208 (4 + 438) 723.6 / 609.1 /
-    // 601.3 / 596.9; with NO data-parallel round in front the linear ranges stay ahead or level (qkv at M = 2168, 432 tiles: 197.6 /
-    // 208.1 / 202.1 / 212.1; gate/up at M = 638, 258 tiles: 117.2 / 123.8 / 126.9 / 135.0; down at M = 4208, 272 tiles: 305.8 / 301.1 /
-    // 295.1 / 308.3) -> auto = 16 behind at least one data-parallel round
-    int cohort = !hybrid ? 0 : (tune().gemm_big_cohort >= 0 ? tune().gemm_big_cohort : (dp_rounds >= 1 ? 16 : 0));
-    if (cohort && cdiv(T - dp_rounds * 256, cohort) < 256 / cohort) cohort = 0;
+    const bool hybrid = g.hybrid;
+    const int dp_rounds = g.dp_rounds, cohort = g.cohort;
+    // stream-K ranges: a cohort of `cohort` columns has 256 / cohort chain links, each covering per >= nk k-tiles; else linear ranges
     const int per = !hybrid ? 0 : cohort ? cdiv((long long)cdiv(T - dp_rounds * 256, cohort) * nk, 256 / cohort)
                                          : (int)(((long long)(T - dp_rounds * 256) * nk + 255) / 256);
-    float* slabs = (float*)sk_ws;
-    int* flg = hybrid ? (int*)((unsigned char*)sk_ws + flags_offset) : nullptr;
-#define TEO_GB_LAUNCH_H(SW, OF, HY) { if (f16) TEO_GB_LAUNCH_HF(SW, OF, HY, true) else TEO_GB_LAUNCH_HF(SW, OF, HY, false) }
-#define TEO_GB_LAUNCH_HF(SW, OF, HY, FV)                                                                                          \
-    {                                                                                                                             \
-        static unsigned long long attr_mask = 0;                                                                                  \
-        if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_bf16_big_kernel<SW, OF, HY, FV>), 2 * GB_RAG_STAGE, &attr_mask, "gemm_big")) return e; \
-        gemm_mfma_bf16_big_kernel<SW, OF, HY, FV><<<(HY) ? 256 : T, 512, lds, st>>>((const bf16_t*)A, (const bf16_t*)W, (const bf16_t*)bias, \
-                                                                               (const bf16_t*)res, C, M, N, K, lda, ldc, act, tiles_m,  \
-                                                                               tiles_n, group, dp_rounds, per, slabs, flg, cohort, rag_tiles); \
-    }
-#define TEO_GB_LAUNCH(SW, OF) { if (hybrid) TEO_GB_LAUNCH_H(SW, OF, true) else TEO_GB_LAUNCH_H(SW, OF, false) }
-    if (swiglu) { if (of32) TEO_GB_LAUNCH(true, true) else TEO_GB_LAUNCH(true, false) }
-    else { if (of32) TEO_GB_LAUNCH(false, true) else TEO_GB_LAUNCH(false, false) }
-#undef TEO_GB_LAUNCH
-#undef TEO_GB_LAUNCH_H
-#undef TEO_GB_LAUNCH_HF
+    float* slabs = (float*)a.sk_ws;
+    int* flg = hybrid ? (int*)((unsigned char*)a.sk_ws + GEMM_SK_SLAB_BYTES) : nullptr;
+    const int e = with_flags([&](auto sw, auto of, auto hy, auto fv) {
+        static unsigned long long attr_mask = 0;
+        if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_bf16_big_kernel<sw, of, hy, fv>), 2 * GB_RAG_STAGE, &attr_mask, "gemm_big")) return e;
+        gemm_mfma_bf16_big_kernel<sw, of, hy, fv><<<hy ? 256 : T, 512, lds, st>>>((const bf16_t*)a.A, (const bf16_t*)a.W, (const bf16_t*)a.bias, (const bf16_t*)a.res, a.C, a.M, a.N,
+                                               a.K, a.lda, a.ldc, a.act, tiles_m, tiles_n, g.group, dp_rounds, per, slabs, flg, cohort, rag_tiles);
+        return (int)TEO_OK;
+    }, a.swiglu, a.of32, hybrid, a.f16);
+    if (e) return e;
     note_kernel(hybrid ? (cohort ? "gemm_big_hybrid_cohort" : "gemm_big_hybrid") : "gemm_big");
     TEO_LAUNCH_CHECK("gemm_mfma_bf16_big");
     return TEO_OK;

@@ -571,10 +571,6 @@ __global__ __launch_bounds__(512) void gemm_mfma_fp8_big_kernel(const unsigned c
     }
 }
 
-// tune().gemm_fp8_big (default 1): 256 x 256 kernel: 0 off, 1 auto (rounds model), 2 forced
-constexpr double F8_BIG_ROUND_COST = 1.66;   // measured: 58.4 us per round of 256 x 256 tiles vs 35.3 us per round of 128 x 256 (gate/up at M = 17344)
-// tune().gemm_fp8_wide (default 1): 0: 128 x 128 kernel only, 1: by the rounds model, 2: wide wherever K has two tiles
-
 bool gemm_fp8_ok(int M, int N, int K, int lda, int ldc, unsigned flags, const void* A, const void* W, const void* res, const void* C) {
     if (M < 1 || N < 1 || K % F8_BK != 0 || lda % 16 != 0 || ldc % 4 != 0 || N % 4 != 0) return false;
     if ((flags & TEO_GEMM_SWIGLU16) && (N % 32 != 0 || res)) return false;
@@ -582,90 +578,70 @@ bool gemm_fp8_ok(int M, int N, int K, int lda, int ldc, unsigned flags, const vo
     return al(A, 16) && al(W, 16) && al(res, 8) && al(C, 16);
 }
 
+// the family and its tile group come from plan_gemm_fp8 (gemm_plan.hip)
 int gemm_fp8(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* res, void* C, int M, int N, int K,
              int lda, int ldc, unsigned flags, int out_dtype, hipStream_t st, void* sk_ws) {
     if (M == 0 || N == 0) return TEO_OK;
-    if (sk_ws) {                                             // the stream-K form is sized for 256 CUs
-        if (device_cu_count() != 256) sk_ws = nullptr;
-    }
-    if (!gemm_fp8_ok(M, N, K, lda, ldc, flags, A8, W8, res, C)) {
+    const GemmProblem p{M, N, K, lda, ldc, TEO_ACT_NONE, flags, TEO_F32, out_dtype, gemm_fp8_ok(M, N, K, lda, ldc, flags, A8, W8, res, C)};
+    const GemmPlan g = plan_gemm_fp8(p, tune(), device_cu_count(), sk_ws != nullptr);
+    if (g.family == GemmFamily::Invalid) {
         set_error("teo_gemm_fp8: needs K %% 128 == 0, lda %% 16 == 0, N %% 4 == 0 (32 with SWIGLU16, no residual) and 16-byte aligned operands "
                   "(M %d N %d K %d lda %d ldc %d)", M, N, K, lda, ldc);
         return TEO_ERR_UNSUPPORTED;
     }
     const bool swiglu = flags & TEO_GEMM_SWIGLU16;
     const bool of32 = out_dtype == TEO_F32;
-    {   // wide tiles when they need fewer (cost-weighted) rounds: same model as the bf16 kernel (gemm.hip gemm_wide_wins)
-        const long long t_wide = (long long)cdiv(M, F8W_BM) * cdiv(N, F8W_BN), t_plain = (long long)cdiv(M, F8_BM) * cdiv(N, F8_BN);
-        const long long rem = t_plain % 512;
-        const double plain = (double)(t_plain / 512) + (rem == 0 ? 0.0 : (rem <= 256 ? 0.66 : 1.0));
-        const double wide = (double)cdiv(t_wide, 256) * 0.80;   // measured: a wide fp8 round costs ~0.8 of a 128 x 128 round (o: 76 vs 81 us, gate/up 219 vs 272)
-        const bool sk_shape = sk_ws && tune().gemm_fp8_wide && !swiglu && K >= 2 * F8_BK && t_wide > 256 && (tune().gemm_fp8_wide == 3 || t_wide <= 256 + 256 / 6);
-        const long long t_big = (long long)cdiv(M, F8B_BM) * cdiv(N, F8B_BN);
-        if (K >= 2 * F8_BK && (tune().gemm_fp8_big == 2 || (tune().gemm_fp8_big == 1 && tune().gemm_fp8_wide == 1 && t_big >= 160 && !sk_shape &&
-                                                  cdiv(t_big, 256) * F8_BIG_ROUND_COST < (double)cdiv(t_wide, 256)))) {
-            const int tiles_m = cdiv(M, F8B_BM), tiles_n = cdiv(N, F8B_BN);
-            const size_t lds = 2 * F8B_STAGE;
-            const int group = tiles_m >= 16 ? 4 : 1;
-#define TEO_F8B_LAUNCH(SW, OF)                                                                                                  \
-    {                                                                                                                           \
-        static unsigned long long attr_mask = 0;                                                                                \
-        if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_fp8_big_kernel<SW, OF>), (int)lds, &attr_mask, "gemm_fp8 big")) return e; \
-        gemm_mfma_fp8_big_kernel<SW, OF><<<tiles_m * tiles_n, 512, lds, st>>>((const unsigned char*)A8, a_scale, (const unsigned char*)W8, \
-                                                                             w_scale, (const bf16_t*)res, C, M, N, K, lda, ldc, tiles_m, tiles_n, group); \
+    const auto A = (const unsigned char*)A8, W = (const unsigned char*)W8;
+    const auto R = (const bf16_t*)res;
+    if (g.family == GemmFamily::Fp8Big) {
+        const int tiles_m = cdiv(M, F8B_BM), tiles_n = cdiv(N, F8B_BN);
+        const size_t lds = 2 * F8B_STAGE;
+        const int e = with_flags([&](auto sw, auto of) {
+            static unsigned long long attr_mask = 0;
+            if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_fp8_big_kernel<sw, of>), (int)lds, &attr_mask, "gemm_fp8 big")) return e;
+            gemm_mfma_fp8_big_kernel<sw, of><<<tiles_m * tiles_n, 512, lds, st>>>(A, a_scale, W, w_scale, R, C, M, N, K, lda, ldc, tiles_m, tiles_n, g.group);
+            return (int)TEO_OK;
+        }, swiglu, of32);
+        if (e) return e;
+        note_kernel("gemm_fp8_big"); TEO_LAUNCH_CHECK("gemm_mfma_fp8_big");
+        return TEO_OK;
     }
-            if (swiglu) { if (of32) TEO_F8B_LAUNCH(true, true) else TEO_F8B_LAUNCH(true, false) }
-            else { if (of32) TEO_F8B_LAUNCH(false, true) else TEO_F8B_LAUNCH(false, false) }
-#undef TEO_F8B_LAUNCH
-            note_kernel("gemm_fp8_big"); TEO_LAUNCH_CHECK("gemm_mfma_fp8_big");
-            return TEO_OK;
-        }
-        if (sk_shape) {
-            // just over one round of wide tiles: persistent stream-K grid (slabs: 256 x 128 KB, flags behind GEMM_SK_SLAB_BYTES as in gemm.hip)
-            const int tiles_m = cdiv(M, F8W_BM), tiles_n = cdiv(N, F8W_BN);
-            const long long total = (long long)tiles_m * tiles_n * (K / F8_BK);
-            const int per = (int)((total + 255) / 256);
-            const size_t lds = 3 * F8W_STAGE;
-            float* slabs = (float*)sk_ws;
-            int* flg = (int*)((unsigned char*)sk_ws + GEMM_SK_SLAB_BYTES);
-#define TEO_F8SK_LAUNCH(OF)                                                                                                     \
-    {                                                                                                                           \
-        static unsigned long long attr_mask = 0;                                                                                \
-        if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_fp8_wide_sk_kernel<OF>), (int)lds, &attr_mask, "gemm_fp8 wide sk")) return e; \
-        gemm_mfma_fp8_wide_sk_kernel<OF><<<256, 512, lds, st>>>((const unsigned char*)A8, a_scale, (const unsigned char*)W8, w_scale, \
-                                                               (const bf16_t*)res, C, M, N, K, lda, ldc, tiles_m, tiles_n, per, slabs, flg); \
+    if (g.family == GemmFamily::Fp8WideSk) {
+        // persistent stream-K grid (slabs: 256 x 128 KB, flags behind GEMM_SK_SLAB_BYTES as in gemm.hip)
+        const int tiles_m = cdiv(M, F8W_BM), tiles_n = cdiv(N, F8W_BN);
+        const long long total = (long long)tiles_m * tiles_n * (K / F8_BK);
+        const int per = (int)((total + 255) / 256);
+        const size_t lds = 3 * F8W_STAGE;
+        float* slabs = (float*)sk_ws;
+        int* flg = (int*)((unsigned char*)sk_ws + GEMM_SK_SLAB_BYTES);
+        const int e = with_flags([&](auto of) {
+            static unsigned long long attr_mask = 0;
+            if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_fp8_wide_sk_kernel<of>), (int)lds, &attr_mask, "gemm_fp8 wide sk")) return e;
+            gemm_mfma_fp8_wide_sk_kernel<of><<<256, 512, lds, st>>>(A, a_scale, W, w_scale, R, C, M, N, K, lda, ldc, tiles_m, tiles_n, per, slabs, flg);
+            return (int)TEO_OK;
+        }, of32);
+        if (e) return e;
+        note_kernel("gemm_fp8_wide_sk"); TEO_LAUNCH_CHECK("gemm_mfma_fp8_wide_sk");
+        return TEO_OK;
     }
-            if (of32) TEO_F8SK_LAUNCH(true) else TEO_F8SK_LAUNCH(false)
-#undef TEO_F8SK_LAUNCH
-            note_kernel("gemm_fp8_wide_sk"); TEO_LAUNCH_CHECK("gemm_mfma_fp8_wide_sk");
-            return TEO_OK;
-        }
-        if (K >= 2 * F8_BK && (tune().gemm_fp8_wide >= 2 || (tune().gemm_fp8_wide == 1 && wide < plain && (t_wide >= 256 || (t_wide >= 144 && t_plain > 256))))) {
-            const int tiles_m = cdiv(M, F8W_BM), tiles_n = cdiv(N, F8W_BN);
-            const size_t lds = 3 * F8W_STAGE;
-#define TEO_F8W_LAUNCH(SW, OF)                                                                                                  \
-    {                                                                                                                           \
-        static unsigned long long attr_mask = 0;                                                                                \
-        if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_fp8_wide_kernel<SW, OF>), (int)lds, &attr_mask, "gemm_fp8 wide")) return e; \
-        gemm_mfma_fp8_wide_kernel<SW, OF><<<tiles_m * tiles_n, 512, lds, st>>>((const unsigned char*)A8, a_scale, (const unsigned char*)W8, \
-                                                                              w_scale, (const bf16_t*)res, C, M, N, K, lda, ldc, tiles_m, tiles_n); \
-    }
-            if (swiglu) { if (of32) TEO_F8W_LAUNCH(true, true) else TEO_F8W_LAUNCH(true, false) }
-            else { if (of32) TEO_F8W_LAUNCH(false, true) else TEO_F8W_LAUNCH(false, false) }
-#undef TEO_F8W_LAUNCH
-            note_kernel("gemm_fp8_wide"); TEO_LAUNCH_CHECK("gemm_mfma_fp8_wide");
-            return TEO_OK;
-        }
+    if (g.family == GemmFamily::Fp8Wide) {
+        const int tiles_m = cdiv(M, F8W_BM), tiles_n = cdiv(N, F8W_BN);
+        const size_t lds = 3 * F8W_STAGE;
+        const int e = with_flags([&](auto sw, auto of) {
+            static unsigned long long attr_mask = 0;
+            if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_fp8_wide_kernel<sw, of>), (int)lds, &attr_mask, "gemm_fp8 wide")) return e;
+            gemm_mfma_fp8_wide_kernel<sw, of><<<tiles_m * tiles_n, 512, lds, st>>>(A, a_scale, W, w_scale, R, C, M, N, K, lda, ldc, tiles_m, tiles_n);
+            return (int)TEO_OK;
+        }, swiglu, of32);
+        if (e) return e;
+        note_kernel("gemm_fp8_wide"); TEO_LAUNCH_CHECK("gemm_mfma_fp8_wide");
+        return TEO_OK;
     }
     const int tiles_m = cdiv(M, F8_BM), tiles_n = cdiv(N, F8_BN);
-    const int nwg = tiles_m * tiles_n;
     const size_t lds = 4 * F8_TILE;
-#define TEO_F8_LAUNCH(SW, OF)                                                                                               \
-    gemm_mfma_fp8_kernel<SW, OF><<<nwg, 256, lds, st>>>((const unsigned char*)A8, a_scale, (const unsigned char*)W8, w_scale,  \
-                                                        (const bf16_t*)res, C, M, N, K, lda, ldc, tiles_m, tiles_n)
-    if (swiglu) { if (of32) TEO_F8_LAUNCH(true, true); else TEO_F8_LAUNCH(true, false); }
-    else { if (of32) TEO_F8_LAUNCH(false, true); else TEO_F8_LAUNCH(false, false); }
-#undef TEO_F8_LAUNCH
+    with_flags([&](auto sw, auto of) {
+        gemm_mfma_fp8_kernel<sw, of><<<tiles_m * tiles_n, 256, lds, st>>>(A, a_scale, W, w_scale, R, C, M, N, K, lda, ldc, tiles_m, tiles_n);
+    }, swiglu, of32);
     note_kernel("gemm_fp8_128"); TEO_LAUNCH_CHECK("gemm_mfma_fp8");
     return TEO_OK;
 }

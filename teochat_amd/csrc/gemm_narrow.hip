@@ -123,29 +123,26 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 ? 2 : 1)) void gemm_mfm
 // SIMD) -- round 6, for problems with at most ONE such tile per CU (LLaMA o / down at M <= 1024, the tower's fc2 / out_proj): a lone
 // four-wave workgroup leaves every SIMD one wave whose MFMA chain waits for its own fragment reads (0.95 us per K step measured on a
 // 128 x 128 tile alone on its CU); with two waves per SIMD one reads while the other multiplies.
-int gemm_narrow_launch(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda, int ldc,
-                       int act, bool of32, bool f16, int bm, hipStream_t st, bool waves8) {
-    // forced: the software-pipelined form of the same tiles (gemm_quad.hip gemm_pipe_launch; its automatic rule is in gemm.hip)
-    if (tune().gemm_narrow_pipe == 2)
-        return gemm_pipe_launch(A, W, bias, res, C, M, N, K, lda, ldc, act, of32, f16, bm, tune().gemm_pipe_bn, tune().gemm_pipe_stages, st);
-    const int bn = 128;
-    const int tiles_m = cdiv(M, bm), tiles_n = cdiv(N, bn);
+int gemm_narrow_launch(const GemmPlan& g, const GemmArgs& a, hipStream_t st) {
+    const int bm = g.bm, bn = 128;
+    const int tiles_m = cdiv(a.M, bm), tiles_n = cdiv(a.N, bn);
     const int nwg = tiles_m * tiles_n;
-#define TEO_GN_LAUNCH_T(TBM, TBN, WM, WN, NS, OF, FV)                                                                             \
-    {                                                                                                                             \
-        constexpr size_t lds = (size_t)(NS) * ((TBM) * GN_BK * 2 + (TBN) * GN_BK * 2);                                            \
-        static unsigned long long attr_mask = 0;                                                                                  \
-        if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_bf16_narrow_kernel<TBM, TBN, WM, WN, NS, OF, FV>), (int)lds, &attr_mask, "gemm_narrow")) return e; \
-        gemm_mfma_bf16_narrow_kernel<TBM, TBN, WM, WN, NS, OF, FV><<<nwg, (WM) * (WN) * 64, lds, st>>>((const bf16_t*)A, (const bf16_t*)W, (const bf16_t*)bias,  \
-                                                                          (const bf16_t*)res, C, M, N, K, lda, ldc, act, tiles_m, tiles_n); \
-    }
-#define TEO_GN_LAUNCH_F(TBM, TBN, WM, WN, NS, OF) { if (f16) TEO_GN_LAUNCH_T(TBM, TBN, WM, WN, NS, OF, true) else TEO_GN_LAUNCH_T(TBM, TBN, WM, WN, NS, OF, false) }
-#define TEO_GN_LAUNCH(TBM, TBN, WM, WN, NS) { if (of32) TEO_GN_LAUNCH_F(TBM, TBN, WM, WN, NS, true) else TEO_GN_LAUNCH_F(TBM, TBN, WM, WN, NS, false) }
-    if (bm == 64) TEO_GN_LAUNCH(64, 128, 2, 2, 3) else if (waves8) TEO_GN_LAUNCH(128, 128, 2, 4, 3) else TEO_GN_LAUNCH(128, 128, 2, 2, 2)
-#undef TEO_GN_LAUNCH
-#undef TEO_GN_LAUNCH_F
-#undef TEO_GN_LAUNCH_T
-    note_kernel(bm == 64 ? "gemm_narrow_64" : (waves8 ? "gemm_narrow_128w8" : "gemm_narrow_128"));
+    const int e = with_flags([&](auto of, auto fv) {
+        const auto one = [&](auto tbm, auto wn, auto ns) {      // TBM x 128 tiles on 2 x WN waves, NS stages
+            constexpr int TBM = decltype(tbm)::value, WN = decltype(wn)::value, NS = decltype(ns)::value;
+            constexpr size_t lds = (size_t)NS * (TBM * GN_BK * 2 + 128 * GN_BK * 2);
+            static unsigned long long attr_mask = 0;
+            if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_bf16_narrow_kernel<TBM, 128, 2, WN, NS, of, fv>), (int)lds, &attr_mask, "gemm_narrow")) return e;
+            gemm_mfma_bf16_narrow_kernel<TBM, 128, 2, WN, NS, of, fv><<<nwg, 2 * WN * 64, lds, st>>>((const bf16_t*)a.A, (const bf16_t*)a.W, (const bf16_t*)a.bias,
+                                                                          (const bf16_t*)a.res, a.C, a.M, a.N, a.K, a.lda, a.ldc, a.act, tiles_m, tiles_n);
+            return (int)TEO_OK;
+        };
+        if (bm == 64) return one(int_c<64>{}, int_c<2>{}, int_c<3>{});      // 64 x 128, four waves, 3 stages
+        if (g.waves8) return one(int_c<128>{}, int_c<4>{}, int_c<3>{});     // 128 x 128, eight waves, 3 stages
+        return one(int_c<128>{}, int_c<2>{}, int_c<2>{});                   // 128 x 128, four waves, 2 stages
+    }, a.of32, a.f16);
+    if (e) return e;
+    note_kernel(bm == 64 ? "gemm_narrow_64" : (g.waves8 ? "gemm_narrow_128w8" : "gemm_narrow_128"));
     TEO_LAUNCH_CHECK("gemm_mfma_bf16_narrow");
     return TEO_OK;
 }

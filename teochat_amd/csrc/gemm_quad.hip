@@ -178,29 +178,23 @@ __global__ __launch_bounds__(WM * 128) __attribute__((amdgpu_waves_per_eu(WM / 2
     gemm_epilogue<NI, MI, (MI % 4 == 0 ? 4 : MI), SWIGLU, OUT_F32, F16>(acc, bv, bias != nullptr, res, Cv, M, N, ldc, act, m0 + wm * (MI * 16), n0 + wn * (NI * 16), fr, fg);
 }
 
-// 256 x 160 tiles, 3 stages (156 KB: one workgroup per CU), eight or four waves (tune().gemm_quad_waves).  No SwiGLU form (gate / up run
+// 256 x 160 tiles, 3 stages (156 KB: one workgroup per CU), eight or four waves (gemm_quad_waves, chosen by the plan).  No SwiGLU form (gate / up run
 // several rounds: the 256 x 256 hybrid's shapes)
-int gemm_quad_launch(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda, int ldc,
-                     int act, bool of32, bool f16, hipStream_t st) {
-    const bool eight = tune().gemm_quad_waves != 4;          // default: eight waves (two per SIMD); 4: one wave per SIMD, 128 x 80 each
+int gemm_quad_launch(const GemmPlan& g, const GemmArgs& a, hipStream_t st) {
     constexpr int NI = 5, NS = 3, TN = 32 * NI;
-    const int tiles_m = cdiv(M, GQ_BM), tiles_n = cdiv(N, TN);
+    const int tiles_m = cdiv(a.M, GQ_BM), tiles_n = cdiv(a.N, TN);
     const int nwg = tiles_m * tiles_n;
     constexpr size_t lds = (size_t)NS * (GQ_BM + TN) * 128;
-#define TEO_GQ_LAUNCH_W(OF, FV, WMV)                                                                                              \
-    {                                                                                                                             \
-        static unsigned long long attr_mask = 0;                                                                                  \
-        if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_bf16_quad_kernel<GQ_BM, NI, NS, WMV, (WMV) / 2, OF, FV>), (int)lds, &attr_mask, "gemm_quad")) return e; \
-        gemm_mfma_bf16_quad_kernel<GQ_BM, NI, NS, WMV, (WMV) / 2, OF, FV><<<nwg, (WMV) * 128, lds, st>>>((const bf16_t*)A, (const bf16_t*)W, (const bf16_t*)bias, \
-                                                                          (const bf16_t*)res, C, M, N, K, lda, ldc, act, tiles_m, tiles_n); \
-    }
-#define TEO_GQ_LAUNCH_T(OF, FV) { if (eight) TEO_GQ_LAUNCH_W(OF, FV, 4) else TEO_GQ_LAUNCH_W(OF, FV, 2) }
-#define TEO_GQ_LAUNCH_F(OF) { if (f16) TEO_GQ_LAUNCH_T(OF, true) else TEO_GQ_LAUNCH_T(OF, false) }
-    if (of32) TEO_GQ_LAUNCH_F(true) else TEO_GQ_LAUNCH_F(false)
-#undef TEO_GQ_LAUNCH_F
-#undef TEO_GQ_LAUNCH_T
-#undef TEO_GQ_LAUNCH_W
-    note_kernel(eight ? "gemm_quad_160" : "gemm_quad_160_w4");
+    const int e = with_flags([&](auto of, auto fv, auto eight) {     // eight waves (two per SIMD) or four (one per SIMD, 128 x 80 each)
+        constexpr int WM = eight ? 4 : 2;
+        static unsigned long long attr_mask = 0;
+        if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_bf16_quad_kernel<GQ_BM, NI, NS, WM, WM / 2, of, fv>), (int)lds, &attr_mask, "gemm_quad")) return e;
+        gemm_mfma_bf16_quad_kernel<GQ_BM, NI, NS, WM, WM / 2, of, fv><<<nwg, WM * 128, lds, st>>>((const bf16_t*)a.A, (const bf16_t*)a.W, (const bf16_t*)a.bias,
+                                                                          (const bf16_t*)a.res, a.C, a.M, a.N, a.K, a.lda, a.ldc, a.act, tiles_m, tiles_n);
+        return (int)TEO_OK;
+    }, a.of32, a.f16, g.waves8);
+    if (e) return e;
+    note_kernel(g.waves8 ? "gemm_quad_160" : "gemm_quad_160_w4");
     TEO_LAUNCH_CHECK("gemm_mfma_bf16_quad");
     return TEO_OK;
 }
@@ -216,38 +210,32 @@ int gemm_quad_launch(const void* A, const void* W, const void* bias, const void*
 // Same LDS image, fragment reads and k-ascending chain: bit-identical to every other family (tests/test_gemm_fuzz_gpu.py).
 // bm 64: tn 64 (ring of 4 = 64 KB: two per CU) or 128 (ring of 3 = 72 KB: two per CU; ring of 4 = 96 KB: one per CU, for launches of at most
 // one workgroup per CU with a long K loop); bm 128: tn 96 (ring of 3 = 84 KB or 4 = 112 KB) or 128 (ring of 3 = 96 KB): one per CU
-int gemm_pipe_launch(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda, int ldc,
-                     int act, bool of32, bool f16, int bm, int tn, int ns, hipStream_t st, bool swiglu) {
-    if (bm != 128) bm = 64;
-    if (swiglu && tn == 96) tn = 128;                    // the SwiGLU epilogue pairs 16-column blocks: an even number of them per wave
-    if (bm == 128) tn = tn == 96 ? 96 : 128;
-    else if (tn != 64) tn = 128;
-    ns = (bm == 128) ? (tn == 96 && ns == 4 ? 4 : 3) : (tn == 64 ? 4 : (ns == 4 ? 4 : 3));
-    const int tiles_m = cdiv(M, bm), tiles_n = cdiv(N, tn);
+// tile (bm x tn) and ring depth from the plan (gemm_plan.hip pipe(): one of the forms above)
+int gemm_pipe_launch(const GemmPlan& g, const GemmArgs& a, hipStream_t st) {
+    const int bm = g.bm, tn = g.tn, ns = g.stages;
+    const int tiles_m = cdiv(a.M, bm), tiles_n = cdiv(a.N, tn);
     const int nwg = tiles_m * tiles_n;
-#define TEO_GP_LAUNCH_S(OF, FV, BMV, NIV, NSV, OCCV, SWV)                                                                         \
-    {                                                                                                                             \
-        constexpr size_t lds = (size_t)(NSV) * ((BMV) + 32 * (NIV)) * 128;                                                        \
-        static unsigned long long attr_mask = 0;                                                                                  \
-        if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_bf16_quad_kernel<BMV, NIV, NSV, 2, OCCV, OF, FV, SWV>), (int)lds, &attr_mask, "gemm_pipe")) return e; \
-        gemm_mfma_bf16_quad_kernel<BMV, NIV, NSV, 2, OCCV, OF, FV, SWV><<<nwg, 256, lds, st>>>((const bf16_t*)A, (const bf16_t*)W, (const bf16_t*)bias, \
-                                                                          (const bf16_t*)res, C, M, N, K, lda, ldc, act, tiles_m, tiles_n); \
-    }
-#define TEO_GP_LAUNCH_W(OF, FV, BMV, NIV, NSV, OCCV) { if (swiglu) TEO_GP_LAUNCH_S(OF, FV, BMV, NIV, NSV, OCCV, true) else TEO_GP_LAUNCH_S(OF, FV, BMV, NIV, NSV, OCCV, false) }
-#define TEO_GP_LAUNCH_T(OF, FV)                                                                                                   \
-    {                                                                                                                             \
-        if (bm == 128 && tn == 96) { if (ns == 4) TEO_GP_LAUNCH_S(OF, FV, 128, 3, 4, 1, false) else TEO_GP_LAUNCH_S(OF, FV, 128, 3, 3, 1, false) } \
-        else if (bm == 128) TEO_GP_LAUNCH_W(OF, FV, 128, 4, 3, 1)                                                                 \
-        else if (tn == 64) TEO_GP_LAUNCH_W(OF, FV, 64, 2, 4, 2)                                                                   \
-        else if (ns == 4) TEO_GP_LAUNCH_W(OF, FV, 64, 4, 4, 2)                                                                    \
-        else TEO_GP_LAUNCH_W(OF, FV, 64, 4, 3, 2)                                                                                 \
-    }
-#define TEO_GP_LAUNCH_F(OF) { if (f16) TEO_GP_LAUNCH_T(OF, true) else TEO_GP_LAUNCH_T(OF, false) }
-    if (of32) TEO_GP_LAUNCH_F(true) else TEO_GP_LAUNCH_F(false)
-#undef TEO_GP_LAUNCH_F
-#undef TEO_GP_LAUNCH_T
-#undef TEO_GP_LAUNCH_W
-#undef TEO_GP_LAUNCH_S
+    const int e = with_flags([&](auto of, auto fv) {
+        const auto one = [&](auto bmv, auto niv, auto nsv, auto occ, auto sw) {     // BM rows x 32 * NI columns, ring of NS, OCC workgroups per CU
+            constexpr int BM = decltype(bmv)::value, NI = decltype(niv)::value, NS = decltype(nsv)::value, OCC = decltype(occ)::value;
+            constexpr size_t lds = (size_t)NS * (BM + 32 * NI) * 128;
+            static unsigned long long attr_mask = 0;
+            if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_bf16_quad_kernel<BM, NI, NS, 2, OCC, of, fv, sw>), (int)lds, &attr_mask, "gemm_pipe")) return e;
+            gemm_mfma_bf16_quad_kernel<BM, NI, NS, 2, OCC, of, fv, sw><<<nwg, 256, lds, st>>>((const bf16_t*)a.A, (const bf16_t*)a.W, (const bf16_t*)a.bias,
+                                                                          (const bf16_t*)a.res, a.C, a.M, a.N, a.K, a.lda, a.ldc, a.act, tiles_m, tiles_n);
+            return (int)TEO_OK;
+        };
+        // the 128 x 96 tile has no SwiGLU form; the others take the epilogue of the call
+        if (bm == 128 && tn == 96) return ns == 4 ? one(int_c<128>{}, int_c<3>{}, int_c<4>{}, int_c<1>{}, std::false_type{})
+                                                  : one(int_c<128>{}, int_c<3>{}, int_c<3>{}, int_c<1>{}, std::false_type{});
+        return with_flags([&](auto sw) {
+            if (bm == 128) return one(int_c<128>{}, int_c<4>{}, int_c<3>{}, int_c<1>{}, sw);
+            if (tn == 64) return one(int_c<64>{}, int_c<2>{}, int_c<4>{}, int_c<2>{}, sw);
+            if (ns == 4) return one(int_c<64>{}, int_c<4>{}, int_c<4>{}, int_c<2>{}, sw);
+            return one(int_c<64>{}, int_c<4>{}, int_c<3>{}, int_c<2>{}, sw);
+        }, a.swiglu);
+    }, a.of32, a.f16);
+    if (e) return e;
     note_kernel(bm == 128 ? (tn == 96 ? "gemm_pipe_128x96" : "gemm_pipe_128") : (tn == 64 ? "gemm_pipe_64x64" : (ns == 4 ? "gemm_pipe_64_r4" : "gemm_pipe_64")));
     TEO_LAUNCH_CHECK("gemm_mfma_bf16_pipe");
     return TEO_OK;

@@ -30,7 +30,6 @@ constexpr int GW_W_BYTES = GW_BN * GW_BK * 2;            // 32 KiB
 constexpr int GW_STAGE = GW_A_BYTES + GW_W_BYTES;        // 48 KiB
 constexpr int GW_PIECES = GW_STAGE / 1024 / 8;           // 1-KiB DMA pieces per wave per K tile = 6
 
-// tune().gemm_wide_sched (default 1: the skewed / carried K-loop order), tune().gemm_wide_group (default 0: chosen from the tile grid)
 
 __device__ __forceinline__ int gw_xcd_remap(int bid, int nwg) {
     const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
@@ -296,55 +295,40 @@ __global__ __launch_bounds__(512, 2) void gemm_mfma_bf16_wide_sk_kernel(const bf
 }
 
 // slabs: 256 x 128 KB (the workspace of gemm_sk_workspace_bytes() holds 512 x 64 KB) + flags behind them
-int gemm_wide_sk_launch(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda, int ldc,
-                        int act, bool of32, bool f16, void* sk_ws, size_t flags_offset, hipStream_t st) {
-    const int tiles_m = cdiv(M, GW_BM), tiles_n = cdiv(N, GW_BN);
-    const int nk = K / GW_BK;
+int gemm_wide_sk_launch(const GemmPlan&, const GemmArgs& a, hipStream_t st) {
+    const int tiles_m = cdiv(a.M, GW_BM), tiles_n = cdiv(a.N, GW_BN);
+    const int nk = a.K / GW_BK;
     const long long total = (long long)tiles_m * tiles_n * nk;
     const int grid = 256;
-    const int per = (int)((total + grid - 1) / grid);                    // >= nk: the caller only comes here with more than 256 tiles
+    const int per = (int)((total + grid - 1) / grid);                    // >= nk: the plan only comes here with more than 256 tiles
     const size_t lds = 3 * GW_STAGE;
-    float* slabs = (float*)sk_ws;
-    int* flg = (int*)((unsigned char*)sk_ws + flags_offset);
-#define TEO_GWSK_LAUNCH(OF) { if (f16) TEO_GWSK_LAUNCH_F(OF, true) else TEO_GWSK_LAUNCH_F(OF, false) }
-#define TEO_GWSK_LAUNCH_F(OF, FV)                                                                                                 \
-    {                                                                                                                             \
-        static unsigned long long attr_mask = 0;                                                                                  \
-        if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_bf16_wide_sk_kernel<OF, FV>), (int)lds, &attr_mask, "gemm_wide_sk")) return e; \
-        gemm_mfma_bf16_wide_sk_kernel<OF, FV><<<grid, 512, lds, st>>>((const bf16_t*)A, (const bf16_t*)W, (const bf16_t*)bias,         \
-                                                                  (const bf16_t*)res, C, M, N, K, lda, ldc, act, tiles_m, tiles_n, \
-                                                                  per, slabs, flg);                                               \
-    }
-    if (of32) TEO_GWSK_LAUNCH(true) else TEO_GWSK_LAUNCH(false)
-#undef TEO_GWSK_LAUNCH
-#undef TEO_GWSK_LAUNCH_F
+    float* slabs = (float*)a.sk_ws;
+    int* flg = (int*)((unsigned char*)a.sk_ws + GEMM_SK_SLAB_BYTES);
+    const int e = with_flags([&](auto of, auto fv) {
+        static unsigned long long attr_mask = 0;
+        if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_bf16_wide_sk_kernel<of, fv>), (int)lds, &attr_mask, "gemm_wide_sk")) return e;
+        gemm_mfma_bf16_wide_sk_kernel<of, fv><<<grid, 512, lds, st>>>((const bf16_t*)a.A, (const bf16_t*)a.W, (const bf16_t*)a.bias, (const bf16_t*)a.res,
+                                                                  a.C, a.M, a.N, a.K, a.lda, a.ldc, a.act, tiles_m, tiles_n, per, slabs, flg);
+        return (int)TEO_OK;
+    }, a.of32, a.f16);
+    if (e) return e;
     note_kernel("gemm_wide_sk"); TEO_LAUNCH_CHECK("gemm_mfma_bf16_wide_sk");
     return TEO_OK;
 }
 
-int gemm_wide_launch(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda, int ldc,
-                     int act, bool swiglu, bool of32, bool f16, hipStream_t st) {
-    const int tiles_m = cdiv(M, GW_BM), tiles_n = cdiv(N, GW_BN);
+// K-loop order (g.sched) and tile group (g.group) from the plan
+int gemm_wide_launch(const GemmPlan& g, const GemmArgs& a, hipStream_t st) {
+    const int tiles_m = cdiv(a.M, GW_BM), tiles_n = cdiv(a.N, GW_BN);
     const int nwg = tiles_m * tiles_n;
     const size_t lds = 3 * GW_STAGE;
-#define TEO_GW_LAUNCH_S(SW, OF, SC) { if (f16) TEO_GW_LAUNCH_SF(SW, OF, SC, true) else TEO_GW_LAUNCH_SF(SW, OF, SC, false) }
-#define TEO_GW_LAUNCH_SF(SW, OF, SC, FV)                                                                                          \
-    {                                                                                                                             \
-        static unsigned long long attr_mask = 0;                                                                                  \
-        if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_bf16_wide_kernel<SW, OF, SC, FV>), (int)lds, &attr_mask, "gemm_wide")) return e; \
-        gemm_mfma_bf16_wide_kernel<SW, OF, SC, FV><<<nwg, 512, lds, st>>>((const bf16_t*)A, (const bf16_t*)W, (const bf16_t*)bias,     \
-                                                                      (const bf16_t*)res, C, M, N, K, lda, ldc, act, tiles_m, tiles_n, tune().gemm_wide_group ? tune().gemm_wide_group : (tiles_m >= 32 ? 4 : 1)); \
-    }
-#define TEO_GW_LAUNCH(SW, OF)                                                                                                     \
-    {                                                                                                                             \
-        if (tune().gemm_wide_sched == 0) TEO_GW_LAUNCH_S(SW, OF, 0)                                                                         \
-        else TEO_GW_LAUNCH_S(SW, OF, 1)                                                                                           \
-    }
-    if (swiglu) { if (of32) TEO_GW_LAUNCH(true, true) else TEO_GW_LAUNCH(true, false) }
-    else { if (of32) TEO_GW_LAUNCH(false, true) else TEO_GW_LAUNCH(false, false) }
-#undef TEO_GW_LAUNCH_S
-#undef TEO_GW_LAUNCH_SF
-#undef TEO_GW_LAUNCH
+    const int e = with_flags([&](auto sw, auto of, auto sc, auto fv) {
+        static unsigned long long attr_mask = 0;
+        if (int e = lds_attr_once(reinterpret_cast<const void*>(&gemm_mfma_bf16_wide_kernel<sw, of, sc, fv>), (int)lds, &attr_mask, "gemm_wide")) return e;
+        gemm_mfma_bf16_wide_kernel<sw, of, sc, fv><<<nwg, 512, lds, st>>>((const bf16_t*)a.A, (const bf16_t*)a.W, (const bf16_t*)a.bias, (const bf16_t*)a.res,
+                                                                      a.C, a.M, a.N, a.K, a.lda, a.ldc, a.act, tiles_m, tiles_n, g.group);
+        return (int)TEO_OK;
+    }, a.swiglu, a.of32, g.sched != 0, a.f16);
+    if (e) return e;
     note_kernel("gemm_wide"); TEO_LAUNCH_CHECK("gemm_mfma_bf16_wide");
     return TEO_OK;
 }

@@ -1,6 +1,7 @@
 // Internal C++ entry points of the kernels (one per .hip file); the extern "C" surface is in abi.hip.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"
 
 struct teo_graph {
     hipGraph_t graph;
@@ -61,9 +62,6 @@ int cross_entropy(const float* logits, long long ld, const long long* labels, fl
                   long long ignore_index, hipStream_t st);
 bool patch_embed_ok(int C, int img, int P, int ldw, int D, int dtype, const void* px, const void* W, const void* out);
 int patch_embed(const void* px, const void* W, void* out, int T, int C, int img, int P, int ldw, int D, hipStream_t st, bool f16 = false);
-bool gemm_big_hybrid_fits(int M, int N, int K);
-int gemm_big_ragged_tiles(int M, int N, int K = 0);    // gemm_big.hip: 128 x 512 tiles over a last row block of <= 128 rows (0: none)
-long long gemm_big_tile_count(int M, int N, int K = 0); // equal-cost tiles of the 256 x 256 family for an M x N problem
 bool skinny_gemm_ok(int MB, int N, int K, int ldx, int w_fp8, unsigned flags, const void* x, const void* W);
 // Producer-side RMSNorm hand-off between the GEMMs of a batched decode step.  A residual-producing GEMM (o / down
 // projection, one row tile per workgroup) also emits xg_out = bf16(h * next_g) and ssq_out[b][workgroup] = its 16
@@ -83,23 +81,28 @@ constexpr int SK_TRACE_SLOTS = 16;
 int skinny_gemm(const void* x, const void* W, const float* wscale, int w_fp8, const void* norm_w, float eps, const void* res,
                 void* out, int MB, int N, int K, int ldx, int ldo, unsigned flags, int out_dtype, hipStream_t st,
                 SkinnyFuse fuse = SkinnyFuse());
-// launch helpers of the tile families; f16: the operands are IEEE binary16 (else bfloat16)
-int gemm_big_launch(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda, int ldc,
-                    int act, bool swiglu, bool of32, bool f16, hipStream_t st, void* sk_ws, size_t flags_offset);
-int gemm_wide_launch(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda, int ldc,
-                     int act, bool swiglu, bool of32, bool f16, hipStream_t st);
-int gemm_narrow_launch(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda, int ldc,
-                       int act, bool of32, bool f16, int bm, hipStream_t st, bool waves8 = false);       // gemm_narrow.hip: bm 64 or 128 (waves8: the 8-wave 128 x 128 form)
-int gemm_quad_launch(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda, int ldc,
-                     int act, bool of32, bool f16, hipStream_t st);                 // gemm_quad.hip: 256 x 160 tiles, 4 waves
-int gemm_pipe_launch(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K, int lda, int ldc,
-                     int act, bool of32, bool f16, int bm, int tn, int ns, hipStream_t st, bool swiglu = false);   // gemm_quad.hip: the same K loop on 64 x 64 / 64 x 128 / 128 x 128 tiles
+// operands of one bf16 / f16 GEMM call for the launch helpers of the tile families, which take their geometry from a GemmPlan
+// (gemm_plan.h) and choose nothing.  f16: the operands are IEEE binary16 (else bfloat16); sk_ws: the stream-K workspace, if the plan uses one
+struct GemmArgs {
+    const void *A, *W, *bias, *res;
+    void* C;
+    int M, N, K, lda, ldc, act;
+    bool swiglu, of32, f16;
+    void* sk_ws;
+};
+int gemm_big_launch(const GemmPlan& g, const GemmArgs& a, hipStream_t st);      // gemm_big.hip
+int gemm_wide_launch(const GemmPlan& g, const GemmArgs& a, hipStream_t st);     // gemm_wide.hip
+int gemm_wide_sk_launch(const GemmPlan& g, const GemmArgs& a, hipStream_t st);
+int gemm_narrow_launch(const GemmPlan& g, const GemmArgs& a, hipStream_t st);   // gemm_narrow.hip
+int gemm_quad_launch(const GemmPlan& g, const GemmArgs& a, hipStream_t st);     // gemm_quad.hip: 256 x 160 tiles
+int gemm_pipe_launch(const GemmPlan& g, const GemmArgs& a, hipStream_t st);     // gemm_quad.hip: the same K loop on the small tiles
 constexpr size_t GEMM_SK_SLAB_BYTES = (size_t)64 << 20;   // slab area of the stream-K workspaces (largest user: 256 x 256 KB)
 constexpr int GEMM_SK_FLAG_INTS = 1024;          // hand-off flags (<= 512 used) + the sticky error word
 constexpr int GEMM_SK_ERR_SLOT = GEMM_SK_FLAG_INTS - 1;   // set to 1 by a hand-off that timed out (results of that GEMM are invalid)
 size_t gemm_sk_workspace_bytes();
 int gemm_sk_workspace_status(const void* ws, int* host_flag, hipStream_t st);
 // w8a8 prefill GEMM on the scaled fp8 MFMA (gemm_fp8.hip) and the per-token activation quantiser (norm_w != NULL: RMSNorm first)
+bool gemm_fp8_ok(int M, int N, int K, int lda, int ldc, unsigned flags, const void* A, const void* W, const void* res, const void* C);
 int gemm_fp8(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* res, void* C, int M, int N, int K,
              int lda, int ldc, unsigned flags, int out_dtype, hipStream_t st, void* sk_ws = nullptr);
 int quant_rows_fp8(const void* x, const void* norm_w, void* q, float* s, int M, int K, int ldx, float eps, hipStream_t st);

@@ -37,7 +37,7 @@ constexpr int SK_TP = 16 * 17;      // padded 16x16 partial tile in LDS: [b][i] 
 // tune().skinny_ring (default 0): streaming form, weight tiles in flight per wave: 0 = default (2 fp8 / 1 bf16: measured best end to end,
                                     // B = 8 fp8 step 3.455 vs 3.54 ms), 1 = one more (3 / 2)
 // tune().skinny_unr (default 0): tile kernel, steps per register set: 0 = auto (8 for long K slices without SwiGLU / in-kernel norm), 4, 8
-// tune().skinny_waves (default 0): tile kernel, waves per workgroup: 0 = auto, 8, 16 (16: K split 16 ways; plain / residual epilogues, one row tile per workgroup)
+// tune().skinny_waves (default 0): tile kernel, waves per workgroup: 0 and 8 = 8; 16 only when forced (K split 16 ways; plain / residual epilogues, one row tile per workgroup)
 // tune().skinny_grid (default 0): streaming form, persistent workgroups per CU: 0 = auto (1), 1, 2, 3
 
 // Timeline marks of the probe build (tools/skinny_probe.hip instantiates TRACE = true; the library only TRACE = false):
@@ -608,7 +608,7 @@ int skinny_gemm(const void* x, const void* W, const float* wscale, int w_fp8, co
     {
         const int steps16 = K / (w_fp8 ? 64 : 32) / 16;
         const bool w16 = !swiglu && !norm_w && rt == 1 && (tune().skinny_nt != 0) && steps16 >= 2 &&
-                         (tune().skinny_waves == 16 || (tune().skinny_waves == 0 && false));
+                         tune().skinny_waves == 16;
         if (w16) {
 #define TEO_SK16(WW, UN)                                                                                    \
             TEO_KLAUNCH((skinny_gemm_kernel<WW, UN, true, false, false, false, 16>), blocks, 1024, 0, st, (const WW*)W, (const bf16_t*)x, MB, N, K, ldx,  \

@@ -280,6 +280,46 @@ def test_tune_blocks_are_independent_and_validated():
         a.close(); b.close()
 
 
+def test_gemm_plan_reproduces_the_recorded_dispatch_table():
+    """The GEMM dispatch without a GPU: teo_gemm_plan / teo_gemm_fp8_plan (gemm_plan.hip) name, for every row of tests/golden/
+    gemm_dispatch_table.json, the family teo_last_kernel reported after a real launch on an MI355X (tools/dispatch_table.py, recorded
+    from the library before the dispatch moved into the planner).  Rows: every GEMM of the runtime at the model's sizes, with and without
+    a stream-K workspace as the runtime calls it, M over {1, 64k, 64k + 1, 257 T}; the defaults at 256 and at 80 CUs, every non-default
+    value of every GEMM knob one at a time and the knob combinations the GPU tests force, on every 4th M."""
+    import json
+    from teochat_amd import _lib as L
+    lib = L.load()
+    with open(os.path.join(ROOT, "tests", "golden", "gemm_dispatch_table.json")) as f:
+        table = json.load(f)
+    ms = sorted({1} | {v for k in range(1, 75) for v in (64 * k, 64 * k + 1)} | {257 * t for t in range(1, 17)})
+    names = table["names"]
+    t = L.Tune()
+    t.bind()
+    bad, rows = [], 0
+    try:
+        for g in table["groups"]:
+            assert t.reset() == 0
+            for k, v in g["knobs"].items():
+                assert t.set(k, v) == 0
+            m_list = ms if g["ms"] == "all" else ms[::4]
+            for shape, ws, runs in g["rows"]:
+                N, K, act, flags, out_dtype, _bias, _res, fp8, _wss = table["shapes"][shape]
+                want = [names[i] for c, i in runs for _ in range(c)]
+                assert len(want) == len(m_list)
+                for M, w in zip(m_list, want):
+                    if fp8:
+                        got = lib.teo_gemm_fp8_plan(M, N, K, flags, out_dtype, ws, g["cu"])
+                    else:
+                        got = lib.teo_gemm_plan(M, N, K, flags, act, L.TEO_BF16, out_dtype, ws, g["cu"])
+                    rows += 1
+                    if got.decode() != w:
+                        bad.append((g["knobs"], g["cu"], shape, ws, M, w, got.decode()))
+    finally:
+        lib.teo_tune_bind(None)
+        t.close()
+    assert rows > 60000 and not bad, (len(bad), bad[:10])
+
+
 def test_hand_scheduled_kernels_have_no_spills_and_no_scratch():
     """the K loops of gemm_quad.hip / gemm_narrow.hip count their `s_waitcnt vmcnt(N)` by hand (only the LDS-DMA pieces may be
     in flight; the asm-volatile MFMAs are invisible to the hazard recogniser).  A compiler that spilled a register or used scratch in those

@@ -151,3 +151,66 @@ def test_production_dispatch_takes_the_small_pipelined_tiles_where_round_six_mea
     L.tune_reset()
     assert torch.equal(got, ref), (ran, float((got.float() - ref.float()).abs().max()))
     assert ran == want, (ran, want, M, N, K)
+
+
+# the model's GEMMs (tools/dispatch_table.py SHAPES): N, K, act, flags, out dtype, bias, residual, w8a8, workspace choices
+_PLAN_SHAPES = {
+    "vit_patch": (1024, 640, L.ACT_NONE, 0, torch.bfloat16, False, False, False, (0, 1)),
+    "vit_qkv": (3072, 1024, L.ACT_NONE, 0, torch.bfloat16, True, False, False, (0, 1)),
+    "vit_out": (1024, 1024, L.ACT_NONE, 0, torch.bfloat16, True, True, False, (0, 1)),
+    "vit_fc1": (4096, 1024, L.ACT_QUICK_GELU, 0, torch.bfloat16, True, False, False, (0, 1)),
+    "vit_fc2": (1024, 4096, L.ACT_NONE, 0, torch.bfloat16, True, True, False, (0, 1)),
+    "proj_fc1": (4096, 1024, L.ACT_GELU_ERF, 0, torch.bfloat16, True, False, False, (0,)),
+    "proj_fc2": (4096, 4096, L.ACT_NONE, 0, torch.bfloat16, True, False, False, (0,)),
+    "llm_qkv": (12288, 4096, L.ACT_NONE, 0, torch.bfloat16, False, False, False, (0, 1)),
+    "llm_o": (4096, 4096, L.ACT_NONE, 0, torch.bfloat16, False, True, False, (0, 1)),
+    "llm_gateup": (22016, 4096, L.ACT_NONE, L.GEMM_SWIGLU16, torch.bfloat16, False, False, False, (0, 1)),
+    "llm_down": (4096, 11008, L.ACT_NONE, 0, torch.bfloat16, False, True, False, (0, 1)),
+    "llm_lm_head": (32000, 4096, L.ACT_NONE, 0, torch.float32, False, False, False, (0, 1)),
+    "fp8_qkv": (12288, 4096, L.ACT_NONE, 0, torch.bfloat16, False, False, True, (0,)),
+    "fp8_o": (4096, 4096, L.ACT_NONE, 0, torch.bfloat16, False, True, True, (0, 1)),
+    "fp8_gateup": (22016, 4096, L.ACT_NONE, L.GEMM_SWIGLU16, torch.bfloat16, False, False, True, (0,)),
+    "fp8_down": (4096, 11008, L.ACT_NONE, 0, torch.bfloat16, False, True, True, (0, 1)),
+}
+_PLAN_MS = (1, 64, 65, 128, 257, 514, 640, 641, 771, 1024, 1028, 1285, 2056, 2176, 2313, 2560, 3084, 3328, 4112, 4737)
+
+
+@pytest.mark.parametrize("shape", sorted(_PLAN_SHAPES))
+def test_launch_follows_the_plan(shape):
+    """teo_gemm_plan / teo_gemm_fp8_plan (the dispatch as data, gemm_plan.hip) name the family the launch helpers then run: after a real
+    teo_gemm_ws / teo_gemm_fp8_ws call on the shipped knobs, teo_last_kernel is the plan's name (tests/test_host_logic.py pins the plan
+    itself against a table recorded from launches)."""
+    lib = G.lib()
+    N, K, act, flags, od, has_bias, has_res, fp8, wss = _PLAN_SHAPES[shape]
+    g = torch.Generator().manual_seed(N + K)
+    mmax, ldc = max(_PLAN_MS), N // 2 if flags else N
+    dt = {torch.bfloat16: L.TEO_BF16, torch.float32: L.TEO_F32}
+    if fp8:
+        A = torch.randint(0, 120, (mmax, K), dtype=torch.uint8, generator=g).cuda()
+        W = torch.randint(0, 120, (N, K), dtype=torch.uint8, generator=g).cuda()
+        sa, sw = torch.full((mmax,), 1e-3, device="cuda"), torch.full((N,), 1e-3, device="cuda")
+    else:
+        A = torch.randn(mmax, K, generator=g).to(torch.bfloat16).cuda()
+        W = (torch.randn(N, K, generator=g) * 0.02).to(torch.bfloat16).cuda()
+    bias = torch.randn(N, generator=g).to(torch.bfloat16).cuda() if has_bias else None
+    res = torch.randn(mmax, ldc, generator=g).to(torch.bfloat16).cuda() if has_res else None
+    Cc = torch.empty(mmax, ldc, dtype=od, device="cuda")
+    ws = torch.empty(lib.teo_gemm_workspace_bytes(), dtype=torch.uint8, device="cuda")
+    L.check(lib.teo_gemm_workspace_init(G.p(ws), G.stream()), "teo_gemm_workspace_init")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    L.tune_reset()
+    for w in wss:
+        for M in _PLAN_MS:
+            wp = G.p(ws) if w else None
+            if fp8:
+                want = lib.teo_gemm_fp8_plan(M, N, K, flags, dt[od], w, cus).decode()
+                L.check(lib.teo_gemm_fp8_ws(G.p(A), G.p(sa), G.p(W), G.p(sw), G.p(res), G.p(Cc), M, N, K, K, ldc, flags, dt[od], wp, G.stream()), shape)
+            else:
+                want = lib.teo_gemm_plan(M, N, K, flags, act, L.TEO_BF16, dt[od], w, cus).decode()
+                L.check(lib.teo_gemm_ws(G.p(A), G.p(W), G.p(bias), G.p(res), G.p(Cc), M, N, K, K, ldc, act, flags, L.TEO_BF16, dt[od], wp,
+                                        G.stream()), shape)
+            assert lib.teo_last_kernel().decode() == want, (shape, w, M, want)
+    torch.cuda.synchronize()
+    flag = C.c_int(-1)
+    L.check(lib.teo_gemm_workspace_status(G.p(ws), C.byref(flag), G.stream()), "teo_gemm_workspace_status")
+    assert flag.value == 0
