@@ -76,7 +76,7 @@ size_t teo_sizeof(const char* struct_name);
  * teo_tune_destroy on a block still bound by ANOTHER thread or named by a live descriptor is a use-after-free of the caller's making.
  * teo_tune_get(NULL, key, &v) reads the shipped default; teo_tune_keys() lists every key, space separated.  Keys (0 / 1 unless said):
  *   decode GEMV   : "gemv_variant" (-1 default; 0..2, 10..13: row-group geometry; fp32 order), "gemv_nt" (non-temporal weight loads),
- *                   "gemv_max_blocks" (workgroup cap), "gemv_small_k" (x prologue sized to K <= 4096), "gemv_splitk_u" (chunks per thread and step of the split-K GEMV: 0 auto, 1/2/3/4/6), "gemv_splitk_r" (its rows per workgroup: 0 auto, 2/4)
+ *                   "gemv_max_blocks" (workgroup cap), "gemv_small_k" (x prologue sized to K <= 4096; bit-identical), "gemv_splitk_u" (chunks per thread and step of the split-K GEMV: 0 auto, 1/2/3/4/6), "gemv_splitk_r" (its rows per workgroup: 0 auto, 2/4)
  *   prefill GEMM  : "gemm_bm" (tile rows of the plain kernel: 0 auto, 64, 128), "gemm_depth", "gemm_sk" (stream-K: 0 off, 1 auto, 2 force),
  *                   "gemm_wide" (0 off, 1 auto, 2 force), "gemm_wide_sched", "gemm_wide_group", "gemm_big" (0 off, 1 auto, 2 force),
  *                   "gemm_big_group", "gemm_big_hybrid" (0 off, 1 auto, 2 force), "gemm_big_cohort" (stream-K part of the hybrid form as
@@ -99,12 +99,14 @@ size_t teo_sizeof(const char* struct_name);
  *                   same tiles, same arithmetic: bit-identical
  *   decode attn   : "attn_chunk" (keys per decode chunk: 0 auto, 32/64/128/256; fp32 order of the split merge + where P is rounded),
  *                   "attn_whole" (batched decode attention as one workgroup per (conversation, head): 0 off, 1 auto = when conversations x
- *                   heads make whole rounds of the CUs (a multiple of the CU count, or at least 7/4 rounds), 2 whenever the shape allows; bit-identical to the split + combine pair at the same chunk)
+ *                   heads make whole rounds of the CUs (a multiple of the CU count, or at least 7/4 rounds), 2 whenever the shape allows; bit-identical to the split + combine pair at the same chunk -- with "attn_chunk" 0 the whole form takes
+ *                   64 keys and the split pair 128, so there it is fp32 order)
  *   batched GEMM  : "skinny_tiles" (0 auto, 1/2/4/8), "skinny_nt", "skinny_stream" (0 off, 1 auto, 2 whenever eligible), "skinny_ring"
  *                   (weight tiles in flight of the streaming form: 0 default, 1 one more), "skinny_unr" (tile kernel steps per register
  *                   set: 0 auto, 4, 8), "skinny_waves" (tile kernel waves per workgroup: 0 and 8 = 8, 16 forced only --
  *                   measured and lost, kept for the A/B), "skinny_grid" (persistent workgroups per CU of the streaming form: 0 auto = 1, 1..3 -- likewise) --
- *                   bit-identical at K = 4096, fp32 order elsewhere
+ *                   "skinny_nt", "skinny_unr", "skinny_ring" and "skinny_grid" bit-identical at every K; "skinny_stream" bit-identical at
+ *                   K = 4096, fp32 order elsewhere; "skinny_tiles" and "skinny_waves" (another split of K across the waves) fp32 order
  * teo_tune_set returns TEO_ERR_ARG for an unknown key or a value outside the key's set (message in teo_last_error). */
 typedef struct teo_tune teo_tune;
 teo_tune* teo_tune_create(void);                      /* a block holding the shipped defaults; NULL when out of memory */

@@ -664,7 +664,8 @@ static int gemv_launch(const void* x, const void* W, const float* ws, const void
         case 2: return launch_rows<T, TO, WT, 2, 8, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
         default: break;
     }
-    const bool small_k = K / Vec16<T>::N <= 2 * GV_THREADS && (tune().gemv_small_k != 0);   // the x prologue fits 2 chunks per thread (stage_x)
+    const bool fits = K / Vec16<T>::N <= 2 * GV_THREADS;              // the x prologue fits 2 chunks per thread (stage_x)
+    const bool small_k = fits && (tune().gemv_small_k != 0);
     // >= 4 KiB contiguous per row per step streams ~7 % faster than 2 KiB; first block prefetched under the prologue.
     // fp8 rows are half as long: 4 rows per wave keep the same bytes in flight per lane
     if constexpr (sizeof(WT) == 1) {
@@ -684,9 +685,13 @@ static int gemv_launch(const void* x, const void* W, const float* ws, const void
         switch (tune().gemv_variant) {
             case 10: return launch_rows<T, TO, WT, 2, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
             case 11: return launch_rows<T, TO, WT, 4, 2, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
+            case 12: return launch_rows<T, TO, WT, 2, 2, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
             case 13: return launch_rows<T, TO, WT, 4, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
             default: break;
         }
+        // the bf16 image sums a step's U chunks before adding them to the row (consume_block), so U sets the fp32 order: where the small
+        // prologue would apply but gemv_small_k = 0, keep its 2 x 4 form (the knob picks the prologue, not the order of the sums)
+        if (fits) return launch_rows<T, TO, WT, 2, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
         return launch_rows<T, TO, WT, 2, 2, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
     }
     if constexpr (Is16<T>::v) { if (small_k) return launch_rows<T, TO, WT, 2, 4, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st); }
@@ -744,8 +749,10 @@ int gemv_qkv_rope(const void* x, const void* W, const float* wscale, int w_fp8, 
     const size_t lds = w_fp8 ? xb_lds_bytes<16>(K) : (dtype == TEO_F32 ? xs_lds_bytes<4>(K) : xs_lds_bytes<8>(K));
     // small x prologue (2 register chunks per thread) whenever K allows: fewer VGPRs, more waves per SIMD (see stage_x); fp8 rows then
     // take 4 chunks per step like the row-group kernel (8 KB per wave in flight)
-    const bool small_k = (tune().gemv_small_k != 0) && K / (dtype == TEO_F32 ? 4 : 8) <= 2 * GV_THREADS;
-    const int uu = (w_fp8 && !small_k) ? 2 : 4;
+    const bool fits = K / (dtype == TEO_F32 ? 4 : 8) <= 2 * GV_THREADS;
+    const bool small_k = (tune().gemv_small_k != 0) && fits;
+    // (fp8: U sets the fp32 order of the bf16 image's sums, see gemv_launch -- it follows what K allows, not gemv_small_k)
+    const int uu = (w_fp8 && !fits) ? 2 : 4;
     const bool pf = K / ve >= 64 * uu;
 #define TEO_QR2(TT, WW, NTV, XP, UU)                                                                                      \
     if (pf) TEO_KLAUNCH((gemv_qkv_rope_kernel<TT, WW, NTV, true, UU, XP>), blocks, GV_THREADS, lds, st, (const WW*)W, (const TT*)x, (const TT*)norm_w, wscale, \
@@ -756,7 +763,7 @@ int gemv_qkv_rope(const void* x, const void* W, const float* wscale, int w_fp8, 
                                                                        S_max, eps)
 #define TEO_QR(TT, WW, NTV) if (small_k) { TEO_QR2(TT, WW, NTV, 2, 4); } else { TEO_QR2(TT, WW, NTV, 6, 4); }
 #define TEO_QR6(TT, WW, NTV) TEO_QR2(TT, WW, NTV, 6, 4)
-#define TEO_QR8(TT, WW, NTV) if (small_k) { TEO_QR2(TT, WW, NTV, 2, 4); } else { TEO_QR2(TT, WW, NTV, 6, 2); }
+#define TEO_QR8(TT, WW, NTV) if (small_k) { TEO_QR2(TT, WW, NTV, 2, 4); } else if (fits) { TEO_QR2(TT, WW, NTV, 6, 4); } else { TEO_QR2(TT, WW, NTV, 6, 2); }
     if (w_fp8)                 { if (tune().gemv_nt) { TEO_QR8(bf16_t, fp8_t, true); } else { TEO_QR8(bf16_t, fp8_t, false); } }
     else if (dtype == TEO_F32) { if (tune().gemv_nt) { TEO_QR6(float, float, true); } else { TEO_QR6(float, float, false); } }
     else if (dtype == TEO_F16) { if (tune().gemv_nt) { TEO_QR(f16_t, f16_t, true); } else { TEO_QR(f16_t, f16_t, false); } }
