@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define TEO_ABI_VERSION 2 /* 2 (round 5): teo_tune blocks instead of process-wide knobs, `tune` field at the end of the descriptors, teo_sizeof */
+#define TEO_ABI_VERSION 3 /* 3: MXFP4 decode weights (teo_llama_desc *_w4 / *_e4, teo_gemv_w4); 2: teo_tune blocks, `tune` last in the descriptors, teo_sizeof */
 
 typedef void* teo_stream_t; /* hipStream_t */
 
@@ -302,6 +302,16 @@ int teo_gemv(const void* d_x, const void* d_W, const void* d_norm_w, const void*
 int teo_gemv_w8(const void* d_x, const void* d_W8, const float* d_w_scale, const void* d_norm_w, const void* d_residual,
                 void* d_y, int N, int K, float eps, unsigned flags, int out_dtype, teo_stream_t stream);
 
+/* teo_gemv with MXFP4 weights (OCP microscaling FP4): W4 [N, K/2] bytes of e2m1 codes, element k = 2j in the low nibble of byte j
+ * and k = 2j + 1 in the high one; e8m0 [N, K/32] bytes, row-major, one biased exponent E per 32-element block along K:
+ *   W[n, k] = e2m1(code) * 2^(E[n, k/32] - 127),   e2m1 magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6}, bit 3 the sign.
+ * E in 1 .. 254 (teochat_amd.engine.quantize_mxfp4_blocks writes 2 .. 252: every nonzero weight a finite bf16 normal).  An e2m1 value
+ * has at most two significant bits and the scale is a power of two, so every weight is exactly a bfloat16 number: a bf16 teo_gemv on
+ * the dequantised matrix sees the same weights (same values up to the fp32 order of the sums).  bf16 activations only; K % 32 != 0
+ * returns TEO_ERR_UNSUPPORTED.  Flags, norm, residual and out_dtype as teo_gemv. */
+int teo_gemv_w4(const void* d_x, const void* d_W4, const void* d_e8m0, const void* d_norm_w, const void* d_residual,
+                void* d_y, int N, int K, float eps, unsigned flags, int out_dtype, teo_stream_t stream);
+
 /* Batched-decode GEMM: out[b, n] = sum_k x[b, k] * W[n, k] (+ residual[b, n]) for MB <= 16 conversations; the weights
  * are streamed once for the whole batch (HF generate with batch > 1 through LlamaForCausalLM.forward,
  * videollava/model/language_model/llava_llama.py:88-99).  bf16 activations x [MB, ldx]; W bf16 [N, K] or fp8 e4m3
@@ -389,6 +399,16 @@ typedef struct {
     const void* const* gateup_w8; const float* const* gateup_s;
     const void* const* down_w8;   const float* const* down_s;
     const void* lm_head8;         const float* lm_head_s;
+    /* Optional MXFP4 copies for the single-conversation DECODE step (teo_gemv_w4's format: [N, K/2] code bytes, [N, K/32] e8m0 bytes),
+     * same row layouts as above (gate/up interleaved-16).  The dequantised weights are exact bfloat16 numbers: prefill, the
+     * batched step and the tower keep reading the 16-bit weights above, which a caller sets to the dequantised values.
+     * teo_llama_decode_step (and its graph / profile forms) streams these when qkv_w4 is set; lm_head stays 16-bit.  All eight or
+     * none; bf16 only; a descriptor holding both *_w8 and *_w4 copies is TEO_ERR_ARG.  teo_llama_decode_batch_step and the
+     * prefill entry points ignore them.  All NULL -> today's behaviour. */
+    const void* const* qkv_w4;    const uint8_t* const* qkv_e4;
+    const void* const* o_w4;      const uint8_t* const* o_e4;
+    const void* const* gateup_w4; const uint8_t* const* gateup_e4;
+    const void* const* down_w4;   const uint8_t* const* down_e4;
     /* Per-engine options (they select a path or change results, so they live here and not in teo_tune_set): */
     int prefill_fp8;   /* 1: prefill Linear layers as w8a8 on the fp8 MFMA (activations quantised per token; needs the *_w8 copies,
                         *    bf16).  Lossy beyond the weight quantisation: selectable, never a default.  0: bf16 / f32 GEMMs */

@@ -66,6 +66,8 @@ class LlamaDesc(C.Structure):
                 ("down_w", PP), ("k_cache", PP), ("v_cache", PP), ("vt_cache", PP),
                 ("qkv_w8", PP), ("qkv_s", PP), ("o_w8", PP), ("o_s", PP), ("gateup_w8", PP), ("gateup_s", PP),
                 ("down_w8", PP), ("down_s", PP), ("lm_head8", C.c_void_p), ("lm_head_s", C.c_void_p),
+                ("qkv_w4", PP), ("qkv_e4", PP), ("o_w4", PP), ("o_e4", PP), ("gateup_w4", PP), ("gateup_e4", PP),
+                ("down_w4", PP), ("down_e4", PP),
                 ("prefill_fp8", C.c_int), ("rope_in_attn", C.c_int), ("tune", C.c_void_p)]
 
 
@@ -130,6 +132,7 @@ _SIGS = {
                                   C.c_void_p]),
     "teo_gemv": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_uint, C.c_int, C.c_int, C.c_void_p]),
     "teo_gemv_w8": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_float, C.c_uint, C.c_int, C.c_void_p]),
+    "teo_gemv_w4": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_float, C.c_uint, C.c_int, C.c_void_p]),
     "teo_vit_workspace_bytes": (C.c_size_t, [C.POINTER(VitDesc), C.c_int]),
     "teo_vit_encode": (C.c_int, [C.POINTER(VitDesc), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "teo_projector_workspace_bytes": (C.c_size_t, [C.POINTER(ProjDesc), C.c_int]),
@@ -176,7 +179,7 @@ _SIGS = {
     "teo_ctx_tune": (C.c_void_p, [C.c_void_p]),
 }
 
-ABI_VERSION = 2            # TEO_ABI_VERSION of include/teo_hip.h this binding was written against
+ABI_VERSION = 3            # TEO_ABI_VERSION of include/teo_hip.h this binding was written against
 # (the ctypes mirrors of the header's structs are checked against the library's own sizeof at load: a stale or newer .so must fail
 # THERE, not by reading shifted fields)
 

@@ -311,12 +311,13 @@ def load_generation_config(model, model_dir):
 def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, load_4bit=False, device_map="auto",
                           device="cuda", cache_dir=None, dtype=None, max_seq=None, seed=2, weight_format=None):
     """dtype None = the reference's choice where it has one: a real checkpoint runs in torch.float16 (builder.py:105 passes
-    torch_dtype=torch.float16 whatever the file holds; eval/inference.py:53 casts the frames to match) -- unless fp8 decode weights are
-    requested, which go with bfloat16 -- and the synthetic presets in torch.bfloat16 (BASELINE.json's headline dtype)."""
+    torch_dtype=torch.float16 whatever the file holds; eval/inference.py:53 casts the frames to match) -- unless fp8 or MXFP4 decode weights
+    are requested (weight_format="fp8" / "mxfp4"), which go with bfloat16 -- and the synthetic presets in torch.bfloat16 (BASELINE.json's
+    headline dtype).  load_4bit (bitsandbytes NF4 in the reference) is not rerouted to MXFP4."""
     if device in (None, "cuda"):
         device = "cuda:0"
     if dtype is None:
-        dtype = torch.bfloat16 if (model_path.startswith("synthetic:") or weight_format == "fp8") else torch.float16
+        dtype = torch.bfloat16 if (model_path.startswith("synthetic:") or weight_format in ("fp8", "mxfp4")) else torch.float16
     if load_8bit or load_4bit:
         warnings.warn("bitsandbytes int8/nf4 loading is CUDA-only and out of scope; loading bf16 weights instead")
     if model_path.startswith("synthetic:"):

@@ -343,7 +343,19 @@ int teo_gemv_w8(const void* x, const void* W8, const float* ws, const void* norm
     ENTER();
     NEED_DT(out_dtype); TEO_CHECK_ARG(N >= 0 && K > 0, "teo_gemv_w8: N %d K %d", N, K);
     if (N) { NEED(x, "x"); NEED(W8, "W8"); NEED(ws, "w_scale"); NEED(y, "y"); }
-    return gemv_w(x, W8, ws, 1, norm_w, res, y, N, K, eps, flags, TEO_BF16, out_dtype, ST(s));
+    return gemv_w(x, W8, ws, GV_W_FP8, norm_w, res, y, N, K, eps, flags, TEO_BF16, out_dtype, ST(s));
+}
+
+int teo_gemv_w4(const void* x, const void* W4, const void* e8m0, const void* norm_w, const void* res, void* y, int N, int K,
+                float eps, unsigned flags, int out_dtype, teo_stream_t s) {
+    ENTER();
+    NEED_DT(out_dtype); TEO_CHECK_ARG(N >= 0 && K > 0, "teo_gemv_w4: N %d K %d", N, K);
+    if (K % 32 != 0) {
+        set_error("teo_gemv_w4: K=%d is not a multiple of the 32-element MX block", K);
+        return TEO_ERR_UNSUPPORTED;
+    }
+    if (N) { NEED(x, "x"); NEED(W4, "W4"); NEED(e8m0, "e8m0"); NEED(y, "y"); }
+    return gemv_w(x, W4, e8m0, GV_W_MXFP4, norm_w, res, y, N, K, eps, flags, TEO_BF16, out_dtype, ST(s));
 }
 
 size_t teo_vit_workspace_bytes(const teo_vit_desc* d, int T) { return d ? vit_workspace_bytes(d, T) : 0; }

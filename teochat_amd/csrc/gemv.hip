@@ -9,7 +9,8 @@
 //     f(x) is staged once per workgroup in LDS as fp32 and re-read with conflict-free ds_read_b128;
 //   - few-long-rows layers (o / down, N = 4096) use split-K workgroups: 4 waves share 2 rows;
 //   - epilogues fused: residual add, SwiGLU on the interleaved-16 gate/up layout, fp32 logits, RoPE + KV append;
-//   - weights may be bf16/f32 (same type as x) or fp8 e4m3 (OCP) with one fp32 scale per output row.
+//   - weights may be bf16/f32 (same type as x), fp8 e4m3 (OCP) with one fp32 scale per output row, or MXFP4 (OCP e2m1 codes,
+//     one e8m0 scale byte per 32 elements along K): a 16-byte chunk is then exactly one MX block.
 // Roofline: HBM (8 TB/s spec); algorithmic bytes per launch = N*K*sizeof(WT) (+ K + N elements, negligible).
 #include <type_traits>
 
@@ -45,6 +46,16 @@ template <> struct Vec16<float> {
         f[0] = __uint_as_float(r.x); f[1] = __uint_as_float(r.y); f[2] = __uint_as_float(r.z); f[3] = __uint_as_float(r.w);
     }
 };
+// MXFP4: a byte holds two e2m1 codes (element 2j in the low nibble, 2j + 1 in the high one); no fp32 unpack (see dot_mx)
+struct fp4x2_t { unsigned char v; };
+template <typename WT> struct IsMx { static constexpr bool v = false; };
+template <> struct IsMx<fp4x2_t> { static constexpr bool v = true; };
+template <> struct Vec16<fp4x2_t> { static constexpr int N = 32; };
+// weight elements per WT unit: rows are K / WPer units long and a 16-byte chunk is CU units
+template <typename WT> struct WPer { static constexpr int v = IsMx<WT>::v ? 2 : 1; };
+template <typename WT> struct CU { static constexpr int v = Vec16<WT>::N / WPer<WT>::v; };
+// per-row fp32 scales (fp8), or one e8m0 byte per chunk (MXFP4, [N][K/32] row-major)
+template <typename WT> using WScaleT = typename std::conditional<IsMx<WT>::v, unsigned char, float>::type;
 template <> struct Vec16<fp8_t> {
     static constexpr int N = 16;
     __device__ static __forceinline__ void cvt(const uint4& r, float* f) {
@@ -111,6 +122,21 @@ __device__ __forceinline__ float dotb<fp8_t>(const uint4& w, const uint4* xv, fl
     }
     return acc;
 }
+// one MX block (32 e2m1 codes, 16 bytes) . 32 bf16 activations: v_cvt_scalef32_pk_bf16_fp4 turns a byte (two codes) and the block
+// scale into two bf16 values -- exact, |code| has two significant bits and the scale is a power of two -- and v_dot2 meets them
+// with x.  escale = 2^(E - 127), the e8m0 byte E shifted into an fp32 exponent (E = 1 .. 254).
+__device__ __forceinline__ float dot_mx(const uint4& w, const uint4* xv, float escale, float acc) {
+    const unsigned ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        acc = dot2bf(__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(ww[i], escale, 0)), xv[i].x, acc);
+        acc = dot2bf(__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(ww[i], escale, 1)), xv[i].y, acc);
+        acc = dot2bf(__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(ww[i], escale, 2)), xv[i].z, acc);
+        acc = dot2bf(__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(ww[i], escale, 3)), xv[i].w, acc);
+    }
+    return acc;
+}
+__device__ __forceinline__ float e8m0_scale(unsigned e) { return __uint_as_float(e << 23); }
 template <typename T> struct IsBf { static constexpr bool v = false; };
 template <> struct IsBf<bf16_t> { static constexpr bool v = true; };
 template <typename T> struct Is16 { static constexpr bool v = IsBf<T>::v || IsF16<T>::v; };      // a 16-bit activation format
@@ -269,22 +295,32 @@ __device__ __forceinline__ void stage_x(const T* __restrict__ x, const T* __rest
 }
 
 // one block of R rows x U chunks: loads and the dot-product update
+// (MXFP4: sx receives the chunks' e8m0 bytes from the scale rows srow -- one byte per lane, a wave's 64 in one request; unused otherwise)
 template <typename WT, int R, int U, bool NT, bool FULL>
-__device__ __forceinline__ void issue_block(uint4 (&w)[U][R], const WT* const (&rowp)[R], int c0, int lane, int nchunk) {
-    constexpr int VE = Vec16<WT>::N;
+__device__ __forceinline__ void issue_block(uint4 (&w)[U][R], unsigned (&sx)[U][R], const WT* const (&rowp)[R],
+                                            const unsigned char* const (&srow)[R], int c0, int lane, int nchunk) {
+    constexpr int CH = CU<WT>::v;
+    if constexpr (IsMx<WT>::v) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int c = c0 + u * 64 + lane;
+#pragma unroll
+            for (int r = 0; r < R; ++r) sx[u][r] = (FULL || c < nchunk) ? (unsigned)srow[r][c] : 0u;
+        }
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int c = c0 + u * 64 + lane;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            if (FULL) w[u][r] = ld16<NT>(rowp[r] + (long long)c * VE);
-            else w[u][r] = (c < nchunk) ? ld16<NT>(rowp[r] + (long long)c * VE) : make_uint4(0, 0, 0, 0);
+            if (FULL) w[u][r] = ld16<NT>(rowp[r] + (long long)c * CH);
+            else w[u][r] = (c < nchunk) ? ld16<NT>(rowp[r] + (long long)c * CH) : make_uint4(0, 0, 0, 0);
         }
     }
 }
 template <typename T, typename WT, int R, int U, bool FULL, bool XB16 = BfImage<T, WT>::v>
-__device__ __forceinline__ void consume_block(const uint4 (&w)[U][R], const float* xs, int c0, int lane, int nchunk,
-                                              float (&acc)[R]) {
+__device__ __forceinline__ void consume_block(const uint4 (&w)[U][R], const unsigned (&sx)[U][R], const float* xs, int c0, int lane,
+                                              int nchunk, float (&acc)[R]) {
     constexpr int VE = Vec16<WT>::N;
     if constexpr (XB16) {
         // one accumulator per (row, chunk): v_dot2c chains of 4 instead of 4 U (the instruction accumulates in place, so
@@ -299,7 +335,10 @@ __device__ __forceinline__ void consume_block(const uint4 (&w)[U][R], const floa
                 xb[j] = (FULL || c < nchunk) ? *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(xs) + xb_off<VE>(c * VE + j * 8))
                                              : make_uint4(0, 0, 0, 0);
 #pragma unroll
-            for (int r = 0; r < R; ++r) part[u][r] = dotb<WT>(w[u][r], xb, 0.f);
+            for (int r = 0; r < R; ++r) {
+                if constexpr (IsMx<WT>::v) part[u][r] = dot_mx(w[u][r], xb, e8m0_scale(sx[u][r]), 0.f);
+                else part[u][r] = dotb<WT>(w[u][r], xb, 0.f);
+            }
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -309,7 +348,7 @@ __device__ __forceinline__ void consume_block(const uint4 (&w)[U][R], const floa
             acc[r] += t;
         }
         return;
-    }
+    } else {            // (the fp32 image: never instantiated for MXFP4 weights, which have no fp32 unpack -- see dot_mx)
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int c = c0 + u * 64 + lane;
@@ -330,6 +369,7 @@ __device__ __forceinline__ void consume_block(const uint4 (&w)[U][R], const floa
         // of the step (that costs 170-250 VGPRs and the occupancy with it)
         if (VE > 8) __builtin_amdgcn_sched_barrier(0);
     }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -337,7 +377,7 @@ __device__ __forceinline__ void consume_block(const uint4 (&w)[U][R], const floa
 // ------------------------------------------------------------------------------------------------
 template <typename T, typename TO, typename WT, int R, int U, bool PF, bool NT, bool SWIGLU, int XPT>
 __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const T* __restrict__ x, const WT* __restrict__ W,
-                                                          const float* __restrict__ wscale, const T* __restrict__ norm_w,
+                                                          const WScaleT<WT>* __restrict__ wscale, const T* __restrict__ norm_w,
                                                           const T* res, TO* y, int N, int K,
                                                           float eps) {
     extern __shared__ __attribute__((aligned(16))) float xs[];     // [K] fp32 (+8 floats of reduction scratch)
@@ -358,6 +398,8 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const T* __restrict__ 
     };
 
     uint4 wa[U][R];
+    unsigned sa[U][R];                            // MXFP4 block scales of wa
+    const long long rowlen = K / WPer<WT>::v;     // WT units per row
     int grp = blockIdx.x * GV_WAVES + wid;
     // PF (host guarantees nchunk >= STEP): NO branch around the prefetch -- at a control-flow merge hipcc waits vmcnt(0),
     // which would drain the weights before the prologue.  Waves past the last group prefetch a clamped (valid) row.
@@ -365,34 +407,42 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const T* __restrict__ 
         if (PF) {
             const int gp = min(grp, ngroups - 1);
             const WT* rowp[R];
+            const unsigned char* srow[R];
 #pragma unroll
-            for (int r = 0; r < R; ++r) rowp[r] = W + row_of(gp, r) * K;
-            issue_block<WT, R, U, NT, true>(wa, rowp, 0, lane, nchunk);
+            for (int r = 0; r < R; ++r) {
+                rowp[r] = W + row_of(gp, r) * rowlen;
+                srow[r] = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) + row_of(gp, r) * nchunk : nullptr;
+            }
+            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, 0, lane, nchunk);
         }
     });
 
     bool have = PF;
     for (; grp < ngroups; grp += nwaves) {
         const WT* rowp[R];
+        const unsigned char* srow[R];
         long long rows[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) { rows[r] = row_of(grp, r); rowp[r] = W + rows[r] * K; }
+        for (int r = 0; r < R; ++r) {
+            rows[r] = row_of(grp, r); rowp[r] = W + rows[r] * rowlen;
+            srow[r] = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) + rows[r] * nchunk : nullptr;
+        }
         float sc[R];                                 // row scales: loaded ahead of the weight stream, never waited on later
 #pragma unroll
-        for (int r = 0; r < R; ++r) sc[r] = wscale ? wscale[rows[r]] : 1.f;
+        for (int r = 0; r < R; ++r) sc[r] = (!IsMx<WT>::v && wscale) ? (float)wscale[rows[r]] : 1.f;
         float acc[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = 0.f;
         int c0 = 0;
-        if (have) { consume_block<T, WT, R, U, true, RowsImage16<T, WT>::v>(wa, xs, 0, lane, nchunk, acc); c0 = STEP; have = false; }
+        if (have) { consume_block<T, WT, R, U, true, RowsImage16<T, WT>::v>(wa, sa, xs, 0, lane, nchunk, acc); c0 = STEP; have = false; }
         const int cfull = (nchunk / STEP) * STEP;          // steady state: no bounds checks, no exec masking
         for (; c0 < cfull; c0 += STEP) {
-            issue_block<WT, R, U, NT, true>(wa, rowp, c0, lane, nchunk);
-            consume_block<T, WT, R, U, true, RowsImage16<T, WT>::v>(wa, xs, c0, lane, nchunk, acc);
+            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, c0, lane, nchunk);
+            consume_block<T, WT, R, U, true, RowsImage16<T, WT>::v>(wa, sa, xs, c0, lane, nchunk, acc);
         }
         if (c0 < nchunk) {
-            issue_block<WT, R, U, NT, false>(wa, rowp, c0, lane, nchunk);
-            consume_block<T, WT, R, U, false, RowsImage16<T, WT>::v>(wa, xs, c0, lane, nchunk, acc);
+            issue_block<WT, R, U, NT, false>(wa, sa, rowp, srow, c0, lane, nchunk);
+            consume_block<T, WT, R, U, false, RowsImage16<T, WT>::v>(wa, sa, xs, c0, lane, nchunk, acc);
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = wave_sum(acc[r]);
@@ -427,7 +477,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const T* __restrict__ 
 // ------------------------------------------------------------------------------------------------
 template <typename T, typename TO, typename WT, int R, int U, bool NT>
 __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __restrict__ x, const WT* __restrict__ W,
-                                                                 const float* __restrict__ wscale, const T* res,
+                                                                 const WScaleT<WT>* __restrict__ wscale, const T* res,
                                                                  TO* y, int N, int K) {
     constexpr int VE = Vec16<WT>::N, VX = Vec16<T>::N;
     constexpr int XL = VE / VX;                           // 16-byte x loads per weight chunk (1, or 2 for fp8 weights)
@@ -435,7 +485,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int nchunk = K / VE;
     const int row0 = blockIdx.x * R;
-    const float my_scale = (wscale && tid < R && row0 + tid < N) ? wscale[row0 + tid] : 1.f;   // ahead of the stream
+    const float my_scale = (!IsMx<WT>::v && wscale && tid < R && row0 + tid < N) ? (float)wscale[row0 + tid] : 1.f;   // ahead of the stream
     // the residual too: read after the reduction barrier it is a dependent global round trip at the tail of EVERY workgroup
     // (all of them are resident at once, so the whole launch ends one memory latency later); only this thread writes y[n]
     const float my_res = (res && tid < R && row0 + tid < N) ? Elem<T>::ld(res + row0 + tid) : 0.f;
@@ -443,13 +493,26 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[r] = 0.f;
     const WT* wrow[R];
+    const unsigned char* srow[R];                         // MXFP4: the rows' e8m0 bytes, one per chunk
 #pragma unroll
-    for (int r = 0; r < R; ++r) wrow[r] = W + (long long)min(row0 + r, N - 1) * K;
+    for (int r = 0; r < R; ++r) {
+        wrow[r] = W + (long long)min(row0 + r, N - 1) * (K / WPer<WT>::v);
+        srow[r] = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) + (long long)min(row0 + r, N - 1) * nchunk : nullptr;
+    }
     // chunk index for (iteration, unroll u): c = cb + u*256 + wid*64 + lane
     auto step = [&](int cb, auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
         uint4 xr[U][XL];
         uint4 w[U][R];
+        unsigned sx[U][R];
+        if constexpr (IsMx<WT>::v) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int c = cb + u * 256 + wid * 64 + lane;
+#pragma unroll
+                for (int r = 0; r < R; ++r) sx[u][r] = (FULL || c < nchunk) ? (unsigned)srow[r][c] : 0u;
+            }
+        }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int c = cb + u * 256 + wid * 64 + lane;
@@ -462,11 +525,14 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
             const int c = cb + u * 256 + wid * 64 + lane;
 #pragma unroll
             for (int r = 0; r < R; ++r)
-                w[u][r] = (FULL || c < nchunk) ? ld16<NT>(wrow[r] + (long long)c * VE) : make_uint4(0, 0, 0, 0);
+                w[u][r] = (FULL || c < nchunk) ? ld16<NT>(wrow[r] + (long long)c * CU<WT>::v) : make_uint4(0, 0, 0, 0);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            if constexpr (Is16<T>::v) {                  // raw 16-bit activations straight into v_dot2_f32_{bf16,f16}
+            if constexpr (IsMx<WT>::v) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) acc[r] = dot_mx(w[u][r], xr[u], e8m0_scale(sx[u][r]), acc[r]);
+            } else if constexpr (Is16<T>::v) {           // raw 16-bit activations straight into v_dot2_f32_{bf16,f16}
 #pragma unroll
                 for (int r = 0; r < R; ++r) acc[r] = dotb<WT>(w[u][r], xr[u], acc[r]);
             } else {
@@ -509,7 +575,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
 // ------------------------------------------------------------------------------------------------
 template <typename T, typename WT, bool NT, bool PF, int U, int XPT>
 __global__ __launch_bounds__(GV_THREADS) void gemv_qkv_rope_kernel(const WT* __restrict__ W, const T* __restrict__ x,
-                                                                   const T* __restrict__ norm_w, const float* __restrict__ wscale,
+                                                                   const T* __restrict__ norm_w, const WScaleT<WT>* __restrict__ wscale,
                                                                    const int* __restrict__ d_pos, int K, int H, int Hk, int hd,
                                                                    T* __restrict__ qout, const float* __restrict__ cs,
                                                                    const float* __restrict__ sn, T* __restrict__ kc,
@@ -542,14 +608,18 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_qkv_rope_kernel(const WT* __r
     };
 
     uint4 wa[U][R];
+    unsigned sa[U][R];                                   // MXFP4 block scales of wa
+    const long long rowlen = K / WPer<WT>::v;
+    const unsigned char* sbase = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) : nullptr;
     const int grp0 = blockIdx.x * GV_WAVES + wid;
     stage_x<T, VE, BfImage<T, WT>::v, XPT>(x, norm_w, xs, red, K, eps, [&]() {
         if (PF) {                                         // branch-free (see gemv_kernel)
             long long rows[R];
             int head, i0;
             rows_of(min(grp0, ngroups - 1), rows, head, i0);
-            const WT* rowp[R] = {W + rows[0] * K, W + rows[1] * K};
-            issue_block<WT, R, U, NT, true>(wa, rowp, 0, lane, nchunk);
+            const WT* rowp[R] = {W + rows[0] * rowlen, W + rows[1] * rowlen};
+            const unsigned char* srow[R] = {sbase ? sbase + rows[0] * nchunk : nullptr, sbase ? sbase + rows[1] * nchunk : nullptr};
+            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, 0, lane, nchunk);
         }
     });
 
@@ -558,22 +628,23 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_qkv_rope_kernel(const WT* __r
         long long rows[R];
         int head = 0, i0 = 0;
         const bool is_qk = rows_of(grp, rows, head, i0);
-        const WT* rowp[R] = {W + rows[0] * K, W + rows[1] * K};
+        const WT* rowp[R] = {W + rows[0] * rowlen, W + rows[1] * rowlen};
+        const unsigned char* srow[R] = {sbase ? sbase + rows[0] * nchunk : nullptr, sbase ? sbase + rows[1] * nchunk : nullptr};
         // rotation coefficients of this pair: loaded before the weight stream so the epilogue never waits on memory
         float rc = 1.f, rs = 0.f;
         if (is_qk) { rc = cs[(long long)pos * half + i0]; rs = sn[(long long)pos * half + i0]; }
-        const float sc0 = wscale ? wscale[rows[0]] : 1.f, sc1 = wscale ? wscale[rows[1]] : 1.f;
+        const float sc0 = (!IsMx<WT>::v && wscale) ? (float)wscale[rows[0]] : 1.f, sc1 = (!IsMx<WT>::v && wscale) ? (float)wscale[rows[1]] : 1.f;
         float acc[R] = {0.f, 0.f};
         int c0 = 0;
-        if (have) { consume_block<T, WT, R, U, true>(wa, xs, 0, lane, nchunk, acc); c0 = STEP; have = false; }
+        if (have) { consume_block<T, WT, R, U, true>(wa, sa, xs, 0, lane, nchunk, acc); c0 = STEP; have = false; }
         const int cfull = (nchunk / STEP) * STEP;
         for (; c0 < cfull; c0 += STEP) {
-            issue_block<WT, R, U, NT, true>(wa, rowp, c0, lane, nchunk);
-            consume_block<T, WT, R, U, true>(wa, xs, c0, lane, nchunk, acc);
+            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, c0, lane, nchunk);
+            consume_block<T, WT, R, U, true>(wa, sa, xs, c0, lane, nchunk, acc);
         }
         if (c0 < nchunk) {
-            issue_block<WT, R, U, NT, false>(wa, rowp, c0, lane, nchunk);
-            consume_block<T, WT, R, U, false>(wa, xs, c0, lane, nchunk, acc);
+            issue_block<WT, R, U, NT, false>(wa, sa, rowp, srow, c0, lane, nchunk);
+            consume_block<T, WT, R, U, false>(wa, sa, xs, c0, lane, nchunk, acc);
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = wave_sum(acc[r]);
@@ -609,7 +680,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_qkv_rope_kernel(const WT* __r
 // host dispatch  (kernels: `res` and the output may be the same buffer -- in-place residual add -- so neither is __restrict__)
 // ------------------------------------------------------------------------------------------------
 template <typename T, typename TO, typename WT, int R, int U, bool PF, int XPT = 6>
-static int launch_rows(const void* x, const void* W, const float* ws, const void* norm_w, const void* res, void* y, int N,
+static int launch_rows(const void* x, const void* W, const void* ws, const void* norm_w, const void* res, void* y, int N,
                        int K, float eps, bool swiglu, hipStream_t st) {
     if (PF && K / Vec16<WT>::N < 64 * U)          // the unconditional prefetch needs one full step per row
         return launch_rows<T, TO, WT, R, U, false>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);   // (short rows: the default prologue)
@@ -618,7 +689,8 @@ static int launch_rows(const void* x, const void* W, const float* ws, const void
     if (blocks > tune().gemv_max_blocks) blocks = tune().gemv_max_blocks;
     const size_t lds = x_image_bytes<RowsImage16<T, WT>::v, Vec16<WT>::N>(K);
 #define TEO_GV(NTV, SW)                                                                                              \
-    TEO_KLAUNCH((gemv_kernel<T, TO, WT, R, U, PF, NTV, SW, XPT>), blocks, GV_THREADS, lds, st, (const T*)x, (const WT*)W, ws, (const T*)norm_w, \
+    TEO_KLAUNCH((gemv_kernel<T, TO, WT, R, U, PF, NTV, SW, XPT>), blocks, GV_THREADS, lds, st, (const T*)x, (const WT*)W, (const WScaleT<WT>*)ws, \
+                (const T*)norm_w, \
                 (const T*)res, (TO*)y, N, K, eps)
     if (tune().gemv_nt) { if (swiglu) TEO_GV(true, true); else TEO_GV(true, false); }
     else           { if (swiglu) TEO_GV(false, true); else TEO_GV(false, false); }
@@ -628,18 +700,19 @@ static int launch_rows(const void* x, const void* W, const float* ws, const void
 }
 
 template <typename T, typename TO, typename WT, int R, int U>
-static int launch_splitk(const void* x, const void* W, const float* ws, const void* res, void* y, int N, int K, hipStream_t st) {
+static int launch_splitk(const void* x, const void* W, const void* ws, const void* res, void* y, int N, int K, hipStream_t st) {
     const int blocks = cdiv(N, R);
+    const WScaleT<WT>* s = (const WScaleT<WT>*)ws;
     if (tune().gemv_nt)
-        TEO_KLAUNCH((gemv_splitk_kernel<T, TO, WT, R, U, true>), blocks, GV_THREADS, 0, st, (const T*)x, (const WT*)W, ws, (const T*)res, (TO*)y, N, K);
+        TEO_KLAUNCH((gemv_splitk_kernel<T, TO, WT, R, U, true>), blocks, GV_THREADS, 0, st, (const T*)x, (const WT*)W, s, (const T*)res, (TO*)y, N, K);
     else
-        TEO_KLAUNCH((gemv_splitk_kernel<T, TO, WT, R, U, false>), blocks, GV_THREADS, 0, st, (const T*)x, (const WT*)W, ws, (const T*)res, (TO*)y, N, K);
+        TEO_KLAUNCH((gemv_splitk_kernel<T, TO, WT, R, U, false>), blocks, GV_THREADS, 0, st, (const T*)x, (const WT*)W, s, (const T*)res, (TO*)y, N, K);
     TEO_LAUNCH_CHECK("gemv_splitk");
     return TEO_OK;
 }
 
 template <typename T, typename TO, typename WT>
-static int gemv_launch(const void* x, const void* W, const float* ws, const void* norm_w, const void* res, void* y, int N, int K,
+static int gemv_launch(const void* x, const void* W, const void* ws, const void* norm_w, const void* res, void* y, int N, int K,
                        float eps, bool swiglu, hipStream_t st) {
     // few long rows without a fused norm (o / down projections): split-K workgroups, 2 rows each (measured best).
     // U is chosen so that ONE step covers the whole row (256*U chunks): every load of the workgroup is in flight at once
@@ -666,6 +739,25 @@ static int gemv_launch(const void* x, const void* W, const float* ws, const void
     }
     const bool fits = K / Vec16<T>::N <= 2 * GV_THREADS;              // the x prologue fits 2 chunks per thread (stage_x)
     const bool small_k = fits && (tune().gemv_small_k != 0);
+    if constexpr (IsMx<WT>::v) {
+        // MXFP4 rows are a quarter of bf16's (K = 4096: 128 chunks, 2 KB).  4 rows x 2 chunks = 8 KB per wave per step, the whole row in
+        // one step, as fp8's 2 x 4.  U sets the fp32 order of the image's sums (see below): it stays 2 whatever gemv_small_k says, and
+        // gemv_small_k picks only the prologue.  gemv_variant 10..13 take fp8's geometries (fp32 order).
+        if (small_k) {
+            switch (tune().gemv_variant) {
+                case 10: return launch_rows<T, TO, WT, 2, 4, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
+                case 12: return launch_rows<T, TO, WT, 2, 2, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
+                case 13: return launch_rows<T, TO, WT, 4, 4, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
+                default: return launch_rows<T, TO, WT, 4, 2, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
+            }
+        }
+        switch (tune().gemv_variant) {
+            case 10: return launch_rows<T, TO, WT, 2, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
+            case 12: return launch_rows<T, TO, WT, 2, 2, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
+            case 13: return launch_rows<T, TO, WT, 4, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
+            default: return launch_rows<T, TO, WT, 4, 2, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
+        }
+    }
     // >= 4 KiB contiguous per row per step streams ~7 % faster than 2 KiB; first block prefetched under the prologue.
     // fp8 rows are half as long: 4 rows per wave keep the same bytes in flight per lane
     if constexpr (sizeof(WT) == 1) {
@@ -698,18 +790,25 @@ static int gemv_launch(const void* x, const void* W, const float* ws, const void
     return launch_rows<T, TO, WT, 2, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
 }
 
-// w_dtype: -1 = same as dtype, 2 = fp8 e4m3 with per-row fp32 scales (bf16 activations only)
-int gemv_w(const void* x, const void* W, const float* wscale, int w_fp8, const void* norm_w, const void* res, void* y, int N,
+// wfmt (ops.h GemvWFmt): the activations' type, fp8 e4m3 with per-row fp32 scales, or MXFP4 with [N][K/32] e8m0 bytes (both: bf16
+// activations only)
+int gemv_w(const void* x, const void* W, const void* wscale, int wfmt, const void* norm_w, const void* res, void* y, int N,
            int K, float eps, unsigned flags, int dtype, int out_dtype, hipStream_t st) {
     if (N == 0) return TEO_OK;
     const bool swiglu = flags & TEO_GEMM_SWIGLU16;
-    const int ve = w_fp8 ? 16 : (dtype == TEO_F32 ? 4 : 8);
+    const bool w_fp8 = wfmt == GV_W_FP8, w_mx = wfmt == GV_W_MXFP4;
+    const int ve = w_mx ? 32 : (w_fp8 ? 16 : (dtype == TEO_F32 ? 4 : 8));
     TEO_CHECK_ARG(K % ve == 0, "teo_gemv: K=%d must be a multiple of %d", K, ve);
     TEO_CHECK_ARG((reinterpret_cast<uintptr_t>(W) & 15) == 0, "teo_gemv: W must be 16-byte aligned");
     TEO_CHECK_ARG((size_t)(K + 1040) * 4 <= 64 * 1024, "teo_gemv: K=%d too large for LDS staging", K);
     TEO_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (norm_w == nullptr || (reinterpret_cast<uintptr_t>(norm_w) & 15) == 0),
                   "teo_gemv: x / norm_w must be 16-byte aligned");
     if (swiglu) TEO_CHECK_ARG(N % 32 == 0 && !res, "teo_gemv: SWIGLU16 needs N %% 32 == 0 and no residual");
+    if (w_mx) {
+        TEO_CHECK_ARG(dtype == TEO_BF16 && wscale != nullptr, "teo_gemv: MXFP4 weights need bf16 activations and block scales");
+        if (out_dtype == TEO_F32) return gemv_launch<bf16_t, float, fp4x2_t>(x, W, wscale, norm_w, res, y, N, K, eps, swiglu, st);
+        return gemv_launch<bf16_t, bf16_t, fp4x2_t>(x, W, wscale, norm_w, res, y, N, K, eps, swiglu, st);
+    }
     if (w_fp8) {
         TEO_CHECK_ARG(dtype == TEO_BF16 && wscale != nullptr, "teo_gemv: fp8 weights need bf16 activations and per-row scales");
         if (out_dtype == TEO_F32) return gemv_launch<bf16_t, float, fp8_t>(x, W, wscale, norm_w, res, y, N, K, eps, swiglu, st);
@@ -733,44 +832,51 @@ int gemv_w(const void* x, const void* W, const float* wscale, int w_fp8, const v
 
 int gemv(const void* x, const void* W, const void* norm_w, const void* res, void* y, int N, int K, float eps,
          unsigned flags, int dtype, int out_dtype, hipStream_t st) {
-    return gemv_w(x, W, nullptr, 0, norm_w, res, y, N, K, eps, flags, dtype, out_dtype, st);
+    return gemv_w(x, W, nullptr, GV_W_NATIVE, norm_w, res, y, N, K, eps, flags, dtype, out_dtype, st);
 }
 
-int gemv_qkv_rope(const void* x, const void* W, const float* wscale, int w_fp8, const void* norm_w, void* qout,
+int gemv_qkv_rope(const void* x, const void* W, const void* wscale, int wfmt, const void* norm_w, void* qout,
                   const float* cs, const float* sn, const int* d_pos, void* kc, void* vc, void* vtc, int S_max, int H, int Hk,
                   int hd, int K, float eps, int dtype, hipStream_t st) {
-    const int ve = w_fp8 ? 16 : (dtype == TEO_F32 ? 4 : 8);
+    const bool w_fp8 = wfmt == GV_W_FP8, w_mx = wfmt == GV_W_MXFP4;
+    const int ve = w_mx ? 32 : (w_fp8 ? 16 : (dtype == TEO_F32 ? 4 : 8));
     TEO_CHECK_ARG(K % ve == 0 && hd >= 2 && (hd & (hd - 1)) == 0, "gemv_qkv_rope: K=%d hd=%d (head_dim must be a power of two)", K, hd);
     TEO_CHECK_ARG((size_t)(K + 1040) * 4 <= 64 * 1024, "gemv_qkv_rope: K=%d too large for LDS staging", K);
-    TEO_CHECK_ARG(!w_fp8 || (dtype == TEO_BF16 && wscale), "gemv_qkv_rope: fp8 weights need bf16 activations and scales");
+    TEO_CHECK_ARG(!(w_fp8 || w_mx) || (dtype == TEO_BF16 && wscale), "gemv_qkv_rope: fp8 / MXFP4 weights need bf16 activations and scales");
     const int ngroups = (H + Hk) * (hd / 2) + Hk * hd / 2;
     int blocks = cdiv(ngroups, GV_WAVES);
     if (blocks > tune().gemv_max_blocks) blocks = tune().gemv_max_blocks;
-    const size_t lds = w_fp8 ? xb_lds_bytes<16>(K) : (dtype == TEO_F32 ? xs_lds_bytes<4>(K) : xs_lds_bytes<8>(K));
+    const size_t lds = w_mx ? xb_lds_bytes<32>(K) : (w_fp8 ? xb_lds_bytes<16>(K) : (dtype == TEO_F32 ? xs_lds_bytes<4>(K) : xs_lds_bytes<8>(K)));
     // small x prologue (2 register chunks per thread) whenever K allows: fewer VGPRs, more waves per SIMD (see stage_x); fp8 rows then
     // take 4 chunks per step like the row-group kernel (8 KB per wave in flight)
     const bool fits = K / (dtype == TEO_F32 ? 4 : 8) <= 2 * GV_THREADS;
     const bool small_k = (tune().gemv_small_k != 0) && fits;
     // (fp8: U sets the fp32 order of the bf16 image's sums, see gemv_launch -- it follows what K allows, not gemv_small_k)
-    const int uu = (w_fp8 && !fits) ? 2 : 4;
+    // (MXFP4: a K = 4096 row is 128 chunks -- 2 chunks per step take it whole; U = 2 at every K keeps one order of the sums)
+    const int uu = w_mx ? 2 : ((w_fp8 && !fits) ? 2 : 4);
     const bool pf = K / ve >= 64 * uu;
 #define TEO_QR2(TT, WW, NTV, XP, UU)                                                                                      \
-    if (pf) TEO_KLAUNCH((gemv_qkv_rope_kernel<TT, WW, NTV, true, UU, XP>), blocks, GV_THREADS, lds, st, (const WW*)W, (const TT*)x, (const TT*)norm_w, wscale, \
+    if (pf) TEO_KLAUNCH((gemv_qkv_rope_kernel<TT, WW, NTV, true, UU, XP>), blocks, GV_THREADS, lds, st, (const WW*)W, (const TT*)x, (const TT*)norm_w, \
+                                                                       (const WScaleT<WW>*)wscale, \
                                                                        d_pos, K, H, Hk, hd, (TT*)qout, cs, sn, (TT*)kc, (TT*)vc, (TT*)vtc, \
                                                                        S_max, eps);                                          \
-    else TEO_KLAUNCH((gemv_qkv_rope_kernel<TT, WW, NTV, false, UU, XP>), blocks, GV_THREADS, lds, st, (const WW*)W, (const TT*)x, (const TT*)norm_w, wscale, \
+    else TEO_KLAUNCH((gemv_qkv_rope_kernel<TT, WW, NTV, false, UU, XP>), blocks, GV_THREADS, lds, st, (const WW*)W, (const TT*)x, (const TT*)norm_w, \
+                                                                       (const WScaleT<WW>*)wscale, \
                                                                        d_pos, K, H, Hk, hd, (TT*)qout, cs, sn, (TT*)kc, (TT*)vc, (TT*)vtc, \
                                                                        S_max, eps)
 #define TEO_QR(TT, WW, NTV) if (small_k) { TEO_QR2(TT, WW, NTV, 2, 4); } else { TEO_QR2(TT, WW, NTV, 6, 4); }
 #define TEO_QR6(TT, WW, NTV) TEO_QR2(TT, WW, NTV, 6, 4)
 #define TEO_QR8(TT, WW, NTV) if (small_k) { TEO_QR2(TT, WW, NTV, 2, 4); } else if (fits) { TEO_QR2(TT, WW, NTV, 6, 4); } else { TEO_QR2(TT, WW, NTV, 6, 2); }
-    if (w_fp8)                 { if (tune().gemv_nt) { TEO_QR8(bf16_t, fp8_t, true); } else { TEO_QR8(bf16_t, fp8_t, false); } }
+#define TEO_QR4(TT, WW, NTV) if (small_k) { TEO_QR2(TT, WW, NTV, 2, 2); } else { TEO_QR2(TT, WW, NTV, 6, 2); }
+    if (w_mx)                  { if (tune().gemv_nt) { TEO_QR4(bf16_t, fp4x2_t, true); } else { TEO_QR4(bf16_t, fp4x2_t, false); } }
+    else if (w_fp8)                 { if (tune().gemv_nt) { TEO_QR8(bf16_t, fp8_t, true); } else { TEO_QR8(bf16_t, fp8_t, false); } }
     else if (dtype == TEO_F32) { if (tune().gemv_nt) { TEO_QR6(float, float, true); } else { TEO_QR6(float, float, false); } }
     else if (dtype == TEO_F16) { if (tune().gemv_nt) { TEO_QR(f16_t, f16_t, true); } else { TEO_QR(f16_t, f16_t, false); } }
     else                       { if (tune().gemv_nt) { TEO_QR(bf16_t, bf16_t, true); } else { TEO_QR(bf16_t, bf16_t, false); } }
 #undef TEO_QR
 #undef TEO_QR6
 #undef TEO_QR8
+#undef TEO_QR4
 #undef TEO_QR2
     TEO_LAUNCH_CHECK("gemv_qkv_rope");
     return TEO_OK;

@@ -380,6 +380,15 @@ static DecodeWs decode_carve(const teo_llama_desc* d, void* ws, size_t cap) {
 size_t llama_decode_workspace_bytes(const teo_llama_desc* d) { return decode_carve(d, nullptr, 0).total; }
 
 int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
+    // MXFP4 copies: all eight per-layer arrays or none, never beside the fp8 copies, bf16 activations (checked before any launch)
+    const bool w4 = d->qkv_w4 != nullptr;
+    if (w4 || d->qkv_e4 || d->o_w4 || d->o_e4 || d->gateup_w4 || d->gateup_e4 || d->down_w4 || d->down_e4) {
+        TEO_CHECK_ARG(d->qkv_w4 && d->qkv_e4 && d->o_w4 && d->o_e4 && d->gateup_w4 && d->gateup_e4 && d->down_w4 && d->down_e4,
+                      "teo_llama_decode_step: the MXFP4 copies need all of qkv/o/gateup/down _w4 and _e4");
+        TEO_CHECK_ARG(!d->qkv_w8 && !d->o_w8 && !d->gateup_w8 && !d->down_w8 && !d->lm_head8,
+                      "teo_llama_decode_step: a descriptor carries fp8 (w8) or MXFP4 (w4) decode weights, not both");
+        TEO_CHECK_ARG(d->dtype == TEO_BF16, "teo_llama_decode_step: MXFP4 weights need bf16 activations");
+    }
     const DecodeWs w = decode_carve(d, ws, ws_bytes);
     if (w.total > ws_bytes) {
         set_error("teo_llama_decode_step: workspace %zu < %zu", ws_bytes, w.total);
@@ -389,13 +398,16 @@ int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* 
     const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim, F = d->inter;
     const int QKV = (H + 2 * Hk) * hd;
     // w.h holds the embedding of *s->d_token: written by the previous step's tail (or by teo_llama_decode_begin)
-    const bool w8 = d->qkv_w8 != nullptr;              // decode streams the fp8 copies when they are present
+    const bool w8 = d->qkv_w8 != nullptr;              // decode streams the fp8 or MXFP4 copies when they are present
+    const int wf = w4 ? GV_W_MXFP4 : (w8 ? GV_W_FP8 : GV_W_NATIVE);
+    auto lin = [&](const void* const* w16, const void* const* q8, const void* const* q4, int l) { return w4 ? q4[l] : (w8 ? q8[l] : w16[l]); };
+    auto scl = [&](const float* const* s8, const uint8_t* const* e4, int l) -> const void* { return w4 ? (const void*)e4[l] : (w8 ? (const void*)s8[l] : nullptr); };
     for (int l = 0; l < d->layers; ++l) {
         if (d->rope_in_attn) {
             // rmsnorm + QKV projection (plain weight stream); RoPE + KV append ride inside the attention kernel
             // (position read from s->d_pos on the device)
             prof_class(TEO_PROF_QKV);
-            TEO_TRY(gemv_w(w.h, w8 ? d->qkv_w8[l] : d->qkv_w[l], w8 ? d->qkv_s[l] : nullptr, w8, d->in_norm_w[l], nullptr,
+            TEO_TRY(gemv_w(w.h, lin(d->qkv_w, d->qkv_w8, d->qkv_w4, l), scl(d->qkv_s, d->qkv_e4, l), wf, d->in_norm_w[l], nullptr,
                            w.qkv, QKV, D, d->eps, 0, dt, dt, st));
             prof_class(TEO_PROF_ATTN);
             TEO_TRY(attn_decode(w.qkv, d->k_cache[l], d->v_cache[l], d->vt_cache[l], d->rope_cos, d->rope_sin, w.attn, w.part,
@@ -403,7 +415,7 @@ int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* 
         } else {
             // rmsnorm -> QKV projection -> RoPE -> KV append in the GEMV epilogue
             prof_class(TEO_PROF_QKV);
-            TEO_TRY(gemv_qkv_rope(w.h, w8 ? d->qkv_w8[l] : d->qkv_w[l], w8 ? d->qkv_s[l] : nullptr, w8, d->in_norm_w[l], w.qkv,
+            TEO_TRY(gemv_qkv_rope(w.h, lin(d->qkv_w, d->qkv_w8, d->qkv_w4, l), scl(d->qkv_s, d->qkv_e4, l), wf, d->in_norm_w[l], w.qkv,
                                   d->rope_cos, d->rope_sin, s->d_pos, d->k_cache[l], d->v_cache[l], d->vt_cache[l], d->max_seq,
                                   H, Hk, hd, D, d->eps, dt, st));
             prof_class(TEO_PROF_ATTN);
@@ -411,17 +423,17 @@ int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* 
                                 d->max_seq, H, Hk, hd, 1.0f / sqrtf((float)hd), dt, st));
         }
         prof_class(TEO_PROF_O);
-        TEO_TRY(gemv_w(w.attn, w8 ? d->o_w8[l] : d->o_w[l], w8 ? d->o_s[l] : nullptr, w8, nullptr, w.h, w.h, D, H * hd, d->eps,
+        TEO_TRY(gemv_w(w.attn, lin(d->o_w, d->o_w8, d->o_w4, l), scl(d->o_s, d->o_e4, l), wf, nullptr, w.h, w.h, D, H * hd, d->eps,
                        0, dt, dt, st));
         prof_class(TEO_PROF_GATEUP);
-        TEO_TRY(gemv_w(w.h, w8 ? d->gateup_w8[l] : d->gateup_w[l], w8 ? d->gateup_s[l] : nullptr, w8, d->post_norm_w[l], nullptr,
+        TEO_TRY(gemv_w(w.h, lin(d->gateup_w, d->gateup_w8, d->gateup_w4, l), scl(d->gateup_s, d->gateup_e4, l), wf, d->post_norm_w[l], nullptr,
                        w.act, 2 * F, D, d->eps, TEO_GEMM_SWIGLU16, dt, dt, st));
         prof_class(TEO_PROF_DOWN);
-        TEO_TRY(gemv_w(w.act, w8 ? d->down_w8[l] : d->down_w[l], w8 ? d->down_s[l] : nullptr, w8, nullptr, w.h, w.h, D, F, d->eps,
+        TEO_TRY(gemv_w(w.act, lin(d->down_w, d->down_w8, d->down_w4, l), scl(d->down_s, d->down_e4, l), wf, nullptr, w.h, w.h, D, F, d->eps,
                        0, dt, dt, st));
     }
     {
-        const bool h8 = d->lm_head8 != nullptr;
+        const bool h8 = d->lm_head8 != nullptr;          // (the MXFP4 mode keeps a 16-bit lm_head)
         prof_class(TEO_PROF_LM_HEAD);
         TEO_TRY(gemv_w(w.h, h8 ? d->lm_head8 : d->lm_head, h8 ? d->lm_head_s : nullptr, h8, d->final_norm_w, nullptr,
                        s->d_logits, d->vocab, D, d->eps, 0, dt, TEO_F32, st));

@@ -81,6 +81,71 @@ def quantize_fp8_rows(w):
     return q.view(torch.uint8).contiguous(), s.contiguous(), dq.contiguous()
 
 
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)      # magnitudes of the OCP e2m1 codes 0..7 (bit 3 = sign)
+MX_E_MIN, MX_E_MAX = 2, 252                               # e8m0 range the quantiser writes: every nonzero weight a finite bf16 normal
+
+
+def _e2m1_round(a):
+    """|v| -> e2m1 magnitude code 0..7: round to nearest on the grid, ties to the even code, saturating at 6."""
+    mids = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)          # midpoint i lies between codes i and i + 1
+    code = torch.zeros(a.shape, dtype=torch.uint8, device=a.device)
+    for i, m in enumerate(mids):
+        code += ((a > m) | ((a == m) & (i % 2 == 1))).to(torch.uint8)
+    return code
+
+
+def quantize_mxfp4_blocks(w):
+    """MXFP4 (OCP microscaling FP4) quantisation of W [N, K] in blocks of 32 along K: W ~= e2m1(q) * 2^(e - 127).
+
+    Returns (q uint8 [N, K/2], e uint8 [N, K/32], dq bf16 [N, K]):
+      q  -- e2m1 codes, byte j of a row holds k = 2j in the low nibble and k = 2j + 1 in the high one; magnitude codes 0..7 are
+            {0, 0.5, 1, 1.5, 2, 3, 4, 6}, bit 3 the sign (set only on a nonzero magnitude: zeros are +0);
+      e  -- one e8m0 biased exponent per block, row-major: scale = 2^(e - 127);
+      dq -- e2m1(q) * 2^(e - 127) exactly.  An e2m1 value has at most two significant bits and the scale is a power of two, so every
+            dq is a bfloat16 number: a bf16 GEMM on dq and the MXFP4 GEMV on (q, e) see the same weights.
+    Definition, per block of 32 values v (computed in float64):
+      elements: v / 2^s rounded to nearest on the e2m1 grid, ties to the even code (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2,
+                2.5 -> 2, 3.5 -> 4, 5 -> 4), saturating at +-6;
+      scale:    e0 = the smallest integer with amax <= 6 * 2^e0 (= ceil(log2(amax / 6))), clamped to [2 - 127, 252 - 127]; of e0 and
+                e0 - 1 (when still in range) the one whose rounded block has the smaller sum of squared errors, e0 on a tie
+                (e0 - 1 clips the largest value at 6 when that lowers the block's error);
+      zeros:    an all-zero block gets e = 127 and zero codes.
+    K % 32 != 0 raises ValueError."""
+    if w.dim() != 2 or w.shape[1] % 32 != 0:
+        raise ValueError(f"quantize_mxfp4_blocks: K must be a multiple of 32, got shape {tuple(w.shape)}")
+    N, K = w.shape
+    v = w.to(torch.float64).reshape(N, K // 32, 32)
+    amax = v.abs().amax(dim=2)
+    nz = amax > 0
+    e0 = torch.ceil(torch.log2(torch.where(nz, amax, torch.ones_like(amax)) / 6.0))
+    e0 = e0 - (6.0 * torch.exp2(e0 - 1) >= amax).to(e0.dtype)      # exact fix-ups of the log2 rounding: smallest e with amax <= 6 * 2^e
+    e0 = e0 + (6.0 * torch.exp2(e0) < amax).to(e0.dtype)
+    e0 = e0.clamp(MX_E_MIN - 127, MX_E_MAX - 127)
+    grid = torch.tensor(E2M1_GRID, dtype=torch.float64, device=w.device)
+
+    def rounded(ex):
+        sc = torch.exp2(ex)[..., None]
+        code = _e2m1_round((v / sc).abs())
+        val = torch.where(v < 0, -grid[code.long()], grid[code.long()]) * sc
+        return code, val, ((val - v) ** 2).sum(dim=2)
+
+    c0, d0, err0 = rounded(e0)
+    e1 = (e0 - 1).clamp_min(MX_E_MIN - 127)
+    c1, d1, err1 = rounded(e1)
+    take1 = (err1 < err0) & (e1 < e0)
+    code = torch.where(take1[..., None], c1, c0)
+    val = torch.where(take1[..., None], d1, d0)
+    ex = torch.where(take1, e1, e0)
+    code = torch.where(nz[..., None], code, torch.zeros_like(code))
+    val = torch.where(nz[..., None], val, torch.zeros_like(val))
+    e = torch.where(nz, ex + 127, torch.full_like(ex, 127)).to(torch.uint8)
+    code = code | ((v < 0) & (code > 0)).to(torch.uint8) << 3
+    code = code.reshape(N, K)
+    q = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    dq = val.reshape(N, K).to(torch.bfloat16).contiguous()
+    return q, e.contiguous(), dq
+
+
 def rope_tables(head_dim, theta, max_pos):
     """cos/sin [max_pos, hd/2] fp32; inv_freq and pos*inv_freq in fp32 on the host (tf LlamaRotaryEmbedding)."""
     inv = 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.float32) / head_dim))
@@ -100,13 +165,14 @@ class TeoEngine:
         self.device = torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device)
         self.max_seq = int(math.ceil((max_seq or config.max_position_embeddings) / 64.0) * 64)
-        self.weight_format = weight_format or "native"          # "fp8": decode streams fp8-e4m3 copies (config C5)
-        if self.weight_format not in ("native", "fp8"):
+        # "fp8": decode streams fp8-e4m3 copies (config C5); "mxfp4": decode streams MXFP4 copies (4-bit, one e8m0 scale per 32 weights)
+        self.weight_format = weight_format or "native"
+        if self.weight_format not in ("native", "fp8", "mxfp4"):
             raise ValueError(f"unknown weight_format {weight_format!r}")
-        if self.weight_format == "fp8" and dtype != torch.bfloat16:
-            # the power-of-two row scales make every dequantised e4m3 weight an exact bfloat16; in binary16 the smallest ones fall
-            # into the subnormal range and would not be exact (and the fp8 GEMV / skinny kernels convert e4m3 -> bf16)
-            raise ValueError("weight_format='fp8' needs dtype=torch.bfloat16")
+        if self.weight_format in ("fp8", "mxfp4") and dtype != torch.bfloat16:
+            # the power-of-two scales make every dequantised e4m3 / e2m1 weight an exact bfloat16; in binary16 the smallest ones fall
+            # into the subnormal range and would not be exact (and the fp8 / MXFP4 GEMV kernels convert to bf16)
+            raise ValueError(f"weight_format={self.weight_format!r} needs dtype=torch.bfloat16")
         self._keep = []                           # host pointer arrays referenced by the descriptors
         self._ws = {}
         self._phase_depth = 0
@@ -246,6 +312,19 @@ class TeoEngine:
             q, s, dq = quantize_fp8_rows(self.lm_head)
             self.lm_head, self.lm_head8, self.lm_head_s = dq, q, s
             self.llama_w8 = (w8, s8)
+        self.llama_w4 = None
+        if self.weight_format == "mxfp4":
+            # the same for the single-conversation decode step in MXFP4 (blocks of 32 along K); lm_head stays 16-bit, and prefill, the
+            # tower and the batched step read the bf16 tensors, replaced by the exact dequantisation
+            w4 = {k: [] for k in ("qkv", "o", "gateup", "down")}
+            e4 = {k: [] for k in ("qkv", "o", "gateup", "down")}
+            for k in w4:
+                for i in range(c.num_hidden_layers):
+                    q, e, dq = quantize_mxfp4_blocks(per[k][i])
+                    per[k][i] = dq
+                    w4[k].append(q)
+                    e4[k].append(e)
+            self.llama_w4 = (w4, e4)
 
     def _alloc_cache(self):
         c = self.cfg
@@ -276,6 +355,12 @@ class TeoEngine:
             d.gateup_w8, d.gateup_s = self._arr(w8["gateup"]), self._arr(s8["gateup"])
             d.down_w8, d.down_s = self._arr(w8["down"]), self._arr(s8["down"])
             d.lm_head8, d.lm_head_s = self.lm_head8.data_ptr(), self.lm_head_s.data_ptr()
+        if self.llama_w4 is not None:
+            w4, e4 = self.llama_w4
+            d.qkv_w4, d.qkv_e4 = self._arr(w4["qkv"]), self._arr(e4["qkv"])
+            d.o_w4, d.o_e4 = self._arr(w4["o"]), self._arr(e4["o"])
+            d.gateup_w4, d.gateup_e4 = self._arr(w4["gateup"]), self._arr(e4["gateup"])
+            d.down_w4, d.down_e4 = self._arr(w4["down"]), self._arr(e4["down"])
         d.tune = self.tune.ptr
         self.llama_desc = d
 

@@ -11,6 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE TCC_EA0_RDREQ_sum; do
   rm -rf /tmp/pmcd_$C
   timeout 900 rocprofv3 --kernel-trace --pmc $C -d /tmp/pmcd_$C -o p -- python3 $ROOT/bench.py --full --steps 1 --warmup 0 --new 12 --no-cpu-baseline --no-graph > /tmp/pmcd_$C.log 2>&1
+  rc=$?; if [ $rc -ne 0 ]; then echo "pass $C failed ($rc): no further GPU passes"; exit $rc; fi
 done
 python3 - "$COMMIT" "$ROOT" <<'PY'
 import glob, json, os, sqlite3, sys
