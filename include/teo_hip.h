@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define TEO_ABI_VERSION 3 /* 3: MXFP4 decode weights (teo_llama_desc *_w4 / *_e4, teo_gemv_w4); 2: teo_tune blocks, `tune` last in the descriptors, teo_sizeof */
+#define TEO_ABI_VERSION 4 /* 4: MXFP4 weights in the batched decode step (teo_gemm_skinny_w4, teo_decode_batch_state.w_mxfp4); 3: MXFP4 decode weights (teo_llama_desc *_w4 / *_e4, teo_gemv_w4); 2: teo_tune blocks, `tune` last in the descriptors, teo_sizeof */
 
 typedef void* teo_stream_t; /* hipStream_t */
 
@@ -45,7 +45,7 @@ typedef enum {
 #define TEO_GEMM_FORCE_SIMPLE 2u /* use the shape-agnostic VALU kernel even when the MFMA kernel applies */
 #define TEO_GEMM_SWIGLU8 8u /* teo_gemm_skinny: like SWIGLU16 with gate/up rows interleaved in blocks of 8 */
 #define TEO_GEMM_F16 16u /* teo_gemm_skinny: x / W / residual are IEEE half (implied by a TEO_F16 output; needed with a TEO_F32 one) */
-#define TEO_GEMM_WTILED 4u /* teo_gemm_skinny: W is stored as 1 KB operand tiles (16 rows x 32 k bf16 / 64 k fp8), see below */
+#define TEO_GEMM_WTILED 4u /* teo_gemm_skinny / teo_gemm_skinny_w4: W is stored as 1 KB operand tiles (16 rows x 32 k bf16 / 64 k fp8 / 128 k MXFP4), see below */
 
 int teo_version(void);
 const char* teo_last_error(void);
@@ -328,6 +328,24 @@ int teo_gemm_skinny(const void* d_x, const void* d_W, const float* d_w_scale, in
                     const void* d_residual, void* d_out, int MB, int N, int K, int ldx, int ldo, unsigned flags, int out_dtype,
                     teo_stream_t stream);
 
+/* teo_gemm_skinny with MXFP4 weights (the values of teo_gemv_w4: W[n, k] = e2m1(code) * 2^(E - 127), one E per 32 k); bf16 activations,
+ * out bf16 / f32, residual, d_norm_w, TEO_GEMM_SWIGLU16 / _SWIGLU8 as in teo_gemm_skinny.  Every code is converted exactly to the
+ * bfloat16 it stands for (block scale included) and multiplied on v_mfma_f32_16x16x32_bf16, so the result is the product with the
+ * dequantised bf16 matrix up to the fp32 order of the sums; there is no row scale.  One k-step is 128 k: K % 128 != 0 returns
+ * TEO_ERR_UNSUPPORTED.
+ * TEO_GEMM_WTILED is REQUIRED (row-major teo_gemv_w4 arrays return TEO_ERR_UNSUPPORTED).  The tiled layout, Np = N rounded up to 16:
+ *   d_W4   ceil(N/16) * (K/128) tiles of 1 KB; tile (n/16, k/128) starts at ((n/16) * (K/128) + k/128) KB.  In it the 16-byte lane
+ *          l = ((k % 128) / 32) * 16 + n % 16 holds bytes [16 l, 16 l + 16): the 16 code bytes of the ONE MX block (row n, block k/32),
+ *          in teo_gemv_w4's order (byte j of the lane = elements k0 + 2j in the low nibble, k0 + 2j + 1 in the high one, k0 = k - k % 32).
+ *          One wave-level load reads 1 KB contiguous; MFMA j (0..3) of a step takes dword j of every lane.
+ *   d_e8m0 64 bytes per tile at ((n/16) * (K/128) + k/128) * 64; byte l = E of lane l's block (one contiguous 64-byte wave access).
+ *   Rows past N: zero codes, E = 127.
+ * In torch terms (teochat_amd.engine.tile_weights_mxfp4): codes q.view(Np/16, 16, K/128, 4, 16).permute(0, 2, 3, 1, 4), scales
+ * e.view(Np/16, 16, K/128, 4).permute(0, 2, 3, 1).  With TEO_GEMM_SWIGLU8 / _SWIGLU16 the ROWS are interleaved before tiling, codes and
+ * scales alike.  The skinny_* keys of teo_tune apply under their stated contracts; skinny_unr has no 4-bit form and is ignored. */
+int teo_gemm_skinny_w4(const void* d_x, const void* d_W4, const void* d_e8m0, const void* d_norm_w, float eps, const void* d_residual,
+                       void* d_out, int MB, int N, int K, int ldx, int ldo, unsigned flags, int out_dtype, teo_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Composed runtime entry points (the layer loops live in C++, not Python)
  * ------------------------------------------------------------------------------------------- */
@@ -399,12 +417,16 @@ typedef struct {
     const void* const* gateup_w8; const float* const* gateup_s;
     const void* const* down_w8;   const float* const* down_s;
     const void* lm_head8;         const float* lm_head_s;
-    /* Optional MXFP4 copies for the single-conversation DECODE step (teo_gemv_w4's format: [N, K/2] code bytes, [N, K/32] e8m0 bytes),
-     * same row layouts as above (gate/up interleaved-16).  The dequantised weights are exact bfloat16 numbers: prefill, the
-     * batched step and the tower keep reading the 16-bit weights above, which a caller sets to the dequantised values.
-     * teo_llama_decode_step (and its graph / profile forms) streams these when qkv_w4 is set; lm_head stays 16-bit.  All eight or
-     * none; bf16 only; a descriptor holding both *_w8 and *_w4 copies is TEO_ERR_ARG.  teo_llama_decode_batch_step and the
-     * prefill entry points ignore them.  All NULL -> today's behaviour. */
+    /* Optional MXFP4 copies for the DECODE steps.  The dequantised weights are exact bfloat16 numbers: prefill and the tower keep
+     * reading the 16-bit weights above, which a caller sets to the dequantised values; lm_head stays 16-bit.
+     *  - teo_llama_decode_step (and its graph / profile forms) streams these when qkv_w4 is set: teo_gemv_w4's row-major format
+     *    ([N, K/2] code bytes, [N, K/32] e8m0 bytes), same row layouts as above (gate/up interleaved-16).  All eight or none; bf16
+     *    only; a descriptor holding both *_w8 and *_w4 copies is TEO_ERR_ARG.
+     *  - teo_llama_decode_batch_step (and _begin / _step_profile / _graph_create) reads them only when teo_decode_batch_state.w_mxfp4
+     *    is 1, and then in teo_gemm_skinny_w4's TILED layout (a batched-step descriptor is a copy of the prefill descriptor with these
+     *    eight arrays replaced); with w_mxfp4 = 0 it ignores them and streams the 16-bit / fp8 matrices.
+     *  - the prefill entry points ignore them.
+     * All NULL -> no MXFP4 anywhere. */
     const void* const* qkv_w4;    const uint8_t* const* qkv_e4;
     const void* const* o_w4;      const uint8_t* const* o_e4;
     const void* const* gateup_w4; const uint8_t* const* gateup_e4;
@@ -503,7 +525,7 @@ int teo_graph_destroy(teo_graph* g);
  * (argmax / sampler, append, stop test, next embedding) runs per conversation.  The descriptor is the one used for
  * prefill except that k_cache/v_cache/vt_cache[l] point at conversation 0 of a [B][...] allocation and
  * `cache_stride` (elements) separates consecutive conversations; with w_tiled = 1 its weight matrices (qkv/o/gateup/
- * down/lm_head, bf16 or fp8) are in the TEO_GEMM_WTILED layout.  Finished conversations keep stepping (their d_stop
+ * down/lm_head, bf16 or fp8; with w_mxfp4 = 1 the four MXFP4 layer matrices and the 16-bit lm_head) are in the TEO_GEMM_WTILED layout.  Finished conversations keep stepping (their d_stop
  * is set; the host truncates), exactly like the single-conversation loop. */
 #define TEO_MAX_DECODE_BATCH 16
 typedef struct {
@@ -511,8 +533,12 @@ typedef struct {
     int out_stride;           /* d_out_tokens is [batch][out_stride] */
     long long cache_stride;   /* elements between conversations in each layer's K, V and V^T cache */
     int w_tiled;              /* 1: the descriptor's decode weight matrices are TEO_GEMM_WTILED */
-    int gateup_block8;        /* 1: the descriptor's gate/up matrices (and their fp8 scales) interleave gate/up rows in blocks
-                               * of 8 (TEO_GEMM_SWIGLU8) instead of 16 -- one row tile per workgroup also for the SwiGLU GEMM */
+    int gateup_block8;        /* 1: the descriptor's gate/up matrices (and their fp8 scales / MXFP4 codes and scales) interleave gate/up
+                               * rows in blocks of 8 (TEO_GEMM_SWIGLU8) instead of 16 -- one row tile per workgroup also for the SwiGLU GEMM */
+    int w_mxfp4;              /* 1: qkv / o / gateup / down come from the descriptor's *_w4 / *_e4 arrays in teo_gemm_skinny_w4's tiled
+                               * layout (lm_head stays 16-bit, tiled).  Needs all eight arrays, w_tiled = 1, no fp8 copies (*_w8, lm_head8)
+                               * and bf16: TEO_ERR_ARG otherwise; a hidden, attention (heads * head_dim) or intermediate size that is not
+                               * a multiple of 128: TEO_ERR_UNSUPPORTED.  0: the step ignores the *_w4 / *_e4 fields */
     long long* d_token;       /* [batch] */
     int* d_pos;               /* [batch] */
     long long* d_out_tokens;  /* [batch][out_stride] */

@@ -85,6 +85,7 @@ COMM_ID_BYTES = 128
 
 class DecodeBatchState(C.Structure):
     _fields_ = [("batch", C.c_int), ("out_stride", C.c_int), ("cache_stride", C.c_longlong), ("w_tiled", C.c_int), ("gateup_block8", C.c_int),
+                ("w_mxfp4", C.c_int),
                 ("d_token", C.c_void_p), ("d_pos", C.c_void_p), ("d_out_tokens", C.c_void_p),
                 ("d_out_count", C.c_void_p), ("d_stop", C.c_void_p), ("d_stop_ids", C.c_void_p),
                 ("n_stop_ids", C.c_int), ("d_logits", C.c_void_p),
@@ -171,6 +172,8 @@ _SIGS = {
                                             C.POINTER(C.c_float), C.POINTER(C.c_ubyte), C.c_int, C.c_void_p]),
     "teo_gemm_skinny": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
                         + [C.c_int] * 5 + [C.c_uint, C.c_int, C.c_void_p]),
+    "teo_gemm_skinny_w4": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+                           + [C.c_int] * 5 + [C.c_uint, C.c_int, C.c_void_p]),
     "teo_comm_unique_id": (C.c_int, [C.c_void_p]),
     "teo_ctx_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "teo_ctx_destroy": (C.c_int, [C.c_void_p]),
@@ -179,7 +182,7 @@ _SIGS = {
     "teo_ctx_tune": (C.c_void_p, [C.c_void_p]),
 }
 
-ABI_VERSION = 3            # TEO_ABI_VERSION of include/teo_hip.h this binding was written against
+ABI_VERSION = 4            # TEO_ABI_VERSION of include/teo_hip.h this binding was written against
 # (the ctypes mirrors of the header's structs are checked against the library's own sizeof at load: a stale or newer .so must fail
 # THERE, not by reading shifted fields)
 

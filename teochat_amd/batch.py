@@ -7,7 +7,8 @@ own KV cache and position, finished conversations keep being stepped and are cut
 `BatchDecoder` borrows the weights of a `TeoEngine` and owns
   * KV caches [layers][B][Hkv][S][hd] (+ V^T), conversation b = slot b,
   * per-slot descriptors for the (unchanged, one conversation at a time) prefill kernels,
-  * a copy of the decode weight matrices in the TEO_GEMM_WTILED layout (include/teo_hip.h) when the activations are bf16,
+  * a copy of the decode weight matrices in the TEO_GEMM_WTILED layout (include/teo_hip.h) when the activations are bf16 -- or, on an
+    mxfp4 engine with set_options(batch_mxfp4=True), tiled MXFP4 copies of the four layer matrices and a 16-bit tiled lm_head only,
   * the device-resident batch state and the hipGraph of one batched step.
 """
 import ctypes as C
@@ -15,7 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .engine import _p, reinterleave_gate_up, tile_weights
+from .engine import _p, reinterleave_gate_up, tile_weights, tile_weights_mxfp4
 
 
 class BatchDecoder:
@@ -50,7 +51,32 @@ class BatchDecoder:
             and (c.num_attention_heads * hd) % ks == 0
         self.tiled_w = None
         self.block8 = False
-        if self.tiled:
+        # engine option batch_mxfp4: stream tiled MXFP4 copies of qkv / o / gateup / down (one k-step = 128 k).  Sizes that are not
+        # multiples of 128 fall back to the 16-bit tiled step below (w4 stays False)
+        self.w4_requested = bool(getattr(engine, "batch_mxfp4", False))
+        self.w4 = self.w4_requested and engine.llama_w4 is not None and self.tiled and dt == torch.bfloat16 and c.hidden_size % 128 == 0 \
+            and c.intermediate_size % 128 == 0 and (c.num_attention_heads * hd) % 128 == 0
+        if self.w4:
+            q4, e4 = engine.llama_w4
+            self.block8 = True                    # (intermediate_size % 128 == 0)
+            tq, te = {}, {}
+            for k in ("qkv", "o", "gateup", "down"):
+                tq[k], te[k] = [], []
+                for q, e in zip(q4[k], e4[k]):
+                    if k == "gateup":             # rows re-interleaved to blocks of 8, codes and exponents alike
+                        q, e = reinterleave_gate_up(q, 8), reinterleave_gate_up(e, 8)
+                    qt, et = tile_weights_mxfp4(q, e)
+                    tq[k].append(qt)
+                    te[k].append(et)
+            head = tile_weights(engine.lm_head)
+            self.tiled_w4 = (tq, te)
+            self.tiled_w = (None, head)           # no 16-bit tiled copies of the layer matrices
+            d.qkv_w4, d.qkv_e4 = self._arr(tq["qkv"]), self._arr(te["qkv"])
+            d.o_w4, d.o_e4 = self._arr(tq["o"]), self._arr(te["o"])
+            d.gateup_w4, d.gateup_e4 = self._arr(tq["gateup"]), self._arr(te["gateup"])
+            d.down_w4, d.down_e4 = self._arr(tq["down"]), self._arr(te["down"])
+            d.lm_head = head.data_ptr()
+        elif self.tiled:
             src = engine.llama_w8[0] if fp8 else engine.llama_w
             # gate/up: pairs re-interleaved in blocks of 8 rows so a gate row and its up row share one 16-row tile
             self.block8 = c.intermediate_size % 16 == 0
@@ -101,6 +127,7 @@ class BatchDecoder:
         assert self.v_cache.stride(1) == s.cache_stride and self.vt_cache.stride(1) == s.cache_stride
         s.w_tiled = 1 if self.tiled else 0
         s.gateup_block8 = 1 if self.block8 else 0
+        s.w_mxfp4 = 1 if self.w4 else 0
         s.d_token, s.d_pos, s.d_out_tokens = self.d_token.data_ptr(), self.d_pos.data_ptr(), self.d_out.data_ptr()
         s.d_out_count, s.d_stop = self.d_count.data_ptr(), self.d_stop.data_ptr()
         s.d_stop_ids, s.n_stop_ids, s.d_logits = self.d_stop_ids.data_ptr(), 0, self.d_logits.data_ptr()

@@ -309,11 +309,13 @@ def load_generation_config(model, model_dir):
 
 
 def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, load_4bit=False, device_map="auto",
-                          device="cuda", cache_dir=None, dtype=None, max_seq=None, seed=2, weight_format=None):
+                          device="cuda", cache_dir=None, dtype=None, max_seq=None, seed=2, weight_format=None,
+                          batch_mxfp4=False):
     """dtype None = the reference's choice where it has one: a real checkpoint runs in torch.float16 (builder.py:105 passes
     torch_dtype=torch.float16 whatever the file holds; eval/inference.py:53 casts the frames to match) -- unless fp8 or MXFP4 decode weights
     are requested (weight_format="fp8" / "mxfp4"), which go with bfloat16 -- and the synthetic presets in torch.bfloat16 (BASELINE.json's
-    headline dtype).  load_4bit (bitsandbytes NF4 in the reference) is not rerouted to MXFP4."""
+    headline dtype).  load_4bit (bitsandbytes NF4 in the reference) is not rerouted to MXFP4.  batch_mxfp4=True (with weight_format="mxfp4"):
+    the batched decode step streams MXFP4 weights too (TeoEngine.set_options)."""
     if device in (None, "cuda"):
         device = "cuda:0"
     if dtype is None:
@@ -351,6 +353,8 @@ def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, l
             tokenizer = ByteTokenizer()
     engine = TeoEngine(sd, cfg, dtype=dtype, device=device, max_seq=max_seq, weight_format=weight_format)
     del sd
+    if batch_mxfp4:
+        engine.set_options(batch_mxfp4=True)      # ValueError unless weight_format="mxfp4"
     image_processor = TeoImageProcessor(size=cfg.vision_config.image_size, engine=engine)     # uint8 frames -> device kernel
     model = LlavaLlamaForCausalLM(cfg, engine, image_processor)
     # GenerationMixin's fallback knobs belong to the model object, which the LoRA / projector branches build with

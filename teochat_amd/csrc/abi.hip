@@ -478,6 +478,19 @@ static int check_batch_state(const teo_llama_desc* d, const teo_decode_batch_sta
         NEED(st->d_rng, "d_rng"); TEO_CHECK_ARG(st->temperature > 0.f, "decode batch: temperature %g", st->temperature);
         const int rc = sampler_check(d->vocab, st->top_k, st->top_p); if (rc != TEO_OK) return rc;
     }
+    if (st->w_mxfp4) {                                    // MXFP4 layer matrices (tiled): checked before any launch
+        TEO_CHECK_ARG(d->qkv_w4 && d->qkv_e4 && d->o_w4 && d->o_e4 && d->gateup_w4 && d->gateup_e4 && d->down_w4 && d->down_e4,
+                      "decode batch: w_mxfp4 needs all of qkv/o/gateup/down _w4 and _e4");
+        TEO_CHECK_ARG(st->w_tiled, "decode batch: w_mxfp4 reads the TEO_GEMM_WTILED layout (w_tiled = 1)");
+        TEO_CHECK_ARG(!d->qkv_w8 && !d->o_w8 && !d->gateup_w8 && !d->down_w8 && !d->lm_head8,
+                      "decode batch: a descriptor carries fp8 (w8) or MXFP4 (w4) decode weights, not both");
+        TEO_CHECK_ARG(d->dtype == TEO_BF16, "decode batch: MXFP4 weights need bf16 activations");
+        if (d->hidden % 128 != 0 || d->inter % 128 != 0 || (d->heads * d->head_dim) % 128 != 0) {
+            set_error("decode batch: w_mxfp4 needs hidden %d, heads * head_dim %d and inter %d to be multiples of 128", d->hidden,
+                      d->heads * d->head_dim, d->inter);
+            return TEO_ERR_UNSUPPORTED;
+        }
+    }
     return TEO_OK;
 }
 
@@ -594,7 +607,26 @@ int teo_gemm_skinny(const void* x, const void* W, const float* w_scale, int w_fp
     TEO_CHECK_ARG(out_dtype == TEO_BF16 || out_dtype == TEO_F32 || out_dtype == TEO_F16, "teo_gemm_skinny: out_dtype %d", out_dtype);
     if (MB == 0 || N == 0) return TEO_OK;
     NEED(x, "x"); NEED(W, "W"); NEED(out, "out");
-    return skinny_gemm(x, W, w_scale, w_fp8, norm_w, eps, res, out, MB, N, K, ldx, ldo, flags, out_dtype, ST(s));
+    return skinny_gemm(x, W, w_scale, w_fp8 ? SK_W_FP8 : SK_W_16, norm_w, eps, res, out, MB, N, K, ldx, ldo, flags, out_dtype, ST(s));
+}
+
+int teo_gemm_skinny_w4(const void* x, const void* W4, const void* e8m0, const void* norm_w, float eps, const void* res, void* out, int MB,
+                       int N, int K, int ldx, int ldo, unsigned flags, int out_dtype, teo_stream_t s) {
+    ENTER();
+    TEO_CHECK_ARG(MB >= 0 && N >= 0 && K > 0, "teo_gemm_skinny_w4: MB %d N %d K %d", MB, N, K);
+    TEO_CHECK_ARG(out_dtype == TEO_BF16 || out_dtype == TEO_F32, "teo_gemm_skinny_w4: out_dtype %d (bf16 activations: bf16 or f32 out)", out_dtype);
+    TEO_CHECK_ARG(!(flags & TEO_GEMM_F16), "teo_gemm_skinny_w4: MXFP4 weights go with bfloat16 activations");
+    if (K % 128 != 0) {
+        set_error("teo_gemm_skinny_w4: K=%d is not a multiple of the 128-k step (four MX blocks)", K);
+        return TEO_ERR_UNSUPPORTED;
+    }
+    if (!(flags & TEO_GEMM_WTILED)) {
+        set_error("teo_gemm_skinny_w4: row-major MXFP4 arrays are not supported, pass the TEO_GEMM_WTILED layout");
+        return TEO_ERR_UNSUPPORTED;
+    }
+    if (MB == 0 || N == 0) return TEO_OK;
+    NEED(x, "x"); NEED(W4, "W4"); NEED(e8m0, "e8m0"); NEED(out, "out");
+    return skinny_gemm(x, W4, e8m0, SK_W_MXFP4, norm_w, eps, res, out, MB, N, K, ldx, ldo, flags, out_dtype, ST(s));
 }
 
 }  // extern "C"

@@ -62,7 +62,10 @@ int cross_entropy(const float* logits, long long ld, const long long* labels, fl
                   long long ignore_index, hipStream_t st);
 bool patch_embed_ok(int C, int img, int P, int ldw, int D, int dtype, const void* px, const void* W, const void* out);
 int patch_embed(const void* px, const void* W, void* out, int T, int C, int img, int P, int ldw, int D, hipStream_t st, bool f16 = false);
-bool skinny_gemm_ok(int MB, int N, int K, int ldx, int w_fp8, unsigned flags, const void* x, const void* W);
+// weight formats of the skinny GEMM: 16-bit (the activations' own type), fp8 e4m3 + one fp32 scale per row, MXFP4 (tiled e2m1 codes + tiled
+// e8m0 block exponents, include/teo_hip.h teo_gemm_skinny_w4).  (0 / 1 are what the `w_fp8` flag of the C ABI passes.)
+enum SkinnyWFmt { SK_W_16 = 0, SK_W_FP8 = 1, SK_W_MXFP4 = 2 };
+bool skinny_gemm_ok(int MB, int N, int K, int ldx, int wfmt, unsigned flags, const void* x, const void* W);
 // Producer-side RMSNorm hand-off between the GEMMs of a batched decode step.  A residual-producing GEMM (o / down
 // projection, one row tile per workgroup) also emits xg_out = bf16(h * next_g) and ssq_out[b][workgroup] = its 16
 // columns' share of sum(h[b]^2); the consumer GEMM takes x = xg_out as a plain operand and rebuilds 1/rms per row from
@@ -78,7 +81,7 @@ struct SkinnyFuse {
     unsigned long long* trace = nullptr;      // probe builds only (tools/skinny_probe.hip): [workgroups][SK_TRACE_SLOTS] wall-clock marks
 };
 constexpr int SK_TRACE_SLOTS = 16;
-int skinny_gemm(const void* x, const void* W, const float* wscale, int w_fp8, const void* norm_w, float eps, const void* res,
+int skinny_gemm(const void* x, const void* W, const void* wscale, int wfmt, const void* norm_w, float eps, const void* res,
                 void* out, int MB, int N, int K, int ldx, int ldo, unsigned flags, int out_dtype, hipStream_t st,
                 SkinnyFuse fuse = SkinnyFuse());
 // operands of one bf16 / f16 GEMM call for the launch helpers of the tile families, which take their geometry from a GemmPlan

@@ -476,9 +476,9 @@ size_t llama_decode_batch_workspace_bytes(const teo_llama_desc* d, int batch) {
 }
 
 // Can every Linear layer of the step run on the MFMA skinny GEMM?  (bf16 activations, K multiples of the k-step.)
-static bool batch_uses_skinny(const teo_llama_desc* d, int B) {
+static bool batch_uses_skinny(const teo_llama_desc* d, int B, bool w4 = false) {
     if (d->dtype != TEO_BF16 && d->dtype != TEO_F16) return false;
-    const int w8 = d->qkv_w8 != nullptr, h8 = d->lm_head8 != nullptr;
+    const int w8 = w4 ? SK_W_MXFP4 : (d->qkv_w8 != nullptr ? SK_W_FP8 : SK_W_16), h8 = d->lm_head8 != nullptr;
     if (d->dtype == TEO_F16 && (w8 || h8)) return false;   // fp8 weights go with bfloat16 activations
     const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim, F = d->inter;
     const void* al = reinterpret_cast<const void*>(16);   // alignment of the real pointers is checked at launch
@@ -488,7 +488,7 @@ static bool batch_uses_skinny(const teo_llama_desc* d, int B) {
 }
 
 // fallback row loop: y[b] = f(norm(x[b])) W^T (+ res[b]) with the single-conversation GEMV (fp32, odd K)
-static int batch_linear_rows(int B, const void* x, int ldx, const void* W, const float* wscale, int w8, const void* norm_w,
+static int batch_linear_rows(int B, const void* x, int ldx, const void* W, const void* wscale, int w8, const void* norm_w,
                              const void* res, void* y, int ldy, int N, int K, float eps, unsigned flags, int dt, int out_dt,
                              hipStream_t st) {
     const size_t e = esize(dt), eo = esize(out_dt);
@@ -512,7 +512,7 @@ int llama_decode_batch_begin(const teo_llama_desc* d, const teo_decode_batch_sta
         set_error("teo_llama_decode_batch_begin: workspace %zu < %zu", ws_bytes, w.total);
         return TEO_ERR_WORKSPACE;
     }
-    if (batch_uses_skinny(d, s->batch))                   // also hand layer 0's RMSNorm its inputs (SkinnyFuse)
+    if (batch_uses_skinny(d, s->batch, s->w_mxfp4 != 0))  // also hand layer 0's RMSNorm its inputs (SkinnyFuse)
         return embed_token_emit(s->d_token, d->embed, w.h, d->hidden, d->dtype, st, s->batch, d->in_norm_w[0], w.hg, w.ssq, w.nparts);
     return embed_token(s->d_token, d->embed, w.h, d->hidden, d->dtype, st, s->batch);
 }
@@ -527,10 +527,14 @@ int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_stat
     const int dt = d->dtype;
     const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim, F = d->inter;
     const int QKV = (H + 2 * Hk) * hd;
+    // w4: the four layer matrices are the descriptor's tiled MXFP4 copies (teo_decode_batch_state.w_mxfp4; the C entry points have
+    // checked that they are all there, tiled, bf16 and without fp8 copies); lm_head stays 16-bit
+    const bool w4 = s->w_mxfp4 != 0;
     const bool w8 = d->qkv_w8 != nullptr, h8 = d->lm_head8 != nullptr;
-    const bool skinny = batch_uses_skinny(d, B);
-    if (!skinny && (s->w_tiled || s->gateup_block8)) {
-        set_error("teo_llama_decode_batch_step: tiled weights need bf16 activations and K %% %d == 0", w8 ? 64 : 32);
+    const int wf = w4 ? SK_W_MXFP4 : (w8 ? SK_W_FP8 : SK_W_16);
+    const bool skinny = batch_uses_skinny(d, B, w4);
+    if (!skinny && (s->w_tiled || s->gateup_block8 || w4)) {
+        set_error("teo_llama_decode_batch_step: tiled weights need bf16 activations and K %% %d == 0", w4 ? 128 : (w8 ? 64 : 32));
         return TEO_ERR_UNSUPPORTED;
     }
     const unsigned tl = s->w_tiled ? TEO_GEMM_WTILED : 0u;
@@ -542,15 +546,18 @@ int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_stat
     take.ssq_in = w.ssq; take.nparts = w.nparts; take.eps = d->eps;
     take.f16 = dt == TEO_F16;
     for (int l = 0; l < d->layers; ++l) {
-        const void* qkv_w = w8 ? d->qkv_w8[l] : d->qkv_w[l];
-        const void* o_w = w8 ? d->o_w8[l] : d->o_w[l];
-        const void* gu_w = w8 ? d->gateup_w8[l] : d->gateup_w[l];
-        const void* dn_w = w8 ? d->down_w8[l] : d->down_w[l];
-        const float *qkv_s = w8 ? d->qkv_s[l] : nullptr, *o_s = w8 ? d->o_s[l] : nullptr;
-        const float *gu_s = w8 ? d->gateup_s[l] : nullptr, *dn_s = w8 ? d->down_s[l] : nullptr;
+        const void* qkv_w = w4 ? d->qkv_w4[l] : (w8 ? d->qkv_w8[l] : d->qkv_w[l]);
+        const void* o_w = w4 ? d->o_w4[l] : (w8 ? d->o_w8[l] : d->o_w[l]);
+        const void* gu_w = w4 ? d->gateup_w4[l] : (w8 ? d->gateup_w8[l] : d->gateup_w[l]);
+        const void* dn_w = w4 ? d->down_w4[l] : (w8 ? d->down_w8[l] : d->down_w[l]);
+        // fp8: fp32 row scales; MXFP4: the tiled e8m0 block exponents
+        const void* qkv_s = w4 ? (const void*)d->qkv_e4[l] : (w8 ? (const void*)d->qkv_s[l] : nullptr);
+        const void* o_s = w4 ? (const void*)d->o_e4[l] : (w8 ? (const void*)d->o_s[l] : nullptr);
+        const void* gu_s = w4 ? (const void*)d->gateup_e4[l] : (w8 ? (const void*)d->gateup_s[l] : nullptr);
+        const void* dn_s = w4 ? (const void*)d->down_e4[l] : (w8 ? (const void*)d->down_s[l] : nullptr);
         prof_class(TEO_PROF_QKV);
         if (skinny) {
-            TEO_TRY(skinny_gemm(w.hg, qkv_w, qkv_s, w8, nullptr, 0.f, nullptr, w.qkv, B, QKV, D, D, QKV, tl, dt, st, take));
+            TEO_TRY(skinny_gemm(w.hg, qkv_w, qkv_s, wf, nullptr, 0.f, nullptr, w.qkv, B, QKV, D, D, QKV, tl, dt, st, take));
         } else {
             TEO_TRY(batch_linear_rows(B, w.h, D, qkv_w, qkv_s, w8, d->in_norm_w[l], nullptr, w.qkv, QKV, QKV, D, d->eps, 0, dt, dt, st));
         }
@@ -563,13 +570,13 @@ int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_stat
             give.f16 = dt == TEO_F16;
             give.next_g = (const unsigned short*)d->post_norm_w[l]; give.xg_out = (unsigned short*)w.hg; give.ssq_out = w.ssq;
             prof_class(TEO_PROF_O);
-            TEO_TRY(skinny_gemm(w.attn, o_w, o_s, w8, nullptr, 0.f, w.h, w.h, B, D, H * hd, H * hd, D, tl, dt, st, give));
+            TEO_TRY(skinny_gemm(w.attn, o_w, o_s, wf, nullptr, 0.f, w.h, w.h, B, D, H * hd, H * hd, D, tl, dt, st, give));
             prof_class(TEO_PROF_GATEUP);
-            TEO_TRY(skinny_gemm(w.hg, gu_w, gu_s, w8, nullptr, 0.f, nullptr, w.act, B, 2 * F, D, D, F,
+            TEO_TRY(skinny_gemm(w.hg, gu_w, gu_s, wf, nullptr, 0.f, nullptr, w.act, B, 2 * F, D, D, F,
                                 tl | (s->gateup_block8 ? TEO_GEMM_SWIGLU8 : TEO_GEMM_SWIGLU16), dt, st, take));
             give.next_g = (const unsigned short*)(l + 1 < d->layers ? d->in_norm_w[l + 1] : d->final_norm_w);
             prof_class(TEO_PROF_DOWN);
-            TEO_TRY(skinny_gemm(w.act, dn_w, dn_s, w8, nullptr, 0.f, w.h, w.h, B, D, F, F, D, tl, dt, st, give));
+            TEO_TRY(skinny_gemm(w.act, dn_w, dn_s, wf, nullptr, 0.f, w.h, w.h, B, D, F, F, D, tl, dt, st, give));
         } else {
             prof_class(TEO_PROF_O);
             TEO_TRY(batch_linear_rows(B, w.attn, H * hd, o_w, o_s, w8, nullptr, w.h, w.h, D, D, H * hd, d->eps, 0, dt, dt, st));

@@ -16,6 +16,9 @@
 //     then scale (fp8), SwiGLU, residual and rounding happen once.  x comes from L2 (K*MB*2 bytes per workgroup).
 //   * fp8-e4m3 weights: a lane's 16-byte chunk covers 16 k of one row = two MFMAs (the k-permutation inside a
 //     64-k step is the same for W and x, so the dot product is unchanged); fp8 -> bf16 is exact.
+//   * MXFP4 weights (mx4_t, tiled only): a lane's 16-byte chunk is the 32 codes of ONE MX block of one row = four MFMAs; the block's
+//     e8m0 exponent comes from a parallel 64-byte-per-tile array (one byte per lane) and goes into the conversion
+//     (v_cvt_scalef32_pk_bf16_fp4), which is exact: the products are those of the dequantised bf16 weights, no scale in the epilogue.
 #include "common.h"
 #include "ops.h"
 
@@ -26,6 +29,9 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef unsigned char fp8_t;
+struct mx4_t { unsigned char v; };     // one byte = two e2m1 codes (element 2j in the low nibble, 2j + 1 in the high one)
+template <typename T> struct IsMx4 { static constexpr bool v = false; };
+template <> struct IsMx4<mx4_t> { static constexpr bool v = true; };
 
 constexpr int SK_WAVES = 8;
 constexpr int SK_THREADS = SK_WAVES * 64;
@@ -67,6 +73,18 @@ __device__ __forceinline__ bf16x8 fp8x8_to_bf16x8(unsigned a, unsigned b) {
     return __builtin_bit_cast(bf16x8, r);
 }
 
+// 8 e2m1 codes (one dword, teo_gemv_w4's nibble order) * 2^(E - 127) -> 8 bf16, exact: four v_cvt_scalef32_pk_bf16_fp4 (one byte = two
+// codes per instruction).  e = the block's e8m0 byte
+__device__ __forceinline__ bf16x8 fp4x8_to_bf16x8(unsigned a, unsigned e) {
+    const float sc = __uint_as_float(e << 23);
+    u32x4 r;
+    r.x = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(a, sc, 0));
+    r.y = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(a, sc, 1));
+    r.z = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(a, sc, 2));
+    r.w = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(a, sc, 3));
+    return __builtin_bit_cast(bf16x8, r);
+}
+
 // x (8 values) * g (8 values) -> 8 values of the same 16-bit format (one rounding), and the sum of squares of x
 template <bool F16>
 __device__ __forceinline__ u32x4 sk_scale_frag(const u32x4& xv, const u32x4& gv, float& ssq) {
@@ -89,15 +107,18 @@ __device__ __forceinline__ u32x4 sk_scale_frag(const u32x4& xv, const u32x4& gv,
 template <typename WT, int UNR, bool NT, bool SWIGLU, bool NORM, bool TRACE = false, int WV = SK_WAVES>
 __global__ __launch_bounds__(WV * 64) void skinny_gemm_kernel(const WT* __restrict__ W, const bf16_t* __restrict__ x,
                                                                  int MB, int N, int K, int ldx, int tiled, int RT,
-                                                                 const float* __restrict__ wscale, const bf16_t* res,
+                                                                 const float* __restrict__ wscale_, const bf16_t* res,
                                                                  const bf16_t* __restrict__ norm_w, float eps, void* outv,
                                                                  int ldo, int ldr, int out_f32, SkinnyFuse fuse, int sw8) {
     // (argument order: what the first weight / activation requests need sits in the 14 dwords that arrive preloaded in SGPRs)
-    constexpr bool F8 = sizeof(WT) == 1;
-    constexpr bool F16 = IsF16<WT>::v;                   // WT = f16_t: IEEE binary16 activations, weights and 16-bit outputs (bf16_t / fp8: bfloat16)
-    constexpr int KS = F8 ? 64 : 32;                     // k elements per step (one 16-byte chunk per lane)
-    constexpr int CH = F8 ? 16 : 8;                      // k elements per lane chunk
-    constexpr int XL = F8 ? 2 : 1;                       // 16-byte activation loads per step
+    constexpr bool MX = IsMx4<WT>::v;                    // MXFP4: wscale_ is the tiled e8m0 array, and no row scale exists
+    constexpr bool F8 = sizeof(WT) == 1 && !MX;
+    constexpr bool F16 = IsF16<WT>::v;                   // WT = f16_t: IEEE binary16 activations, weights and 16-bit outputs (bf16_t / fp8 / MXFP4: bfloat16)
+    constexpr int KS = MX ? 128 : (F8 ? 64 : 32);        // k elements per step (one 16-byte chunk per lane)
+    constexpr int CH = MX ? 32 : (F8 ? 16 : 8);          // k elements per lane chunk
+    constexpr int CB = MX ? 16 : CH;                     // the chunk in units of WT (MXFP4: bytes of two codes)
+    constexpr int XL = MX ? 4 : (F8 ? 2 : 1);            // 16-byte activation loads per step
+    const float* const wscale = MX ? nullptr : wscale_;
     // WV waves per workgroup: 8, or 16 (round 6: the one-tile-per-CU launches -- o / down -- split K over twice as many waves, i.e.
     // twice the weight requests of a CU in flight from the first cycle; `skinny_waves`)
     constexpr int WG_THREADS = WV * 64;
@@ -113,7 +134,7 @@ __global__ __launch_bounds__(WV * 64) void skinny_gemm_kernel(const WT* __restri
             reinterpret_cast<u32x4*>(sk_dyn)[i] = reinterpret_cast<const u32x4*>(norm_w)[i];
         __syncthreads();
     }
-    const bf16_t* gs = reinterpret_cast<const bf16_t*>(sk_dyn) + fg * (sizeof(WT) == 1 ? 16 : 8);
+    const bf16_t* gs = reinterpret_cast<const bf16_t*>(sk_dyn) + fg * CH;
     float ssq = 0.f;
     // the 8 waves of a workgroup = RT row tiles (16 weight rows each) x KSPLIT contiguous K slices
     // (RT is 1, 2, 4 or 8 -- host-checked: shifts, no integer division in front of the first weight request)
@@ -128,11 +149,15 @@ __global__ __launch_bounds__(WV * 64) void skinny_gemm_kernel(const WT* __restri
     // weight addressing.  Row-major [N][K]: a wave instruction touches 16 rows x 64 B.  Tiled (TEO_GEMM_WTILED): the
     // matrix is stored as 1 KB tiles of 16 rows x KS k in operand order (tile (n/16, k/KS) at ((n/16)*(K/KS) + k/KS) KB,
     // lane l = (k%KS)/CH*16 + n%16 owns bytes [16 l, 16 l + 16)), so one instruction reads 1 KB contiguous.
+    // MXFP4: tiled only (host-checked); the tile's 64 e8m0 bytes sit at the same tile index of a parallel array, byte = lane
     const WT* wp;
     long long pstep;
+    const unsigned char* ep = nullptr;
     if (tiled) {
-        wp = W + ((long long)min(n0 / 16 + rt, (N + 15) / 16 - 1) * nsteps) * (64 * CH) + lane * CH;
-        pstep = 64 * CH;
+        const long long t0 = (long long)min(n0 / 16 + rt, (N + 15) / 16 - 1) * nsteps;
+        wp = W + t0 * (64 * CB) + lane * CB;
+        pstep = 64 * CB;
+        if constexpr (MX) ep = reinterpret_cast<const unsigned char*>(wscale_) + t0 * 64 + lane;
     } else {
         wp = W + (long long)min(n0 + rt * 16 + fr, N - 1) * K + fg * CH;
         pstep = KS;
@@ -174,16 +199,29 @@ __global__ __launch_bounds__(WV * 64) void skinny_gemm_kernel(const WT* __restri
     // Software pipeline over the wave's K slice: two register sets of UNR steps each; every load is unconditional
     // (step index clamped to the slice, the x fragment of an out-of-range step is zeroed) so hipcc keeps counting
     // vmcnt instead of draining the queue at a control-flow merge.
-#define TEO_SK_LOAD(WR, XR, BASE)                                                                              \
+#define TEO_SK_LOAD(WR, XR, ER, BASE)                                                                          \
     _Pragma("unroll") for (int u = 0; u < UNR; ++u) {                                                          \
         const long long si = min((BASE) + u, s1 - 1);                                                          \
         WR[u] = sk_ldw<NT>(wp + si * pstep);                                                                   \
+        if constexpr (MX) ER[u] = ep[si * 64];                                                                 \
         _Pragma("unroll") for (int j = 0; j < XL; ++j)                                                         \
             XR[u][j] = *reinterpret_cast<const u32x4*>(xp + si * KS + j * 8);                                  \
     }
-#define TEO_SK_COMP(WR, XR, BASE)                                                                              \
+#define TEO_SK_COMP(WR, XR, ER, BASE)                                                                          \
     _Pragma("unroll") for (int u = 0; u < UNR; ++u) {                                                          \
         const bool ok = (BASE) + u < s1;                                                                       \
+        if constexpr (MX) {                                                                                    \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                    \
+                u32x4 xj = XR[u][j % XL]      ;                                                                \
+                if (!ok) xj = (u32x4){0u, 0u, 0u, 0u};                                                         \
+                if (NORM) {                                                                                    \
+                    const long long sg = min((BASE) + u, s1 - 1);                                              \
+                    xj = sk_scale_frag<F16>(xj, *reinterpret_cast<const u32x4*>(gs + sg * KS + j * 8), ssq);   \
+                }                                                                                              \
+                acc = mfma16<F16>(fp4x8_to_bf16x8(WR[u][j], ER[u]), __builtin_bit_cast(bf16x8, xj), acc);      \
+            }                                                                                                  \
+            continue;                                                                                          \
+        }                                                                                                      \
         u32x4 x0 = XR[u][0], x1 = XR[u][XL - 1];                                                               \
         if (!ok) { x0 = (u32x4){0u, 0u, 0u, 0u}; x1 = x0; }                                                    \
         if (NORM) {                                                                                            \
@@ -246,20 +284,21 @@ _Pragma("unroll") \
 
     if (s0 < s1) {
         u32x4 wa[UNR], xa[UNR][XL], wb[UNR], xb[UNR][XL];
+        unsigned ea[UNR], eb[UNR];                       // MXFP4: the e8m0 byte of each step's block
         int s = s0;
         TEO_SK_SSQ_LOAD
-        TEO_SK_LOAD(wa, xa, s)
+        TEO_SK_LOAD(wa, xa, ea, s)
         TEO_SK_SSQ_REDUCE
         if (wid == 0) sk_mark<TRACE>(fuse, 1);
         for (; s + 2 * UNR < s1; s += 2 * UNR) {
-            TEO_SK_LOAD(wb, xb, s + UNR)
-            TEO_SK_COMP(wa, xa, s)
-            TEO_SK_LOAD(wa, xa, s + 2 * UNR)
-            TEO_SK_COMP(wb, xb, s + UNR)
+            TEO_SK_LOAD(wb, xb, eb, s + UNR)
+            TEO_SK_COMP(wa, xa, ea, s)
+            TEO_SK_LOAD(wa, xa, ea, s + 2 * UNR)
+            TEO_SK_COMP(wb, xb, eb, s + UNR)
         }
-        TEO_SK_LOAD(wb, xb, s + UNR)
-        TEO_SK_COMP(wa, xa, s)
-        TEO_SK_COMP(wb, xb, s + UNR)
+        TEO_SK_LOAD(wb, xb, eb, s + UNR)
+        TEO_SK_COMP(wa, xa, ea, s)
+        TEO_SK_COMP(wb, xb, eb, s + UNR)
     } else {                                             // K shorter than 8 slices: this wave only owes its rows' 1/rms
         TEO_SK_SSQ_LOAD
         TEO_SK_SSQ_REDUCE
@@ -362,12 +401,15 @@ constexpr int SS_TP = 16 * 20;                 // partial tile in LDS: [b][i] at
 
 template <typename WT, int UNR, int SPT, int NS, bool SW8, bool TRACE = false>
 __global__ __launch_bounds__(SK_THREADS) void skinny_stream_kernel(const bf16_t* __restrict__ x, const WT* __restrict__ W,
-                                                                   const float* __restrict__ wscale, const bf16_t* res, void* outv,
+                                                                   const float* __restrict__ wscale_, const bf16_t* res, void* outv,
                                                                    int MB, int N, int K, int ldx, int ldo, int tiled, int out_f32,
                                                                    SkinnyFuse fuse) {
-    constexpr bool F8 = sizeof(WT) == 1;
+    constexpr bool MX = IsMx4<WT>::v;                    // MXFP4 (tiled only, host-checked): wscale_ is the tiled e8m0 array, no row scale
+    constexpr bool F8 = sizeof(WT) == 1 && !MX;
     constexpr bool F16 = IsF16<WT>::v;
-    constexpr int KS = F8 ? 64 : 32, CH = F8 ? 16 : 8, XL = F8 ? 2 : 1;
+    constexpr int KS = MX ? 128 : (F8 ? 64 : 32), CH = MX ? 32 : (F8 ? 16 : 8), CB = MX ? 16 : CH, XL = MX ? 4 : (F8 ? 2 : 1);
+    const float* const wscale = MX ? nullptr : wscale_;
+    const unsigned char* const e8 = reinterpret_cast<const unsigned char*>(wscale_);
     constexpr int PER = UNR * SPT;                       // steps of one wave per tile
     constexpr int WV = SK_WAVES;
     static_assert(NS % SPT == 0 && NS >= 2, "the ring holds whole tiles");
@@ -417,19 +459,27 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_stream_kernel(const bf16_t*
     }
     // ---- weight ring: set g = (tile g / SPT of this workgroup, steps (g % SPT) * UNR ..).  Sets past the end re-read the
     // activation buffer (L2-resident, always mapped) so that every load stays unconditional and costs no HBM traffic.
-    const long long pstep = tiled ? 64 * CH : KS;
-    const long long tstride = (long long)nsteps * (64 * CH);
+    // MXFP4: a dead set re-reads tile 0 of W and its exponents instead (always mapped; an arbitrary activation byte could be E = 255)
+    const long long pstep = tiled ? 64 * CB : KS;
+    const long long tstride = (long long)nsteps * (64 * CB);
     u32x4 w[NS][UNR];
+    unsigned we[NS][UNR];                                // MXFP4: the e8m0 byte of each step's block
 #define TEO_SS_LOADW(SLOT, GI)                                                                                 \
     {                                                                                                          \
         const int g_ = (GI);                                                                                   \
         const int tq = (int)blockIdx.x + (g_ / SPT) * G, ls_ = g_ % SPT;                                       \
-        const WT* wt = tiled ? W + (long long)tq * tstride + lane * CH                                         \
+        const WT* wt = tiled ? W + (long long)tq * tstride + lane * CB                                         \
                              : W + (long long)(tq * 16 + fr) * K + fg * CH;                                    \
         const bool live_ = g_ < total;                                                                         \
         _Pragma("unroll") for (int u = 0; u < UNR; ++u) {                                                      \
-            const WT* pw = wt + (long long)min(s0 + ls_ * UNR + u, nsteps - 1) * pstep;                        \
-            w[SLOT][u] = sk_ldw<true>(live_ ? pw : reinterpret_cast<const WT*>(x) + lane * CH);                \
+            const long long st_ = min(s0 + ls_ * UNR + u, nsteps - 1);                                         \
+            const WT* pw = wt + st_ * pstep;                                                                   \
+            if constexpr (MX) {                                                                                \
+                w[SLOT][u] = sk_ldw<true>(live_ ? pw : W + lane * CB);                                         \
+                we[SLOT][u] = e8[live_ ? ((long long)tq * nsteps + st_) * 64 + lane : (long long)lane];        \
+            } else {                                                                                           \
+                w[SLOT][u] = sk_ldw<true>(live_ ? pw : reinterpret_cast<const WT*>(x) + lane * CH);            \
+            }                                                                                                  \
         }                                                                                                      \
     }
 #pragma unroll
@@ -460,7 +510,11 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_stream_kernel(const bf16_t*
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 const int i = ls * UNR + u;
-                if (F8) {
+                if constexpr (MX) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        acc = mfma16<F16>(fp4x8_to_bf16x8(w[r][u][j], we[r][u]), __builtin_bit_cast(bf16x8, xr[i][j % XL]), acc);
+                } else if (F8) {
                     acc = mfma16<F16>(fp8x8_to_bf16x8(w[r][u].x, w[r][u].y),
                                                                   __builtin_bit_cast(bf16x8, xr[i][0]), acc);
                     acc = mfma16<F16>(fp8x8_to_bf16x8(w[r][u].z, w[r][u].w),
@@ -531,8 +585,10 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_stream_kernel(const bf16_t*
 #undef TEO_SK_SSQ_LOAD
 #undef TEO_SK_SSQ_REDUCE
 
-bool skinny_gemm_ok(int MB, int N, int K, int ldx, int w_fp8, unsigned flags, const void* x, const void* W) {
-    const int ks = w_fp8 ? 64 : 32;
+static inline int skinny_kstep(int wfmt) { return wfmt == SK_W_MXFP4 ? 128 : (wfmt == SK_W_FP8 ? 64 : 32); }
+
+bool skinny_gemm_ok(int MB, int N, int K, int ldx, int wfmt, unsigned flags, const void* x, const void* W) {
+    const int ks = skinny_kstep(wfmt);
     if (MB < 1 || MB > 16 || N < 1 || K < ks || K % ks != 0 || ldx % 8 != 0) return false;
     if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(W) & 15)) return false;
     if ((flags & TEO_GEMM_SWIGLU16) && N % 32 != 0) return false;
@@ -540,19 +596,30 @@ bool skinny_gemm_ok(int MB, int N, int K, int ldx, int w_fp8, unsigned flags, co
     return true;
 }
 
-// bf16 activations; W bf16 or fp8 e4m3 (+ per-row scales), row-major or TEO_GEMM_WTILED; out bf16 or f32;
-// res (bf16, may alias out) optional
+// bf16 activations; W bf16 or fp8 e4m3 (+ per-row scales), row-major or TEO_GEMM_WTILED, or MXFP4 (wfmt = SK_W_MXFP4: wscale = the
+// e8m0 bytes; TEO_GEMM_WTILED only); out bf16 or f32; res (bf16, may alias out) optional
 // norm_w != NULL: fused RMSNorm of x (see the kernel).  fuse: producer-side norm hand-off (ops.h SkinnyFuse).
-int skinny_gemm(const void* x, const void* W, const float* wscale, int w_fp8, const void* norm_w, float eps, const void* res,
+int skinny_gemm(const void* x, const void* W, const void* wscale_v, int wfmt, const void* norm_w, float eps, const void* res,
                 void* out, int MB, int N, int K, int ldx, int ldo, unsigned flags, int out_dtype, hipStream_t st, SkinnyFuse fuse) {
     const bool swiglu = (flags & (TEO_GEMM_SWIGLU16 | TEO_GEMM_SWIGLU8)) != 0;
     const int tiled = (flags & TEO_GEMM_WTILED) ? 1 : 0;
-    if (!skinny_gemm_ok(MB, N, K, ldx, w_fp8, flags, x, W)) {
-        set_error("skinny_gemm: unsupported MB=%d N=%d K=%d ldx=%d", MB, N, K, ldx);
+    const bool w_mx = wfmt == SK_W_MXFP4;
+    const int w_fp8 = wfmt == SK_W_FP8 ? 1 : 0;
+    const float* wscale = reinterpret_cast<const float*>(wscale_v);     // fp8: [N] fp32 row scales; MXFP4: the tiled e8m0 bytes
+    const int kstep = skinny_kstep(wfmt);
+    TEO_CHECK_ARG(wfmt == SK_W_16 || wfmt == SK_W_FP8 || wfmt == SK_W_MXFP4, "skinny_gemm: weight format %d", wfmt);
+    if (!skinny_gemm_ok(MB, N, K, ldx, wfmt, flags, x, W)) {
+        set_error("skinny_gemm: unsupported MB=%d N=%d K=%d ldx=%d (K must be a multiple of %d)", MB, N, K, ldx, kstep);
+        return TEO_ERR_UNSUPPORTED;
+    }
+    if (w_mx && !tiled) {
+        set_error("skinny_gemm: MXFP4 weights are read in the TEO_GEMM_WTILED layout only");
         return TEO_ERR_UNSUPPORTED;
     }
     TEO_CHECK_ARG(!w_fp8 || wscale, "skinny_gemm: fp8 weights need per-row scales");
+    TEO_CHECK_ARG(!w_mx || wscale, "skinny_gemm: MXFP4 weights need their e8m0 block exponents");
     if (out_dtype == TEO_F16 || (flags & TEO_GEMM_F16)) fuse.f16 = true;      // the runtime sets fuse.f16 itself
+    TEO_CHECK_ARG(!(fuse.f16 && w_mx), "skinny_gemm: MXFP4 weights go with bfloat16 activations");
     TEO_CHECK_ARG(!(fuse.f16 && w_fp8), "skinny_gemm: fp8 weights go with bfloat16 activations (their power-of-two row scales are exact in bf16 only)");
     TEO_CHECK_ARG(!(swiglu && res), "skinny_gemm: SWIGLU16 takes no residual");
     TEO_CHECK_ARG(!norm_w || (K <= 16384 && (reinterpret_cast<uintptr_t>(norm_w) & 15) == 0), "skinny_gemm: fused norm needs K <= 16384 and an aligned weight");
@@ -568,13 +635,14 @@ int skinny_gemm(const void* x, const void* W, const float* wscale, int w_fp8, co
     const int ldr = ldo, of = out_dtype == TEO_F32;
     // streaming form (persistent workgroups, activations in registers): K <= 4096, whole 16-row tiles, one row tile at a time
     {
-        const int nsteps = K / (w_fp8 ? 64 : 32), ntiles = N / 16;
+        const int nsteps = K / kstep, ntiles = N / 16;
         const auto al = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
         bool ok = tune().skinny_stream != 0 && !norm_w && !(flags & TEO_GEMM_SWIGLU16) && (tune().skinny_tiles == 0 || tune().skinny_tiles == 1) && N % 16 == 0 &&
-                  nsteps <= (w_fp8 ? 64 : 128) && al(x, 16);
+                  nsteps <= (w_mx ? 32 : (w_fp8 ? 64 : 128)) && al(x, 16);
         // auto: where it measures faster than one tile per workgroup -- at least two tiles per workgroup, and fp8 weights or more
         // than 8 rows (bf16 at <= 8 rows: a tie, the duplicate activation rows of the tile kernel coalesce)
-        if (ok && tune().skinny_stream == 1) ok = ntiles >= 512 && (w_fp8 || MB > 8);
+        // (MXFP4: the fp8 rule)
+        if (ok && tune().skinny_stream == 1) ok = ntiles >= 512 && (w_fp8 || w_mx || MB > 8);
         if (ok) {
             const int cus = device_cu_count();
             const int per_cu = tune().skinny_grid > 0 ? tune().skinny_grid : 1;
@@ -582,7 +650,11 @@ int skinny_gemm(const void* x, const void* W, const float* wscale, int w_fp8, co
 #define TEO_SS(WW, UN, SP, NSV, SW)                                                                         \
             TEO_KLAUNCH((skinny_stream_kernel<WW, UN, SP, NSV, SW>), grid, SK_THREADS, 0, st, (const bf16_t*)x, (const WW*)W, wscale, (const bf16_t*)res, \
                         out, MB, N, K, ldx, ldo, tiled, of, fuse)
-            if (tune().skinny_ring == 0) {
+            // MXFP4: a wave's share of a tile is 4 steps = 4 KB, half of fp8's: 4 tiles in the ring hold what 2 fp8 tiles hold
+            if (w_mx) {
+                if (tune().skinny_ring == 0) { if (sw8) TEO_SS(mx4_t, 4, 1, 4, true); else TEO_SS(mx4_t, 4, 1, 4, false); }
+                else                         { if (sw8) TEO_SS(mx4_t, 4, 1, 5, true); else TEO_SS(mx4_t, 4, 1, 5, false); }
+            } else if (tune().skinny_ring == 0) {
                 if (w_fp8)         { if (sw8) TEO_SS(fp8_t, 8, 1, 2, true); else TEO_SS(fp8_t, 8, 1, 2, false); }
                 else if (fuse.f16) { if (sw8) TEO_SS(f16_t, 8, 2, 2, true); else TEO_SS(f16_t, 8, 2, 2, false); }
                 else               { if (sw8) TEO_SS(bf16_t, 8, 2, 2, true); else TEO_SS(bf16_t, 8, 2, 2, false); }
@@ -592,7 +664,7 @@ int skinny_gemm(const void* x, const void* W, const float* wscale, int w_fp8, co
                 else               { if (sw8) TEO_SS(bf16_t, 8, 2, 4, true); else TEO_SS(bf16_t, 8, 2, 4, false); }
             }
 #undef TEO_SS
-            note_kernel("skinny_stream");
+            note_kernel(w_mx ? "skinny_stream_w4" : "skinny_stream");
             TEO_LAUNCH_CHECK("skinny_gemm (stream)");
             return TEO_OK;
         }
@@ -606,7 +678,7 @@ int skinny_gemm(const void* x, const void* W, const float* wscale, int w_fp8, co
     // 16 waves per workgroup (round 6): the launches with about one 16-row tile per CU (o, down: N = 4096 -> 256 workgroups) are bound by
     // how many weight requests a CU has in flight, not by its waves' arithmetic -- 16 K slices put twice the requests out from the first cycle
     {
-        const int steps16 = K / (w_fp8 ? 64 : 32) / 16;
+        const int steps16 = K / kstep / 16;
         const bool w16 = !swiglu && !norm_w && rt == 1 && (tune().skinny_nt != 0) && steps16 >= 2 &&
                          tune().skinny_waves == 16;
         if (w16) {
@@ -616,18 +688,21 @@ int skinny_gemm(const void* x, const void* W, const float* wscale, int w_fp8, co
             // steps per register set: two sets cover the wave's whole K slice where the registers allow (every request of the launch out at once)
             // (fp8: at most 4 -- its activation fragments are twice the weights, UNR = 6 spills 67 VGPRs under the 128-register cap of a
             // 1024-thread workgroup: tools/kernel_meta.py)
+            // (MXFP4: 2 -- its activation fragments are four times the weights)
             const int un = steps16 <= 4 ? 2 : ((steps16 <= 8 || w_fp8) ? 4 : 6);
-            if (w_fp8)         { if (un == 2) TEO_SK16(fp8_t, 2); else TEO_SK16(fp8_t, 4); }
+            if (w_mx)          { TEO_SK16(mx4_t, 2); }
+            else if (w_fp8)    { if (un == 2) TEO_SK16(fp8_t, 2); else TEO_SK16(fp8_t, 4); }
             else if (fuse.f16) { if (un == 2) TEO_SK16(f16_t, 2); else if (un == 4) TEO_SK16(f16_t, 4); else TEO_SK16(f16_t, 6); }
             else               { if (un == 2) TEO_SK16(bf16_t, 2); else if (un == 4) TEO_SK16(bf16_t, 4); else TEO_SK16(bf16_t, 6); }
 #undef TEO_SK16
-            note_kernel("skinny_gemm_w16");
+            note_kernel(w_mx ? "skinny_gemm_w16_w4" : "skinny_gemm_w16");
             TEO_LAUNCH_CHECK("skinny_gemm");
             return TEO_OK;
         }
     }
-    const int steps_per_wave = K / (w_fp8 ? 64 : 32) / (SK_WAVES / rt);
-    const bool unr8 = !swiglu && !norm_w && (tune().skinny_nt != 0) && (tune().skinny_unr == 8 || (tune().skinny_unr == 0 && steps_per_wave >= 16 && blocks <= 2 * std::max(device_cu_count(), 1)));
+    const int steps_per_wave = K / kstep / (SK_WAVES / rt);
+    // (MXFP4 has no long-set form -- 8 steps of activation fragments are 128 VGPRs per set: skinny_unr is ignored)
+    const bool unr8 = !w_mx && !swiglu && !norm_w && (tune().skinny_nt != 0) && (tune().skinny_unr == 8 || (tune().skinny_unr == 0 && steps_per_wave >= 16 && blocks <= 2 * std::max(device_cu_count(), 1)));
     if (unr8) {
         if (w_fp8) TEO_KLAUNCH((skinny_gemm_kernel<fp8_t, 6, true, false, false>), blocks, SK_THREADS, 0, st, (const fp8_t*)W, (const bf16_t*)x, MB, N, K, ldx, tiled, rt,
                                wscale, (const bf16_t*)res, (const bf16_t*)nullptr, eps, out, ldo, ldr, of, fuse, sw8);
@@ -639,19 +714,25 @@ int skinny_gemm(const void* x, const void* W, const float* wscale, int w_fp8, co
         TEO_LAUNCH_CHECK("skinny_gemm");
         return TEO_OK;
     }
-#define TEO_SK(WW, NTV, SW, NM)                                                                            \
-    TEO_KLAUNCH((skinny_gemm_kernel<WW, 4, NTV, SW, NM>), blocks, SK_THREADS, dyn, st,                     \
+#define TEO_SK(WW, NTV, SW, NM) TEO_SKU(WW, 4, NTV, SW, NM)
+#define TEO_SKU(WW, UNV, NTV, SW, NM)                                                                            \
+    TEO_KLAUNCH((skinny_gemm_kernel<WW, UNV, NTV, SW, NM>), blocks, SK_THREADS, dyn, st,                   \
         (const WW*)W, (const bf16_t*)x, MB, N, K, ldx, tiled, rt, wscale, (const bf16_t*)res, (const bf16_t*)norm_w, eps, out, ldo, ldr, \
         of, fuse, sw8)
 #define TEO_SK_N(WW, NTV, SW) if (norm_w) { TEO_SK(WW, NTV, SW, true); } else { TEO_SK(WW, NTV, SW, false); }
 #define TEO_SK_F(WW, NTV) if (swiglu) { TEO_SK_N(WW, NTV, true) } else { TEO_SK_N(WW, NTV, false) }
-    if (w_fp8)         { if ((tune().skinny_nt != 0)) { TEO_SK_F(fp8_t, true) } else { TEO_SK_F(fp8_t, false) } }
+    // MXFP4, a K slice of at most 4 steps per wave (o at K = 4096, plain / residual epilogue): two sets of 2 steps hold the whole slice --
+    // with sets of 4 the second set is four clamped duplicates, each dragging its 4 activation loads along (o: 8.7 -> see profiles/r08)
+    if (w_mx && !swiglu && !norm_w && tune().skinny_nt != 0 && steps_per_wave <= 4) { TEO_SKU(mx4_t, 2, true, false, false); }
+    else if (w_mx)     { if ((tune().skinny_nt != 0)) { TEO_SK_F(mx4_t, true) } else { TEO_SK_F(mx4_t, false) } }
+    else if (w_fp8)    { if ((tune().skinny_nt != 0)) { TEO_SK_F(fp8_t, true) } else { TEO_SK_F(fp8_t, false) } }
     else if (fuse.f16) { TEO_SK_F(f16_t, true) }              // (non-temporal weight loads only: one instantiation set for the second format)
     else               { if ((tune().skinny_nt != 0)) { TEO_SK_F(bf16_t, true) } else { TEO_SK_F(bf16_t, false) } }
 #undef TEO_SK_F
 #undef TEO_SK_N
 #undef TEO_SK
-    note_kernel("skinny_gemm");
+#undef TEO_SKU
+    note_kernel(w_mx ? "skinny_gemm_w4" : "skinny_gemm");
     TEO_LAUNCH_CHECK("skinny_gemm");
     return TEO_OK;
 }

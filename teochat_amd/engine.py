@@ -52,6 +52,32 @@ def tile_weights(W):
     return W.view(npad // 16, 16, K // ks, 4, ch).permute(0, 2, 3, 1, 4).contiguous().view(npad, K)
 
 
+def tile_weights_mxfp4(q, e):
+    """Row-major MXFP4 arrays (teo_gemv_w4's format: codes q uint8 [N, K/2], block exponents e uint8 [N, K/32]) -> (q_tiled, e_tiled), the
+    TEO_GEMM_WTILED layout of teo_gemm_skinny_w4 (include/teo_hip.h): tiles of 16 rows x 128 k = 1 KB of codes, tile (n/16, k/128) at
+    ((n/16) * (K/128) + k/128) KB, 16-byte lane ((k % 128) / 32) * 16 + n % 16 = the 16 code bytes of one MX block; 64 exponent bytes per
+    tile in the same tile order, byte = lane.  Rows past N: zero codes, E = 127.  Returns uint8 [Np, K/2] and [Np, K/32] (Np = N rounded
+    up to 16; the shapes only carry the sizes).  K % 128 != 0 raises ValueError."""
+    N, K = q.shape[0], q.shape[1] * 2
+    if q.dim() != 2 or e.dim() != 2 or K % 128 or tuple(e.shape) != (N, K // 32):
+        raise ValueError(f"tile_weights_mxfp4: K must be a multiple of 128 and e [N, K/32]; got q {tuple(q.shape)}, e {tuple(e.shape)}")
+    npad = (N + 15) // 16 * 16
+    if npad != N:
+        q = torch.cat([q, torch.zeros(npad - N, K // 2, dtype=q.dtype, device=q.device)])
+        e = torch.cat([e, torch.full((npad - N, K // 32), 127, dtype=e.dtype, device=e.device)])
+    qt = q.view(npad // 16, 16, K // 128, 4, 16).permute(0, 2, 3, 1, 4).contiguous().view(npad, K // 2)
+    et = e.view(npad // 16, 16, K // 128, 4).permute(0, 2, 3, 1).contiguous().view(npad, K // 32)
+    return qt, et
+
+
+def untile_weights_mxfp4(qt, et, N):
+    """Inverse of tile_weights_mxfp4: the first N rows of the row-major arrays."""
+    npad, K = qt.shape[0], qt.shape[1] * 2
+    q = qt.view(npad // 16, K // 128, 4, 16, 16).permute(0, 3, 1, 2, 4).contiguous().view(npad, K // 2)
+    e = et.view(npad // 16, K // 128, 4, 16).permute(0, 3, 1, 2).contiguous().view(npad, K // 32)
+    return q[:N].contiguous(), e[:N].contiguous()
+
+
 def reinterleave_gate_up(gu, block):
     """gate/up rows interleaved in blocks of 16 (the engine's layout) -> blocks of `block` rows (same pairs)."""
     n, k = gu.shape
@@ -313,6 +339,7 @@ class TeoEngine:
             self.lm_head, self.lm_head8, self.lm_head_s = dq, q, s
             self.llama_w8 = (w8, s8)
         self.llama_w4 = None
+        self.batch_mxfp4 = False                  # set_options(batch_mxfp4=True): the batched step streams tiled MXFP4 copies too
         if self.weight_format == "mxfp4":
             # the same for the single-conversation decode step in MXFP4 (blocks of 32 along K); lm_head stays 16-bit, and prefill, the
             # tower and the batched step read the bf16 tensors, replaced by the exact dequantisation
@@ -630,11 +657,21 @@ class TeoEngine:
             L.check(self.lib.teo_llama_decode_begin(C.byref(self.llama_desc), C.byref(self.decode_state), _p(ws), ws.numel(),
                                                     st), "teo_llama_decode_begin")
 
-    def set_options(self, prefill_fp8=None, rope_in_attn=None):
+    def set_options(self, prefill_fp8=None, rope_in_attn=None, batch_mxfp4=None):
         """Per-engine options of the LLaMA descriptor (include/teo_hip.h teo_llama_desc): `prefill_fp8` = w8a8 prefill on the fp8
         MFMA (lossy, needs weight_format='fp8'), `rope_in_attn` = RoPE + KV append inside the decode attention kernel instead of
-        the QKV GEMV epilogue (same values).  Not process-global: two engines in one process can differ."""
+        the QKV GEMV epilogue (same values).  Not process-global: two engines in one process can differ.
+        `batch_mxfp4` (default False; needs weight_format='mxfp4'): the BATCHED decode step streams tiled MXFP4 copies of qkv / o /
+        gateup / down (teo_decode_batch_state.w_mxfp4) instead of 16-bit tiled copies of the dequantised weights -- the same weights,
+        another fp32 order of the sums.  A BatchDecoder reads it when it is built (model.batch_decoder() rebuilds its cached one)."""
         d = self.llama_desc
+        if batch_mxfp4 is not None:
+            if batch_mxfp4 and self.llama_w4 is None:
+                raise ValueError("batch_mxfp4 needs weight_format='mxfp4' (the MXFP4 weight copies)")
+            if bool(batch_mxfp4) != self.batch_mxfp4:
+                self.batch_mxfp4 = bool(batch_mxfp4)
+                for hook in self._tune_hooks:     # a captured batched step belongs to the decoder built under the old setting
+                    hook()
         if prefill_fp8 is not None:
             if prefill_fp8 and self.llama_w8 is None:
                 raise ValueError("prefill_fp8 needs weight_format='fp8' (the e4m3 weight copies)")

@@ -607,7 +607,7 @@ class LlavaLlamaForCausalLM:
     def batch_decoder(self, batch, max_new=1024):
         from .batch import BatchDecoder
         cur = getattr(self, "_batch_decoder", None)
-        if cur is None or cur.B != batch or cur.max_new < max_new:
+        if cur is None or cur.B != batch or cur.max_new < max_new or cur.w4_requested != bool(getattr(self.engine, "batch_mxfp4", False)):
             self._batch_decoder = None          # free the old caches first
             cur = BatchDecoder(self.engine, batch, max_new=max(max_new, 64))
             self._batch_decoder = cur
