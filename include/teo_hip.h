@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define TEO_ABI_VERSION 4 /* 4: MXFP4 weights in the batched decode step (teo_gemm_skinny_w4, teo_decode_batch_state.w_mxfp4); 3: MXFP4 decode weights (teo_llama_desc *_w4 / *_e4, teo_gemv_w4); 2: teo_tune blocks, `tune` last in the descriptors, teo_sizeof */
+#define TEO_ABI_VERSION 4 /* 4 (additive, same number: teo_gemm_w4, teo_gemm_w4_plan, teo_llama_desc.prefill_w4 in front of `tune` -- the load-time teo_sizeof check, not this number, refuses a binding older than the library); 4: MXFP4 weights in the batched decode step (teo_gemm_skinny_w4, teo_decode_batch_state.w_mxfp4); 3: MXFP4 decode weights (teo_llama_desc *_w4 / *_e4, teo_gemv_w4); 2: teo_tune blocks, `tune` last in the descriptors, teo_sizeof */
 
 typedef void* teo_stream_t; /* hipStream_t */
 
@@ -52,7 +52,7 @@ const char* teo_last_error(void);
 /* Diagnostics: which kernel family the most recent teo_gemm* / teo_attention call of this thread dispatched to
  * ("gemm_simple", "gemm_mfma_128", "gemm_mfma_128_sk", "gemm_wide", "gemm_wide_sk", "gemm_big", "gemm_big_hybrid", "gemm_fp8_*",
  * "gemm_big_hybrid_cohort", "gemm_narrow_64", "gemm_narrow_128", "gemm_narrow_128w8", "gemm_pipe_64x64", "gemm_pipe_64", "gemm_pipe_64_r4", "gemm_pipe_128x96",
- * "gemm_pipe_128", "gemm_quad_160", "gemm_quad_160_w4", "attn_flash32", "attn_simple").  Lets the parity tests state which production kernel they checked. */
+ * "gemm_pipe_128", "gemm_quad_160", "gemm_quad_160_w4", "gemm_w4_64", "gemm_w4_128", "gemm_w4_256", "gemm_w4_256x160", "attn_flash32", "attn_simple").  Lets the parity tests state which production kernel they checked. */
 const char* teo_last_kernel(void);
 /* The family name teo_gemm_ws / teo_gemm_fp8_ws would note for this problem under the calling thread's tune block, on a device of
  * cu_count CUs, with (with_ws = 1) or without a stream-K workspace; nothing is launched.  Dense operands (lda = K, ldc = N, or N / 2
@@ -60,6 +60,9 @@ const char* teo_last_kernel(void);
  * for a shape the w8a8 kernels do not take. */
 const char* teo_gemm_plan(int M, int N, int K, unsigned flags, int act, int dtype, int out_dtype, int with_ws, int cu_count);
 const char* teo_gemm_fp8_plan(int M, int N, int K, unsigned flags, int out_dtype, int with_ws, int cu_count);
+/* The same for teo_gemm_w4 ("gemm_w4_64", "gemm_w4_128", "gemm_w4_256x160", "gemm_w4_256"; "" for a shape it does not take).  The tile
+ * follows from M, N, the flags and the CU count alone: no teo_tune key applies to this family and it uses no workspace. */
+const char* teo_gemm_w4_plan(int M, int N, int K, unsigned flags, int out_dtype, int cu_count);
 /* Size of a struct of this header as the LIBRARY was built with it (0 for an unknown name): a binding checks its own layout against it
  * at load time -- "teo_vit_desc", "teo_proj_desc", "teo_llama_desc", "teo_decode_state", "teo_decode_batch_state", "teo_attn_args". */
 size_t teo_sizeof(const char* struct_name);
@@ -346,6 +349,19 @@ int teo_gemm_skinny(const void* d_x, const void* d_W, const float* d_w_scale, in
 int teo_gemm_skinny_w4(const void* d_x, const void* d_W4, const void* d_e8m0, const void* d_norm_w, float eps, const void* d_residual,
                        void* d_out, int MB, int N, int K, int ldx, int ldo, unsigned flags, int out_dtype, teo_stream_t stream);
 
+/* Prefill GEMM on MXFP4 weights: C[M, N] = A[M, K] . W[N, K]^T (+ residual[M, N]), W in teo_gemv_w4's ROW-MAJOR format (d_W4 [N, K/2] code
+ * bytes, d_e8m0 [N, K/32] bytes; not the tiled layout of teo_gemm_skinny_w4).  A, residual bf16 (residual may alias C), C bf16 or f32,
+ * lda / ldc as teo_gemm; flags: TEO_GEMM_SWIGLU16 as in teo_gemm (C [M, N/2]); no bias, no activation.
+ * Every code is converted exactly to the bfloat16 it stands for and fed to the k-ascending v_mfma_f32_16x16x32_bf16 chain of the bf16
+ * tile families, through their LDS image and their epilogue: the result is BIT-IDENTICAL to teo_gemm / teo_gemm_ws on the dequantised
+ * bf16 matrix, for every M >= 1 and every tile this family picks.
+ * Supported when the bf16 call of the same shape runs on the MFMA (K % 64 == 0, lda % 8 == 0, ldc % 4 == 0, N % 4 == 0 -- % 32 with
+ * SWIGLU16 --, 16-byte aligned A / W4 / C) and K % 128 == 0; otherwise TEO_ERR_UNSUPPORTED (there is no VALU fallback).
+ * TEO_GEMM_F16 / a TEO_F16 output: TEO_ERR_ARG (MXFP4 weights go with bfloat16).  Exponent bytes: 1 .. 254 as teo_gemv_w4 (0 and 255 are
+ * not supported: the scale is formed as the float with that exponent field, 0 would give 0 and 255 infinity; not checked). */
+int teo_gemm_w4(const void* d_A, const void* d_W4, const void* d_e8m0, const void* d_residual, void* d_C, int M, int N, int K, int lda,
+                int ldc, unsigned flags, int out_dtype, teo_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Composed runtime entry points (the layer loops live in C++, not Python)
  * ------------------------------------------------------------------------------------------- */
@@ -417,15 +433,17 @@ typedef struct {
     const void* const* gateup_w8; const float* const* gateup_s;
     const void* const* down_w8;   const float* const* down_s;
     const void* lm_head8;         const float* lm_head_s;
-    /* Optional MXFP4 copies for the DECODE steps.  The dequantised weights are exact bfloat16 numbers: prefill and the tower keep
-     * reading the 16-bit weights above, which a caller sets to the dequantised values; lm_head stays 16-bit.
+    /* Optional MXFP4 copies of the four layer matrices.  The dequantised weights are exact bfloat16 numbers, so a caller that also
+     * keeps 16-bit matrices sets those to the dequantised values and every path sees the same weights; lm_head stays 16-bit.
      *  - teo_llama_decode_step (and its graph / profile forms) streams these when qkv_w4 is set: teo_gemv_w4's row-major format
      *    ([N, K/2] code bytes, [N, K/32] e8m0 bytes), same row layouts as above (gate/up interleaved-16).  All eight or none; bf16
      *    only; a descriptor holding both *_w8 and *_w4 copies is TEO_ERR_ARG.
      *  - teo_llama_decode_batch_step (and _begin / _step_profile / _graph_create) reads them only when teo_decode_batch_state.w_mxfp4
      *    is 1, and then in teo_gemm_skinny_w4's TILED layout (a batched-step descriptor is a copy of the prefill descriptor with these
      *    eight arrays replaced); with w_mxfp4 = 0 it ignores them and streams the 16-bit / fp8 matrices.
-     *  - the prefill entry points ignore them.
+     *  - teo_llama_prefill, teo_llama_prefill_attentions and teo_llama_prefill_batch read them only when prefill_w4 is 1 (below), in
+     *    the ROW-MAJOR format of the single decode step -- never hand a descriptor whose arrays are tiled to a prefill entry with
+     *    prefill_w4 = 1: the entry cannot tell the layouts apart.  With prefill_w4 = 0 they ignore them.
      * All NULL -> no MXFP4 anywhere. */
     const void* const* qkv_w4;    const uint8_t* const* qkv_e4;
     const void* const* o_w4;      const uint8_t* const* o_e4;
@@ -434,6 +452,14 @@ typedef struct {
     /* Per-engine options (they select a path or change results, so they live here and not in teo_tune_set): */
     int prefill_fp8;   /* 1: prefill Linear layers as w8a8 on the fp8 MFMA (activations quantised per token; needs the *_w8 copies,
                         *    bf16).  Lossy beyond the weight quantisation: selectable, never a default.  0: bf16 / f32 GEMMs */
+    int prefill_w4;    /* 1: the four Linear layers of every prefill entry point run teo_gemm_w4 on the row-major *_w4 / *_e4 arrays --
+                        *    bit-identical to the bf16 GEMMs on the dequantised matrices (RMSNorm, RoPE / KV append, attention, lm_head
+                        *    and the hidden-state snapshots are unchanged).  qkv_w / o_w / gateup_w / down_w are then never read and may
+                        *    be NULL: an engine can hold 4-bit layer weights only.  Needs all eight arrays, bf16, no *_w8 copies and
+                        *    prefill_fp8 = 0 (else TEO_ERR_ARG); hidden, heads * head_dim and inter multiples of 128 (else
+                        *    TEO_ERR_UNSUPPORTED); checked before anything is written.  0 (default): prefill reads the 16-bit matrices.
+                        *    With NULL 16-bit layer pointers the other paths refuse instead of reading them: prefill with
+                        *    prefill_w4 = 0, and the batched decode step with w_mxfp4 = 0 and no *_w8 copies, return TEO_ERR_ARG */
     int rope_in_attn;  /* single-conversation decode step: 0 = RoPE + KV append in the QKV GEMV epilogue (default), 1 = inside the
                         *    decode attention kernel (same values; the batched step always uses 1) */
     const teo_tune* tune; /* performance knobs of this engine (as teo_vit_desc.tune); a captured decode graph keeps the choices made at capture */

@@ -16,7 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .engine import _p, reinterleave_gate_up, tile_weights, tile_weights_mxfp4
+from .engine import _p, dequantize_mxfp4_blocks, reinterleave_gate_up, tile_weights, tile_weights_mxfp4
 
 
 class BatchDecoder:
@@ -45,6 +45,7 @@ class BatchDecoder:
             self.slot_desc.append(d)
         # batched-step descriptor: slot 0's caches + (optionally) operand-tiled weights
         d = L.LlamaDesc.from_buffer_copy(self.slot_desc[0])
+        d.prefill_w4 = 0                          # its *_w4 arrays become TILED below: never a prefill descriptor
         fp8 = engine.llama_w8 is not None
         ks = 64 if fp8 else 32
         self.tiled = bool(tiled) and dt in (torch.bfloat16, torch.float16) and c.hidden_size % ks == 0 and c.intermediate_size % ks == 0 \
@@ -76,6 +77,24 @@ class BatchDecoder:
             d.gateup_w4, d.gateup_e4 = self._arr(tq["gateup"]), self._arr(te["gateup"])
             d.down_w4, d.down_e4 = self._arr(tq["down"]), self._arr(te["down"])
             d.lm_head = head.data_ptr()
+        elif getattr(engine, "mxfp4_only", False):
+            # an mxfp4_only engine has no 16-bit layer matrices and this decoder cannot take the tiled 4-bit step (tiled=False): it owns
+            # 16-bit copies rebuilt from the codes (exactly the dequantised weights), tiled when the 16-bit step is
+            q4, e4 = engine.llama_w4
+            self.block8 = self.tiled and c.intermediate_size % 16 == 0
+            tw = {}
+            for k in ("qkv", "o", "gateup", "down"):
+                tw[k] = []
+                for q, e in zip(q4[k], e4[k]):
+                    w = dequantize_mxfp4_blocks(q, e)
+                    if self.tiled:
+                        w = tile_weights(reinterleave_gate_up(w, 8) if (k == "gateup" and self.block8) else w)
+                    tw[k].append(w)
+            head = tile_weights(engine.lm_head) if self.tiled else engine.lm_head
+            self.tiled_w = (tw, head)
+            d.qkv_w, d.o_w = self._arr(tw["qkv"]), self._arr(tw["o"])
+            d.gateup_w, d.down_w = self._arr(tw["gateup"]), self._arr(tw["down"])
+            d.lm_head = head.data_ptr()
         elif self.tiled:
             src = engine.llama_w8[0] if fp8 else engine.llama_w
             # gate/up: pairs re-interleaved in blocks of 8 rows so a gate row and its up row share one 16-row tile
@@ -105,6 +124,8 @@ class BatchDecoder:
             if o is not None:
                 for dd in o.slot_desc + [o.desc]:
                     dd.prefill_fp8, dd.rope_in_attn = src.prefill_fp8, src.rope_in_attn
+                for dd in o.slot_desc:            # row-major *_w4 arrays; the step descriptor's are tiled and keep prefill_w4 = 0
+                    dd.prefill_w4 = src.prefill_w4
         engine._option_hooks.append(_sync_options)
 
         def _knob_changed():                      # TeoEngine.tune_set: the captured batched step keeps the choices of its capture

@@ -310,12 +310,14 @@ def load_generation_config(model, model_dir):
 
 def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, load_4bit=False, device_map="auto",
                           device="cuda", cache_dir=None, dtype=None, max_seq=None, seed=2, weight_format=None,
-                          batch_mxfp4=False):
+                          batch_mxfp4=False, mxfp4_only=False):
     """dtype None = the reference's choice where it has one: a real checkpoint runs in torch.float16 (builder.py:105 passes
     torch_dtype=torch.float16 whatever the file holds; eval/inference.py:53 casts the frames to match) -- unless fp8 or MXFP4 decode weights
     are requested (weight_format="fp8" / "mxfp4"), which go with bfloat16 -- and the synthetic presets in torch.bfloat16 (BASELINE.json's
     headline dtype).  load_4bit (bitsandbytes NF4 in the reference) is not rerouted to MXFP4.  batch_mxfp4=True (with weight_format="mxfp4"):
-    the batched decode step streams MXFP4 weights too (TeoEngine.set_options)."""
+    the batched decode step streams MXFP4 weights too (TeoEngine.set_options).  mxfp4_only=True (with weight_format="mxfp4"): the engine keeps
+    NO 16-bit copies of qkv / o / gate-up / down -- prefill runs on teo_gemm_w4 (bit-identical to the bf16 prefill on the dequantised weights),
+    the batched step on the tiled 4-bit copies; both options are then on for good."""
     if device in (None, "cuda"):
         device = "cuda:0"
     if dtype is None:
@@ -351,7 +353,7 @@ def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, l
             tokenizer = AutoTokenizer.from_pretrained(tok_dir, use_fast=False)
         else:
             tokenizer = ByteTokenizer()
-    engine = TeoEngine(sd, cfg, dtype=dtype, device=device, max_seq=max_seq, weight_format=weight_format)
+    engine = TeoEngine(sd, cfg, dtype=dtype, device=device, max_seq=max_seq, weight_format=weight_format, mxfp4_only=mxfp4_only)
     del sd
     if batch_mxfp4:
         engine.set_options(batch_mxfp4=True)      # ValueError unless weight_format="mxfp4"

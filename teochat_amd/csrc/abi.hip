@@ -108,6 +108,11 @@ const char* teo_gemm_fp8_plan(int M, int N, int K, unsigned flags, int out_dtype
     const bool ok = teo::gemm_fp8_ok(M, N, K, K, ldc, flags, nullptr, nullptr, nullptr, nullptr);
     return teo::plan_gemm_fp8({M, N, K, K, ldc, TEO_ACT_NONE, flags, TEO_F32, out_dtype, ok}, teo::tune(), cu_count, with_ws != 0).name;
 }
+const char* teo_gemm_w4_plan(int M, int N, int K, unsigned flags, int out_dtype, int cu_count) {
+    const int ldc = (flags & TEO_GEMM_SWIGLU16) ? N / 2 : N;
+    const bool ok = (out_dtype == TEO_BF16 || out_dtype == TEO_F32) && teo::gemm_w4_ok(M, N, K, K, ldc, flags, nullptr, nullptr, nullptr, nullptr);
+    return teo::plan_gemm_w4({M, N, K, K, ldc, TEO_ACT_NONE, flags, TEO_BF16, out_dtype, ok}, teo::tune(), cu_count).name;
+}
 
 teo_tune* teo_tune_create(void) { return new (std::nothrow) teo_tune(); }
 int teo_tune_destroy(teo_tune* t) {
@@ -209,6 +214,17 @@ int teo_gemm_fp8_ws(const void* A8, const float* a_scale, const void* W8, const 
     TEO_CHECK_ARG(ws == nullptr || (reinterpret_cast<uintptr_t>(ws) & 255) == 0, "teo_gemm_fp8_ws: workspace must be 256-byte aligned");
     if (M && N) { NEED(A8, "A8"); NEED(a_scale, "a_scale"); NEED(W8, "W8"); NEED(w_scale, "w_scale"); NEED(C, "C"); }
     return gemm_fp8(A8, a_scale, W8, w_scale, res, C, M, N, K, lda, ldc, flags, out_dtype, ST(s), ws);
+}
+int teo_gemm_w4(const void* A, const void* W4, const void* e8m0, const void* res, void* C, int M, int N, int K, int lda, int ldc,
+                unsigned flags, int out_dtype, teo_stream_t s) {
+    ENTER();
+    TEO_CHECK_ARG(M >= 0 && N >= 0 && K > 0 && lda >= K, "teo_gemm_w4: M %d N %d K %d lda %d", M, N, K, lda);
+    TEO_CHECK_ARG(ldc >= ((flags & TEO_GEMM_SWIGLU16) ? N / 2 : N), "teo_gemm_w4: ldc %d too small", ldc);
+    TEO_CHECK_ARG(out_dtype == TEO_BF16 || out_dtype == TEO_F32, "teo_gemm_w4: out_dtype %d (bf16 activations: bf16 or f32 out)", out_dtype);
+    TEO_CHECK_ARG(!(flags & TEO_GEMM_F16), "teo_gemm_w4: MXFP4 weights go with bfloat16 activations");
+    if (M == 0 || N == 0) return TEO_OK;
+    NEED(A, "A"); NEED(W4, "W4"); NEED(e8m0, "e8m0"); NEED(C, "C");
+    return gemm_w4(A, W4, e8m0, res, C, M, N, K, lda, ldc, flags, out_dtype, ST(s));
 }
 int teo_quant_rows_fp8(const void* x, const void* norm_w, void* q, float* scale, int rows, int K, int ldx, float eps, teo_stream_t s) {
     ENTER();
@@ -377,6 +393,27 @@ int teo_projector(const teo_proj_desc* d, const void* x, int rows, void* y, void
     return projector(d, x, rows, y, ws, wsb, ST(s));
 }
 
+// teo_llama_desc.prefill_w4 and the 16-bit layer pointers it makes optional: argument checks of every prefill entry, before any launch
+static int check_prefill_weights(const teo_llama_desc* d) {
+    if (!d->prefill_w4) {
+        TEO_CHECK_ARG(d->qkv_w && d->o_w && d->gateup_w && d->down_w,
+                      "prefill: the 16-bit qkv / o / gateup / down matrices are missing (a 4-bit-only descriptor needs prefill_w4 = 1)");
+        return TEO_OK;
+    }
+    TEO_CHECK_ARG(d->qkv_w4 && d->qkv_e4 && d->o_w4 && d->o_e4 && d->gateup_w4 && d->gateup_e4 && d->down_w4 && d->down_e4,
+                  "prefill: prefill_w4 needs all of qkv/o/gateup/down _w4 and _e4");
+    TEO_CHECK_ARG(!d->qkv_w8 && !d->o_w8 && !d->gateup_w8 && !d->down_w8 && !d->lm_head8,
+                  "prefill: a descriptor carries fp8 (w8) or MXFP4 (w4) weights, not both");
+    TEO_CHECK_ARG(d->dtype == TEO_BF16, "prefill: prefill_w4 needs bf16 activations");
+    TEO_CHECK_ARG(!d->prefill_fp8, "prefill: prefill_w4 and prefill_fp8 exclude each other");
+    if (d->hidden % 128 != 0 || d->inter % 128 != 0 || (d->heads * d->head_dim) % 128 != 0) {
+        set_error("prefill: prefill_w4 needs hidden %d, heads * head_dim %d and inter %d to be multiples of 128", d->hidden,
+                  d->heads * d->head_dim, d->inter);
+        return TEO_ERR_UNSUPPORTED;
+    }
+    return TEO_OK;
+}
+
 size_t teo_llama_prefill_workspace_bytes(const teo_llama_desc* d, int S) { return d ? llama_prefill_workspace_bytes(d, S) : 0; }
 int teo_llama_prefill(const teo_llama_desc* d, const void* emb, const int* pos, int S, int past, int last_only,
                       float* logits, void* ws, size_t wsb, teo_stream_t s, void* hidden_states) {
@@ -385,6 +422,7 @@ int teo_llama_prefill(const teo_llama_desc* d, const void* emb, const int* pos, 
     TuneScope tune_scope(d->tune);
     TEO_CHECK_ARG(S >= 0 && past >= 0, "teo_llama_prefill: S %d past %d", S, past);
     if (S) { NEED(emb, "embeds"); NEED(logits, "logits"); NEED(ws, "workspace"); }
+    { const int rc = check_prefill_weights(d); if (rc != TEO_OK) return rc; }
     return llama_prefill(d, emb, pos, S, past, last_only, logits, ws, wsb, ST(s), hidden_states, nullptr);
 }
 
@@ -395,6 +433,7 @@ int teo_llama_prefill_attentions(const teo_llama_desc* d, const void* emb, const
     TuneScope tune_scope(d->tune);
     TEO_CHECK_ARG(S >= 0 && past >= 0, "teo_llama_prefill_attentions: S %d past %d", S, past);
     if (S) { NEED(emb, "embeds"); NEED(logits, "logits"); NEED(ws, "workspace"); }
+    { const int rc = check_prefill_weights(d); if (rc != TEO_OK) return rc; }
     return llama_prefill(d, emb, pos, S, past, last_only, logits, ws, wsb, ST(s), hidden_states, attentions);
 }
 
@@ -406,6 +445,7 @@ int teo_llama_prefill_batch(const teo_llama_desc* d, const void* emb, const int*
     TEO_CHECK_ARG(nseq >= 0 && (nseq <= 1 || cache_stride > 0), "teo_llama_prefill_batch: nseq %d cache_stride %lld", nseq, cache_stride);
     if (nseq == 0) return TEO_OK;
     NEED(emb, "embeds"); NEED(logits, "logits"); NEED(ws, "workspace");
+    { const int rc = check_prefill_weights(d); if (rc != TEO_OK) return rc; }
     return llama_prefill_batch(d, emb, seq_lens, nseq, cache_stride, last_only, logits, ws, wsb, ST(s), hidden_states);
 }
 
@@ -491,6 +531,10 @@ static int check_batch_state(const teo_llama_desc* d, const teo_decode_batch_sta
             return TEO_ERR_UNSUPPORTED;
         }
     }
+    // a 4-bit-only descriptor (NULL 16-bit layer matrices, teo_llama_desc.prefill_w4) cannot run the 16-bit step
+    if (!st->w_mxfp4 && !d->qkv_w8)
+        TEO_CHECK_ARG(d->qkv_w && d->o_w && d->gateup_w && d->down_w,
+                      "decode batch: the 16-bit qkv / o / gateup / down matrices are missing (a 4-bit-only descriptor needs w_mxfp4 = 1)");
     return TEO_OK;
 }
 

@@ -17,6 +17,7 @@
 //   narrow 128      128 x 128       auto, what no other family took (no SwiGLU)
 //   plain           gemm_mfma_64 / gemm_mfma_128   the rest (the register-staged kernel: the SwiGLU epilogue, forced gemm_bm)
 // w8a8 (plan_gemm_fp8): fp8 big (256 x 256) -> fp8 wide stream-K -> fp8 wide (128 x 256) -> fp8 128 x 128.
+// MXFP4 weights (plan_gemm_w4): gemm_w4_64 -> gemm_w4_128 -> gemm_w4_256x160 -> gemm_w4_256, from the problem alone (no knob, no workspace).
 // The stream-K and hybrid forms need a workspace and a 256-CU device (their grids are sized for it).
 #include "common.h"
 #include <algorithm>
@@ -297,6 +298,30 @@ GemmPlan plan_gemm_fp8(const GemmProblem& p, const teo_tune& t, int cu_count, bo
     if (K >= 2 * F8_BK && (t.gemm_fp8_wide >= 2 || (t.gemm_fp8_wide == 1 && wide < plain && (t_wide >= 256 || (t_wide >= 144 && t_plain > 256)))))
         return named(g, GemmFamily::Fp8Wide, "gemm_fp8_wide");
     return named(g, GemmFamily::Fp8, "gemm_fp8_128");
+}
+
+// The MXFP4 prefill GEMM (gemm_w4.hip).  Its tiles are 2-stage rings of (bm + tn) x 128 bytes: 64 x 64 and 128 x 128 run two and more
+// four-wave workgroups per CU, the 256-row tiles one eight-wave workgroup.  The rules, in order:
+//   64 x 64      a short turn (M <= 64), or at most two of them per CU: the launch is bound by W's stream, many small tiles spread it
+//   128 x 128    at most one round of them at two per CU (qkv / o / down of config C2, M = 638)
+//   256 x 160    no SwiGLU, one round of them at one per CU where 128 x 128 tiles need more than a round (o / down at M = 2056 .. 2304:
+//                9 x 26 = 234 tiles -- the shape gemm_quad.hip's tile was made for)
+//   256 x 128    everything else: each weight is converted once per 256 rows (qkv, gate/up at config C3)
+// No teo_tune key selects among them (the header says so): tests reach every family through M.
+GemmPlan plan_gemm_w4(const GemmProblem& p, const teo_tune&, int cu_count) {
+    const int M = p.M, N = p.N;
+    const bool swiglu = p.flags & TEO_GEMM_SWIGLU16;
+    GemmPlan g;
+    if (!p.aligned) return named(g, GemmFamily::Invalid, "");
+    const long long cus = cu_count > 0 ? cu_count : 256;
+    const auto tile = [&](int bm, int tn, const char* name) {
+        g.bm = bm, g.tn = tn, g.stages = 2;
+        return named(g, GemmFamily::W4, name);
+    };
+    if (M <= 64 || (long long)cdiv(M, 64) * cdiv(N, 64) <= 2 * cus) return tile(64, 64, "gemm_w4_64");
+    if ((long long)cdiv(M, 128) * cdiv(N, 128) <= 2 * cus) return tile(128, 128, "gemm_w4_128");
+    if (!swiglu && (long long)cdiv(M, 256) * cdiv(N, 160) <= cus) return tile(256, 160, "gemm_w4_256x160");
+    return tile(256, 128, "gemm_w4_256");
 }
 
 }  // namespace teo

@@ -190,6 +190,22 @@ static int prefill_layer_fp8(const teo_llama_desc* d, const PrefillWs& w, int l,
     return gemm_fp8(w.q8, w.qs, d->down_w8[l], d->down_s[l], w.h, w.h, S, D, Fi, Fi, D, 0, dt, st, w.sk);
 }
 
+// one decoder layer's four Linear layers on the MXFP4 prefill GEMM (gemm_w4.hip; the descriptor's `prefill_w4` option, checked by the C
+// entry points): the row-major *_w4 / *_e4 arrays, the bits of the bf16 GEMMs on the dequantised matrices.  The 16-bit pointers are not read
+template <typename F>
+static int prefill_layer_w4(const teo_llama_desc* d, const PrefillWs& w, int l, int S, F attend, hipStream_t st) {
+    const int dt = d->dtype;
+    const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim, Fi = d->inter;
+    const int QKV = (H + 2 * Hk) * hd;
+    TEO_TRY(rmsnorm(w.h, d->in_norm_w[l], w.n, S, D, d->eps, dt, st));
+    TEO_TRY(gemm_w4(w.n, d->qkv_w4[l], d->qkv_e4[l], nullptr, w.qkv, S, QKV, D, D, QKV, 0, dt, st));
+    TEO_TRY(attend());
+    TEO_TRY(gemm_w4(w.attn, d->o_w4[l], d->o_e4[l], w.h, w.h, S, D, H * hd, H * hd, D, 0, dt, st));
+    TEO_TRY(rmsnorm(w.h, d->post_norm_w[l], w.n, S, D, d->eps, dt, st));
+    TEO_TRY(gemm_w4(w.n, d->gateup_w4[l], d->gateup_e4[l], nullptr, w.act, S, 2 * Fi, D, D, Fi, TEO_GEMM_SWIGLU16, dt, st));
+    return gemm_w4(w.act, d->down_w4[l], d->down_e4[l], w.h, w.h, S, D, Fi, Fi, D, 0, dt, st);
+}
+
 size_t llama_prefill_workspace_bytes(const teo_llama_desc* d, int S) { return prefill_carve(d, S, nullptr, 0).total; }
 // sticky hand-off error word of the GEMM workspace inside a prefill / tower workspace (0 = fine); synchronises the stream
 int llama_prefill_workspace_status(const teo_llama_desc* d, int S, void* ws, size_t ws_bytes, int* host_flag, hipStream_t st) {
@@ -253,6 +269,10 @@ int llama_prefill(const teo_llama_desc* d, const void* embeds, const int* positi
         };
         if (fp8) {
             TEO_TRY(prefill_layer_fp8(d, w, l, S, attend, st));
+            continue;
+        }
+        if (d->prefill_w4) {
+            TEO_TRY(prefill_layer_w4(d, w, l, S, attend, st));
             continue;
         }
         TEO_TRY(rmsnorm(w.h, d->in_norm_w[l], w.n, S, D, d->eps, dt, st));
@@ -329,6 +349,10 @@ int llama_prefill_batch(const teo_llama_desc* d, const void* embeds, const int* 
         };
         if (fp8) {
             TEO_TRY(prefill_layer_fp8(d, w, l, S, attend, st));
+            continue;
+        }
+        if (d->prefill_w4) {
+            TEO_TRY(prefill_layer_w4(d, w, l, S, attend, st));
             continue;
         }
         TEO_TRY(rmsnorm(w.h, d->in_norm_w[l], w.n, S, D, d->eps, dt, st));

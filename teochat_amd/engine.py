@@ -163,13 +163,43 @@ def quantize_mxfp4_blocks(w):
     val = torch.where(take1[..., None], d1, d0)
     ex = torch.where(take1, e1, e0)
     code = torch.where(nz[..., None], code, torch.zeros_like(code))
-    val = torch.where(nz[..., None], val, torch.zeros_like(val))
+    val = torch.where(nz[..., None], val, torch.zeros_like(val)) + 0.0      # (+ 0.0: a small negative weight that rounded to code 0 is +0,
+                                                                            #  what every kernel computes from the code, not -0)
     e = torch.where(nz, ex + 127, torch.full_like(ex, 127)).to(torch.uint8)
     code = code | ((v < 0) & (code > 0)).to(torch.uint8) << 3
     code = code.reshape(N, K)
     q = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
     dq = val.reshape(N, K).to(torch.bfloat16).contiguous()
     return q, e.contiguous(), dq
+
+
+def dequantize_mxfp4_blocks(q, e):
+    """Exact inverse of quantize_mxfp4_blocks' `dq`: codes q uint8 [N, K/2] and block exponents e uint8 [N, K/32] (teo_gemv_w4's row-major
+    format) -> bf16 [N, K] = e2m1(code) * 2^(e - 127), every value an exact bfloat16 (the bits v_cvt_scalef32_pk_bf16_fp4 produces).
+    Load-time torch like the quantiser: for code that needs a 16-bit matrix of an `mxfp4_only` engine for a moment."""
+    if q.dim() != 2 or e.dim() != 2 or (q.shape[1] * 2) % 32 != 0 or tuple(e.shape) != (q.shape[0], q.shape[1] * 2 // 32):
+        raise ValueError(f"dequantize_mxfp4_blocks: q [N, K/2] and e [N, K/32] with K % 32 == 0; got q {tuple(q.shape)}, e {tuple(e.shape)}")
+    N, K = q.shape[0], q.shape[1] * 2
+    code = torch.stack((q & 0xF, q >> 4), dim=2).reshape(N, K).long()
+    grid = torch.tensor(E2M1_GRID + tuple(-g for g in E2M1_GRID), dtype=torch.float32, device=q.device)
+    ex = (e.to(torch.int32) - 127).repeat_interleave(32, dim=1)
+    return torch.ldexp(grid[code], ex).to(torch.bfloat16).contiguous()
+
+
+def quantize_mxfp4_rows(w, max_elems=1 << 21):
+    """quantize_mxfp4_blocks(w)[:2] computed over slices of rows (the blocks run along K: rows are independent, the codes are the same),
+    so that the quantiser's float64 temporaries do not grow with the matrix: the load path of an `mxfp4_only` engine.  The quantiser
+    holds about nine float64-sized temporaries per element at its peak: 2^21 elements per slice (512 rows at K = 4096) is about 150 MB,
+    which beside the largest 16-bit matrix of a 7B layer (gate/up, 172 MiB) stays inside one layer's 386 MiB."""
+    N, K = w.shape
+    rows = max(1, max_elems // max(K, 1))
+    q = torch.empty(N, K // 2, dtype=torch.uint8, device=w.device)
+    e = torch.empty(N, K // 32, dtype=torch.uint8, device=w.device)
+    for r0 in range(0, N, rows):
+        qs, es, _ = quantize_mxfp4_blocks(w[r0:r0 + rows])
+        q[r0:r0 + rows].copy_(qs)
+        e[r0:r0 + rows].copy_(es)
+    return q, e
 
 
 def rope_tables(head_dim, theta, max_pos):
@@ -180,7 +210,7 @@ def rope_tables(head_dim, theta, max_pos):
 
 
 class TeoEngine:
-    def __init__(self, state_dict, config, dtype=torch.bfloat16, device="cuda:0", max_seq=None, weight_format=None):
+    def __init__(self, state_dict, config, dtype=torch.bfloat16, device="cuda:0", max_seq=None, weight_format=None, mxfp4_only=False):
         self.lib = L.load()                       # raises TeoLibraryError when the HIP library is missing
         if not torch.cuda.is_available():
             raise RuntimeError("TeoEngine needs an MI355X (no CPU fallback exists for the product path)")
@@ -199,6 +229,13 @@ class TeoEngine:
             # the power-of-two scales make every dequantised e4m3 / e2m1 weight an exact bfloat16; in binary16 the smallest ones fall
             # into the subnormal range and would not be exact (and the fp8 / MXFP4 GEMV kernels convert to bf16)
             raise ValueError(f"weight_format={self.weight_format!r} needs dtype=torch.bfloat16")
+        # mxfp4_only: the four layer matrices exist in MXFP4 alone (no 16-bit copies): prefill on teo_gemm_w4, the batched step on the
+        # tiled 4-bit copies; both options on for good
+        self.mxfp4_only = bool(mxfp4_only)
+        if self.mxfp4_only:
+            if self.weight_format != "mxfp4":
+                raise ValueError("mxfp4_only needs weight_format='mxfp4'")
+            self._check_mxfp4_sizes("mxfp4_only")
         self._keep = []                           # host pointer arrays referenced by the descriptors
         self._ws = {}
         self._phase_depth = 0
@@ -213,6 +250,12 @@ class TeoEngine:
         self._load_llama(state_dict)
         self._alloc_cache()
         self._alloc_decode_state(max_new=max(4096, self.max_seq))
+
+    def _check_mxfp4_sizes(self, what):
+        c = self.cfg
+        if c.hidden_size % 128 or c.intermediate_size % 128 or (c.num_attention_heads * c.head_dim) % 128:
+            raise ValueError(f"{what} needs hidden_size {c.hidden_size}, num_attention_heads * head_dim {c.num_attention_heads * c.head_dim} and "
+                             f"intermediate_size {c.intermediate_size} to be multiples of 128 (the k-step of the MXFP4 GEMMs)")
 
     # ------------------------------------------------------------------ weights
     def _dev(self, t):
@@ -314,14 +357,42 @@ class TeoEngine:
         cs, sn = rope_tables(hd, c.rope_theta, self.max_pos)
         self.rope_cos, self.rope_sin = cs.to(self.device), sn.to(self.device)
         per = {k: [] for k in ("in_norm", "qkv", "o", "post_norm", "gateup", "down")}
+        self.prefill_mxfp4 = False                # set_options(prefill_mxfp4=True): prefill reads the MXFP4 arrays (teo_llama_desc.prefill_w4)
+        fused = {"qkv": lambda p: torch.cat([sd[p + f"self_attn.{n}_proj.weight"] for n in "qkv"], dim=0),
+                 "o": lambda p: sd[p + "self_attn.o_proj.weight"],
+                 "gateup": lambda p: interleave_gate_up(sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"]),
+                 "down": lambda p: sd[p + "mlp.down_proj.weight"]}
+        if self.mxfp4_only:
+            # matrix by matrix: 16-bit on the device, quantised in row slices, dropped -- the engine never holds more than ONE 16-bit layer
+            # matrix (plus the quantiser's temporaries, about 150 MB at the default slice) above its final size
+            w4 = {k: [] for k in fused}
+            e4 = {k: [] for k in fused}
+            for i in range(c.num_hidden_layers):
+                p = f"model.layers.{i}."
+                per["in_norm"].append(self._dev(sd[p + "input_layernorm.weight"]))
+                per["post_norm"].append(self._dev(sd[p + "post_attention_layernorm.weight"]))
+                for k in fused:
+                    w16 = self._dev(fused[k](p))
+                    q, e = quantize_mxfp4_rows(w16)
+                    del w16
+                    w4[k].append(q)
+                    e4[k].append(e)
+            for k in fused:
+                per[k] = None                     # no 16-bit layer matrices: dequantize_mxfp4_blocks(*llama_w4...) rebuilds one on demand
+            self.llama_w = per
+            self.llama_w8 = None
+            self.llama_w4 = (w4, e4)
+            self.batch_mxfp4 = True
+            self.prefill_mxfp4 = True
+            return
         for i in range(c.num_hidden_layers):
             p = f"model.layers.{i}."
             per["in_norm"].append(self._dev(sd[p + "input_layernorm.weight"]))
-            per["qkv"].append(self._dev(torch.cat([sd[p + f"self_attn.{n}_proj.weight"] for n in "qkv"], dim=0)))
-            per["o"].append(self._dev(sd[p + "self_attn.o_proj.weight"]))
+            per["qkv"].append(self._dev(fused["qkv"](p)))
+            per["o"].append(self._dev(fused["o"](p)))
             per["post_norm"].append(self._dev(sd[p + "post_attention_layernorm.weight"]))
-            per["gateup"].append(self._dev(interleave_gate_up(sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"])))
-            per["down"].append(self._dev(sd[p + "mlp.down_proj.weight"]))
+            per["gateup"].append(self._dev(fused["gateup"](p)))
+            per["down"].append(self._dev(fused["down"](p)))
         self.llama_w = per
         self.llama_w8 = None
         if self.weight_format == "fp8":
@@ -367,11 +438,12 @@ class TeoEngine:
         d.embed, d.final_norm_w, d.lm_head = self.embed.data_ptr(), self.final_norm.data_ptr(), self.lm_head.data_ptr()
         d.rope_cos, d.rope_sin, d.max_pos = self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), self.max_pos
         d.in_norm_w = self._arr(self.llama_w["in_norm"])
-        d.qkv_w = self._arr(self.llama_w["qkv"])
-        d.o_w = self._arr(self.llama_w["o"])
         d.post_norm_w = self._arr(self.llama_w["post_norm"])
-        d.gateup_w = self._arr(self.llama_w["gateup"])
-        d.down_w = self._arr(self.llama_w["down"])
+        if not self.mxfp4_only:                   # (mxfp4_only: the 16-bit layer pointers stay NULL; prefill_w4 below makes prefill not read them)
+            d.qkv_w = self._arr(self.llama_w["qkv"])
+            d.o_w = self._arr(self.llama_w["o"])
+            d.gateup_w = self._arr(self.llama_w["gateup"])
+            d.down_w = self._arr(self.llama_w["down"])
         d.k_cache = self._arr([self.k_cache[i] for i in range(Lr)])
         d.v_cache = self._arr([self.v_cache[i] for i in range(Lr)])
         d.vt_cache = self._arr([self.vt_cache[i] for i in range(Lr)])
@@ -388,6 +460,7 @@ class TeoEngine:
             d.o_w4, d.o_e4 = self._arr(w4["o"]), self._arr(e4["o"])
             d.gateup_w4, d.gateup_e4 = self._arr(w4["gateup"]), self._arr(e4["gateup"])
             d.down_w4, d.down_e4 = self._arr(w4["down"]), self._arr(e4["down"])
+        d.prefill_w4 = 1 if self.prefill_mxfp4 else 0
         d.tune = self.tune.ptr
         self.llama_desc = d
 
@@ -604,6 +677,7 @@ class TeoEngine:
                 cur = getattr(eng, "_fwd_slots", None)
                 if cur is not None:
                     cur["desc"].prefill_fp8, cur["desc"].rope_in_attn = src.prefill_fp8, src.rope_in_attn
+                    cur["desc"].prefill_w4 = src.prefill_w4          # (a copy of the engine's descriptor: row-major *_w4 arrays)
             if not getattr(self, "_fwd_hooked", False):
                 self._option_hooks.append(_sync)
                 self._fwd_hooked = True
@@ -657,14 +731,27 @@ class TeoEngine:
             L.check(self.lib.teo_llama_decode_begin(C.byref(self.llama_desc), C.byref(self.decode_state), _p(ws), ws.numel(),
                                                     st), "teo_llama_decode_begin")
 
-    def set_options(self, prefill_fp8=None, rope_in_attn=None, batch_mxfp4=None):
+    def set_options(self, prefill_fp8=None, rope_in_attn=None, batch_mxfp4=None, prefill_mxfp4=None):
         """Per-engine options of the LLaMA descriptor (include/teo_hip.h teo_llama_desc): `prefill_fp8` = w8a8 prefill on the fp8
         MFMA (lossy, needs weight_format='fp8'), `rope_in_attn` = RoPE + KV append inside the decode attention kernel instead of
         the QKV GEMV epilogue (same values).  Not process-global: two engines in one process can differ.
         `batch_mxfp4` (default False; needs weight_format='mxfp4'): the BATCHED decode step streams tiled MXFP4 copies of qkv / o /
         gateup / down (teo_decode_batch_state.w_mxfp4) instead of 16-bit tiled copies of the dequantised weights -- the same weights,
-        another fp32 order of the sums.  A BatchDecoder reads it when it is built (model.batch_decoder() rebuilds its cached one)."""
+        another fp32 order of the sums.  A BatchDecoder reads it when it is built (model.batch_decoder() rebuilds its cached one).
+        `prefill_mxfp4` (default False; needs weight_format='mxfp4' and hidden / heads * head_dim / intermediate sizes that are multiples
+        of 128): the four Linear layers of every prefill run teo_gemm_w4 on the MXFP4 arrays (teo_llama_desc.prefill_w4) -- bit-identical
+        to the bf16 prefill on the dequantised matrices.  On an `mxfp4_only` engine prefill_mxfp4 and batch_mxfp4 are on and cannot be
+        switched off (there is no 16-bit matrix to go back to): ValueError."""
         d = self.llama_desc
+        if self.mxfp4_only and ((prefill_mxfp4 is not None and not prefill_mxfp4) or (batch_mxfp4 is not None and not batch_mxfp4)):
+            raise ValueError("an mxfp4_only engine holds no 16-bit layer matrices: prefill_mxfp4 / batch_mxfp4 cannot be switched off")
+        if prefill_mxfp4 is not None:
+            if prefill_mxfp4:
+                if self.llama_w4 is None:
+                    raise ValueError("prefill_mxfp4 needs weight_format='mxfp4' (the MXFP4 weight copies)")
+                self._check_mxfp4_sizes("prefill_mxfp4")
+            self.prefill_mxfp4 = bool(prefill_mxfp4)
+            d.prefill_w4 = 1 if prefill_mxfp4 else 0
         if batch_mxfp4 is not None:
             if batch_mxfp4 and self.llama_w4 is None:
                 raise ValueError("batch_mxfp4 needs weight_format='mxfp4' (the MXFP4 weight copies)")
