@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define TEO_ABI_VERSION 4 /* 4 (additive, same number: teo_gemm_w4, teo_gemm_w4_plan, teo_llama_desc.prefill_w4 in front of `tune` -- the load-time teo_sizeof check, not this number, refuses a binding older than the library); 4: MXFP4 weights in the batched decode step (teo_gemm_skinny_w4, teo_decode_batch_state.w_mxfp4); 3: MXFP4 decode weights (teo_llama_desc *_w4 / *_e4, teo_gemv_w4); 2: teo_tune blocks, `tune` last in the descriptors, teo_sizeof */
+#define TEO_ABI_VERSION 4 /* 4 (additive, same number: teo_gemm_w4a8, teo_gemm_w4a8_plan, teo_llama_desc.prefill_w4a8 behind rope_in_attn in what was padding -- no offset moves and sizeof stays, so an older binding keeps working and leaves it 0; before that teo_gemm_w4, teo_gemm_w4_plan, teo_llama_desc.prefill_w4 in front of `tune` -- that change grew sizeof: the load-time teo_sizeof check, not this number, refuses a binding older than IT); 4: MXFP4 weights in the batched decode step (teo_gemm_skinny_w4, teo_decode_batch_state.w_mxfp4); 3: MXFP4 decode weights (teo_llama_desc *_w4 / *_e4, teo_gemv_w4); 2: teo_tune blocks, `tune` last in the descriptors, teo_sizeof */
 
 typedef void* teo_stream_t; /* hipStream_t */
 
@@ -52,7 +52,7 @@ const char* teo_last_error(void);
 /* Diagnostics: which kernel family the most recent teo_gemm* / teo_attention call of this thread dispatched to
  * ("gemm_simple", "gemm_mfma_128", "gemm_mfma_128_sk", "gemm_wide", "gemm_wide_sk", "gemm_big", "gemm_big_hybrid", "gemm_fp8_*",
  * "gemm_big_hybrid_cohort", "gemm_narrow_64", "gemm_narrow_128", "gemm_narrow_128w8", "gemm_pipe_64x64", "gemm_pipe_64", "gemm_pipe_64_r4", "gemm_pipe_128x96",
- * "gemm_pipe_128", "gemm_quad_160", "gemm_quad_160_w4", "gemm_w4_64", "gemm_w4_128", "gemm_w4_256", "gemm_w4_256x160", "attn_flash32", "attn_simple").  Lets the parity tests state which production kernel they checked. */
+ * "gemm_pipe_128", "gemm_quad_160", "gemm_quad_160_w4", "gemm_w4_64", "gemm_w4_128", "gemm_w4_256", "gemm_w4_256x160", "gemm_w4a8_64", "gemm_w4a8_128", "gemm_w4a8_wide", "gemm_w4a8_big", "attn_flash32", "attn_simple").  Lets the parity tests state which production kernel they checked. */
 const char* teo_last_kernel(void);
 /* The family name teo_gemm_ws / teo_gemm_fp8_ws would note for this problem under the calling thread's tune block, on a device of
  * cu_count CUs, with (with_ws = 1) or without a stream-K workspace; nothing is launched.  Dense operands (lda = K, ldc = N, or N / 2
@@ -63,6 +63,9 @@ const char* teo_gemm_fp8_plan(int M, int N, int K, unsigned flags, int out_dtype
 /* The same for teo_gemm_w4 ("gemm_w4_64", "gemm_w4_128", "gemm_w4_256x160", "gemm_w4_256"; "" for a shape it does not take).  The tile
  * follows from M, N, the flags and the CU count alone: no teo_tune key applies to this family and it uses no workspace. */
 const char* teo_gemm_w4_plan(int M, int N, int K, unsigned flags, int out_dtype, int cu_count);
+/* The same for teo_gemm_w4a8 ("gemm_w4a8_64", "gemm_w4a8_128", "gemm_w4a8_wide", "gemm_w4a8_big"; "" for a shape it does not take, a
+ * TEO_F16 output included).  From M, N, the flags and the CU count alone: no teo_tune key, no workspace. */
+const char* teo_gemm_w4a8_plan(int M, int N, int K, unsigned flags, int out_dtype, int cu_count);
 /* Size of a struct of this header as the LIBRARY was built with it (0 for an unknown name): a binding checks its own layout against it
  * at load time -- "teo_vit_desc", "teo_proj_desc", "teo_llama_desc", "teo_decode_state", "teo_decode_batch_state", "teo_attn_args". */
 size_t teo_sizeof(const char* struct_name);
@@ -362,6 +365,26 @@ int teo_gemm_skinny_w4(const void* d_x, const void* d_W4, const void* d_e8m0, co
 int teo_gemm_w4(const void* d_A, const void* d_W4, const void* d_e8m0, const void* d_residual, void* d_C, int M, int N, int K, int lda,
                 int ldc, unsigned flags, int out_dtype, teo_stream_t stream);
 
+/* w4a8 prefill GEMM: MXFP4 weights x per-token e4m3 activations on the block-scaled MFMA (gemm_w4a8.hip):
+ *     C[m, n] = a_scale[m] * sum_k A8[m, k] * ( e2m1(W4[n, k]) * 2^(E[n, k/32] - 127) )     (+ residual[m, n], or the SWIGLU16 pairing)
+ * d_A8 [M, lda] e4m3 bytes and d_a_scale [M] fp32: what teo_quant_rows_fp8 writes.  d_W4 [N, K/2] / d_e8m0 [N, K/32]: teo_gemv_w4's
+ * ROW-MAJOR arrays (low nibble = even k), the ones teo_gemm_w4 reads -- no copy, no re-tiling; gate/up rows interleaved for
+ * TEO_GEMM_SWIGLU16 as for teo_gemm_w4.  residual bf16 [M, ldc] (may alias C), C bf16 or f32.
+ * One K step of 128 is one v_mfma_scale_f32_16x16x128_f8f6f4 with W as the first operand in format fp4 (cbsz = 4): lane l holds the 16
+ * code bytes of MX block l >> 4 of weight row l & 15 in the low four operand registers (byte j = k 2j in the low nibble, 2j + 1 in the
+ * high one) and that block's e8m0 byte in byte 0 of its scale register (op_sel 0); A8 is the second operand (blgp = 0: e4m3, lane l =
+ * bytes 16 (l >> 4) .. + 15 of activation row l & 15 in registers 0 .. 3 and bytes 64 + 16 (l >> 4) .. + 15 in registers 4 .. 7: the
+ * k numbering of an 8-register fp8 operand, as measured) with scale 2^0.  These maps are verified with exact data by
+ * tests/test_mxfp4_a8_gpu.py (one-hot rows against asymmetric codes and exponents).  a_scale[m] is applied once, in the epilogue.
+ * Every product e4m3 x e2m1 x 2^E is exact; the rounding is the instruction's fp32 accumulation and the epilogue's.  Each
+ * accumulator is ONE k-ascending chain of one MFMA per 128 k, so every tile family of this entry is bit-identical to every other.
+ * Supported: every M >= 1, K % 128 == 0, N % 4 == 0 (% 32 with SWIGLU16, which takes no residual), lda % 16 == 0, ldc % 4 == 0,
+ * 16-byte aligned d_A8 / d_W4 / d_e8m0 / d_C (residual: 8); otherwise TEO_ERR_UNSUPPORTED before any launch.  TEO_GEMM_F16 / a TEO_F16
+ * output: TEO_ERR_ARG.  Exponent bytes: the quantiser writes 2 .. 252; 1 .. 254 follow the formula above; 0 and 255 (NaN in OCP MX) are
+ * NOT supported -- what the hardware makes of them is neither defined here nor checked. */
+int teo_gemm_w4a8(const void* d_A8, const float* d_a_scale, const void* d_W4, const void* d_e8m0, const void* d_residual, void* d_C, int M,
+                  int N, int K, int lda, int ldc, unsigned flags, int out_dtype, teo_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Composed runtime entry points (the layer loops live in C++, not Python)
  * ------------------------------------------------------------------------------------------- */
@@ -462,6 +485,13 @@ typedef struct {
                         *    prefill_w4 = 0, and the batched decode step with w_mxfp4 = 0 and no *_w8 copies, return TEO_ERR_ARG */
     int rope_in_attn;  /* single-conversation decode step: 0 = RoPE + KV append in the QKV GEMV epilogue (default), 1 = inside the
                         *    decode attention kernel (same values; the batched step always uses 1) */
+    int prefill_w4a8;  /* (in the four bytes that padded the struct in front of `tune`: no existing field moved, sizeof is unchanged, and a
+                        *    binding written before this field leaves it 0)  1 (only with prefill_w4 = 1, else TEO_ERR_ARG): those four Linear layers run teo_quant_rows_fp8 + teo_gemm_w4a8
+                        *    instead -- activations quantised per token to e4m3 (RMSNorm fused into the quantiser for qkv and gate/up),
+                        *    the same row-major *_w4 / *_e4 arrays, no further device memory.  Lossy beyond the weight quantisation:
+                        *    selectable, never a default.  prefill_w4's checks apply; hidden or inter above the quantiser's 12288:
+                        *    TEO_ERR_UNSUPPORTED; all before anything is written.  RoPE / KV append, attention, lm_head and the
+                        *    hidden-state snapshots are untouched */
     const teo_tune* tune; /* performance knobs of this engine (as teo_vit_desc.tune); a captured decode graph keeps the choices made at capture */
 } teo_llama_desc;
 

@@ -68,7 +68,7 @@ class LlamaDesc(C.Structure):
                 ("down_w8", PP), ("down_s", PP), ("lm_head8", C.c_void_p), ("lm_head_s", C.c_void_p),
                 ("qkv_w4", PP), ("qkv_e4", PP), ("o_w4", PP), ("o_e4", PP), ("gateup_w4", PP), ("gateup_e4", PP),
                 ("down_w4", PP), ("down_e4", PP),
-                ("prefill_fp8", C.c_int), ("prefill_w4", C.c_int), ("rope_in_attn", C.c_int), ("tune", C.c_void_p)]
+                ("prefill_fp8", C.c_int), ("prefill_w4", C.c_int), ("rope_in_attn", C.c_int), ("prefill_w4a8", C.c_int), ("tune", C.c_void_p)]
 
 
 class DecodeState(C.Structure):
@@ -100,6 +100,7 @@ _SIGS = {
     "teo_gemm_plan": (C.c_char_p, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "teo_gemm_fp8_plan": (C.c_char_p, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int]),
     "teo_gemm_w4_plan": (C.c_char_p, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]),
+    "teo_gemm_w4a8_plan": (C.c_char_p, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]),
     "teo_sizeof": (C.c_size_t, [C.c_char_p]),
     "teo_tune_create": (C.c_void_p, []),
     "teo_tune_destroy": (C.c_int, [C.c_void_p]),
@@ -115,6 +116,7 @@ _SIGS = {
     "teo_gemm_fp8": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_uint, C.c_int, C.c_void_p]),
     "teo_gemm_fp8_ws": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_uint, C.c_int, C.c_void_p, C.c_void_p]),
     "teo_gemm_w4": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_uint, C.c_int, C.c_void_p]),
+    "teo_gemm_w4a8": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_uint, C.c_int, C.c_void_p]),
     "teo_quant_rows_fp8": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "teo_gemm_workspace_bytes": (C.c_size_t, []),
     "teo_gemm_workspace_init": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -185,7 +187,8 @@ _SIGS = {
 }
 
 ABI_VERSION = 4            # TEO_ABI_VERSION of include/teo_hip.h this binding was written against (teo_gemm_w4 / teo_gemm_w4_plan /
-# teo_llama_desc.prefill_w4 were added under the same number: additive, and a stale .so fails the sizeof check below)
+# teo_llama_desc.prefill_w4 were added under the same number: additive, and a stale .so fails the sizeof check below; then teo_gemm_w4a8 /
+# teo_gemm_w4a8_plan and teo_llama_desc.prefill_w4a8, which sits in former padding behind rope_in_attn: no offset moved, a stale .so misses the exports)
 # (the ctypes mirrors of the header's structs are checked against the library's own sizeof at load: a stale or newer .so must fail
 # THERE, not by reading shifted fields)
 

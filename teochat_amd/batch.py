@@ -46,6 +46,7 @@ class BatchDecoder:
         # batched-step descriptor: slot 0's caches + (optionally) operand-tiled weights
         d = L.LlamaDesc.from_buffer_copy(self.slot_desc[0])
         d.prefill_w4 = 0                          # its *_w4 arrays become TILED below: never a prefill descriptor
+        d.prefill_w4a8 = 0
         fp8 = engine.llama_w8 is not None
         ks = 64 if fp8 else 32
         self.tiled = bool(tiled) and dt in (torch.bfloat16, torch.float16) and c.hidden_size % ks == 0 and c.intermediate_size % ks == 0 \
@@ -126,6 +127,7 @@ class BatchDecoder:
                     dd.prefill_fp8, dd.rope_in_attn = src.prefill_fp8, src.rope_in_attn
                 for dd in o.slot_desc:            # row-major *_w4 arrays; the step descriptor's are tiled and keep prefill_w4 = 0
                     dd.prefill_w4 = src.prefill_w4
+                    dd.prefill_w4a8 = src.prefill_w4a8
         engine._option_hooks.append(_sync_options)
 
         def _knob_changed():                      # TeoEngine.tune_set: the captured batched step keeps the choices of its capture

@@ -310,14 +310,16 @@ def load_generation_config(model, model_dir):
 
 def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, load_4bit=False, device_map="auto",
                           device="cuda", cache_dir=None, dtype=None, max_seq=None, seed=2, weight_format=None,
-                          batch_mxfp4=False, mxfp4_only=False):
+                          batch_mxfp4=False, mxfp4_only=False, prefill_mxfp4_a8=False):
     """dtype None = the reference's choice where it has one: a real checkpoint runs in torch.float16 (builder.py:105 passes
     torch_dtype=torch.float16 whatever the file holds; eval/inference.py:53 casts the frames to match) -- unless fp8 or MXFP4 decode weights
     are requested (weight_format="fp8" / "mxfp4"), which go with bfloat16 -- and the synthetic presets in torch.bfloat16 (BASELINE.json's
     headline dtype).  load_4bit (bitsandbytes NF4 in the reference) is not rerouted to MXFP4.  batch_mxfp4=True (with weight_format="mxfp4"):
     the batched decode step streams MXFP4 weights too (TeoEngine.set_options).  mxfp4_only=True (with weight_format="mxfp4"): the engine keeps
     NO 16-bit copies of qkv / o / gate-up / down -- prefill runs on teo_gemm_w4 (bit-identical to the bf16 prefill on the dequantised weights),
-    the batched step on the tiled 4-bit copies; both options are then on for good."""
+    the batched step on the tiled 4-bit copies; both options are then on for good.
+    prefill_mxfp4_a8=True (with weight_format="mxfp4"): prefill on teo_gemm_w4a8 -- the MXFP4 weights against per-token e4m3 activations
+    (lossy; switches prefill_mxfp4 on with it; TeoEngine.set_options)."""
     if device in (None, "cuda"):
         device = "cuda:0"
     if dtype is None:
@@ -357,6 +359,8 @@ def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, l
     del sd
     if batch_mxfp4:
         engine.set_options(batch_mxfp4=True)      # ValueError unless weight_format="mxfp4"
+    if prefill_mxfp4_a8:
+        engine.set_options(prefill_mxfp4=True, prefill_mxfp4_a8=True)
     image_processor = TeoImageProcessor(size=cfg.vision_config.image_size, engine=engine)     # uint8 frames -> device kernel
     model = LlavaLlamaForCausalLM(cfg, engine, image_processor)
     # GenerationMixin's fallback knobs belong to the model object, which the LoRA / projector branches build with

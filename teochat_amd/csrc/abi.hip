@@ -113,6 +113,11 @@ const char* teo_gemm_w4_plan(int M, int N, int K, unsigned flags, int out_dtype,
     const bool ok = (out_dtype == TEO_BF16 || out_dtype == TEO_F32) && teo::gemm_w4_ok(M, N, K, K, ldc, flags, nullptr, nullptr, nullptr, nullptr);
     return teo::plan_gemm_w4({M, N, K, K, ldc, TEO_ACT_NONE, flags, TEO_BF16, out_dtype, ok}, teo::tune(), cu_count).name;
 }
+const char* teo_gemm_w4a8_plan(int M, int N, int K, unsigned flags, int out_dtype, int cu_count) {
+    const int ldc = (flags & TEO_GEMM_SWIGLU16) ? N / 2 : N;
+    const bool ok = (out_dtype == TEO_BF16 || out_dtype == TEO_F32) && teo::gemm_w4a8_ok(M, N, K, K, ldc, flags, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return teo::plan_gemm_w4a8({M, N, K, K, ldc, TEO_ACT_NONE, flags, TEO_BF16, out_dtype, ok}, teo::tune(), cu_count).name;
+}
 
 teo_tune* teo_tune_create(void) { return new (std::nothrow) teo_tune(); }
 int teo_tune_destroy(teo_tune* t) {
@@ -225,6 +230,16 @@ int teo_gemm_w4(const void* A, const void* W4, const void* e8m0, const void* res
     if (M == 0 || N == 0) return TEO_OK;
     NEED(A, "A"); NEED(W4, "W4"); NEED(e8m0, "e8m0"); NEED(C, "C");
     return gemm_w4(A, W4, e8m0, res, C, M, N, K, lda, ldc, flags, out_dtype, ST(s));
+}
+int teo_gemm_w4a8(const void* A8, const float* a_scale, const void* W4, const void* e8m0, const void* res, void* C, int M, int N, int K, int lda,
+                  int ldc, unsigned flags, int out_dtype, teo_stream_t s) {
+    ENTER();
+    TEO_CHECK_ARG(M >= 0 && N >= 0 && K > 0 && lda >= K, "teo_gemm_w4a8: M %d N %d K %d lda %d", M, N, K, lda);
+    TEO_CHECK_ARG(ldc >= ((flags & TEO_GEMM_SWIGLU16) ? N / 2 : N), "teo_gemm_w4a8: ldc %d too small", ldc);
+    TEO_CHECK_ARG(out_dtype == TEO_BF16 || out_dtype == TEO_F32, "teo_gemm_w4a8: out_dtype %d (bf16 or f32 out)", out_dtype);
+    TEO_CHECK_ARG(!(flags & TEO_GEMM_F16), "teo_gemm_w4a8: MXFP4 weights go with bfloat16");
+    if (M && N) { NEED(A8, "A8"); NEED(a_scale, "a_scale"); NEED(W4, "W4"); NEED(e8m0, "e8m0"); NEED(C, "C"); }
+    return gemm_w4a8(A8, a_scale, W4, e8m0, res, C, M, N, K, lda, ldc, flags, out_dtype, ST(s));
 }
 int teo_quant_rows_fp8(const void* x, const void* norm_w, void* q, float* scale, int rows, int K, int ldx, float eps, teo_stream_t s) {
     ENTER();
@@ -395,6 +410,7 @@ int teo_projector(const teo_proj_desc* d, const void* x, int rows, void* y, void
 
 // teo_llama_desc.prefill_w4 and the 16-bit layer pointers it makes optional: argument checks of every prefill entry, before any launch
 static int check_prefill_weights(const teo_llama_desc* d) {
+    TEO_CHECK_ARG(!d->prefill_w4a8 || d->prefill_w4, "prefill: prefill_w4a8 is an option of prefill_w4 = 1");
     if (!d->prefill_w4) {
         TEO_CHECK_ARG(d->qkv_w && d->o_w && d->gateup_w && d->down_w,
                       "prefill: the 16-bit qkv / o / gateup / down matrices are missing (a 4-bit-only descriptor needs prefill_w4 = 1)");
@@ -408,6 +424,11 @@ static int check_prefill_weights(const teo_llama_desc* d) {
     TEO_CHECK_ARG(!d->prefill_fp8, "prefill: prefill_w4 and prefill_fp8 exclude each other");
     if (d->hidden % 128 != 0 || d->inter % 128 != 0 || (d->heads * d->head_dim) % 128 != 0) {
         set_error("prefill: prefill_w4 needs hidden %d, heads * head_dim %d and inter %d to be multiples of 128", d->hidden,
+                  d->heads * d->head_dim, d->inter);
+        return TEO_ERR_UNSUPPORTED;
+    }
+    if (d->prefill_w4a8 && (d->hidden > 12288 || d->inter > 12288 || d->heads * d->head_dim > 12288)) {
+        set_error("prefill: prefill_w4a8 quantises rows of at most 12288 elements (hidden %d, heads * head_dim %d, inter %d)", d->hidden,
                   d->heads * d->head_dim, d->inter);
         return TEO_ERR_UNSUPPORTED;
     }

@@ -22,6 +22,7 @@ enum class GemmFamily {
     Fp8WideSk,    // gemm_mfma_fp8_wide_sk_kernel
     Fp8Big,       // gemm_mfma_fp8_big_kernel 256 x 256
     W4,           // gemm_w4_kernel (gemm_w4.hip): MXFP4 weights, bm x tn of 64 x 64, 128 x 128, 256 x 128, 256 x 160
+    W4A8,         // gemm_w4a8_kernel (gemm_w4a8.hip): MXFP4 weights x e4m3 activations, bm x tn of 64 x 32, 128 x 128, 128 x 256, 256 x 256
     Invalid,      // no kernel takes the problem (gemm_fp8_ok failed)
 };
 
@@ -37,8 +38,8 @@ struct GemmProblem {
 struct GemmPlan {
     GemmFamily family = GemmFamily::Simple;
     bool workspace = false;   // the stream-K workspace is usable (given, and the device has the 256 CUs its grids are sized for)
-    int bm = 0;               // Plain / Narrow / Pipe / W4: tile rows
-    int tn = 0;               // Pipe / W4: tile columns
+    int bm = 0;               // Plain / Narrow / Pipe / W4 / W4A8: tile rows
+    int tn = 0;               // Pipe / W4 / W4A8: tile columns
     int stages = 0;           // Pipe: LDS ring depth
     int depth = 0;            // Plain (bm 128): register prefetch depth, 2 or 1
     bool waves8 = false;      // Narrow 128 x 128 / Quad: the eight-wave form
@@ -54,6 +55,7 @@ struct GemmPlan {
 GemmPlan plan_gemm(const GemmProblem& p, const teo_tune& t, int cu_count, bool have_workspace);
 GemmPlan plan_gemm_fp8(const GemmProblem& p, const teo_tune& t, int cu_count, bool have_workspace);
 GemmPlan plan_gemm_w4(const GemmProblem& p, const teo_tune& t, int cu_count);      // aligned = gemm_w4_ok of the call
+GemmPlan plan_gemm_w4a8(const GemmProblem& p, const teo_tune& t, int cu_count);    // aligned = gemm_w4a8_ok of the call and a bf16 / f32 output
 
 // f(std::integral_constant<bool, b>...) with every runtime flag turned into a compile-time one: the launch helpers' way of picking a
 // template instantiation (each call instantiates f for all 2^n combinations of its flags, no more)

@@ -18,6 +18,7 @@
 //   plain           gemm_mfma_64 / gemm_mfma_128   the rest (the register-staged kernel: the SwiGLU epilogue, forced gemm_bm)
 // w8a8 (plan_gemm_fp8): fp8 big (256 x 256) -> fp8 wide stream-K -> fp8 wide (128 x 256) -> fp8 128 x 128.
 // MXFP4 weights (plan_gemm_w4): gemm_w4_64 -> gemm_w4_128 -> gemm_w4_256x160 -> gemm_w4_256, from the problem alone (no knob, no workspace).
+// MXFP4 weights x e4m3 activations (plan_gemm_w4a8): gemm_w4a8_64 -> gemm_w4a8_128 -> gemm_w4a8_big -> gemm_w4a8_wide, likewise.
 // The stream-K and hybrid forms need a workspace and a 256-CU device (their grids are sized for it).
 #include "common.h"
 #include <algorithm>
@@ -322,6 +323,32 @@ GemmPlan plan_gemm_w4(const GemmProblem& p, const teo_tune&, int cu_count) {
     if ((long long)cdiv(M, 128) * cdiv(N, 128) <= 2 * cus) return tile(128, 128, "gemm_w4_128");
     if (!swiglu && (long long)cdiv(M, 256) * cdiv(N, 160) <= cus) return tile(256, 160, "gemm_w4_256x160");
     return tile(256, 128, "gemm_w4_256");
+}
+
+// The w4a8 prefill GEMM (gemm_w4a8.hip): rings of three LDS-DMA stages, every tile bit-identical to every other.  The rules, in order:
+//   64 x 32      a short turn (M <= 128): the launch is bound by W's stream, and 32-column tiles put o / down (N = 4096) on 128 / 256
+//                workgroups instead of 64
+//   128 x 128    fewer than 192 tiles of 128 x 256, i.e. under three quarters of a round at one eight-wave workgroup per CU (config C2,
+//                M = 638: qkv 480, o / down 160 tiles of 128 x 128, two four-wave workgroups per CU)
+//   256 x 256    where the rounds model of the w8a8 planner prefers it (a round costs F8_BIG_ROUND_COST rounds of 128 x 256 for twice
+//                the area): qkv at M = 2168 (432 tiles: 2 rounds against 4), and o / down there (144 tiles: ONE round where 272 tiles of
+//                128 x 256 need a ragged second one -- this entry has no workspace, so no stream-K form)
+//   128 x 256    everything else (gate/up at M = 2168: 1462 tiles, 6 rounds against 4 x 1.66)
+// No teo_tune key selects among them and no workspace is used: tests reach every family through M and N.
+GemmPlan plan_gemm_w4a8(const GemmProblem& p, const teo_tune&, int cu_count) {
+    const int M = p.M, N = p.N;
+    GemmPlan g;
+    if (!p.aligned) return named(g, GemmFamily::Invalid, "");
+    const long long cus = cu_count > 0 ? cu_count : 256;
+    const auto tile = [&](int bm, int tn, const char* name) {
+        g.bm = bm, g.tn = tn, g.stages = 3;
+        return named(g, GemmFamily::W4A8, name);
+    };
+    if (M <= 128) return tile(64, 32, "gemm_w4a8_64");
+    const long long t_wide = (long long)cdiv(M, 128) * cdiv(N, 256), t_big = (long long)cdiv(M, 256) * cdiv(N, 256);
+    if (t_wide * 4 < cus * 3) return tile(128, 128, "gemm_w4a8_128");
+    if ((double)cdiv(t_big, cus) * F8_BIG_ROUND_COST < (double)cdiv(t_wide, cus)) return tile(256, 256, "gemm_w4a8_big");
+    return tile(128, 256, "gemm_w4a8_wide");
 }
 
 }  // namespace teo

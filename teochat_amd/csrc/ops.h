@@ -112,6 +112,11 @@ int gemm_fp8(const void* A8, const float* a_scale, const void* W8, const float* 
 bool gemm_w4_ok(int M, int N, int K, int lda, int ldc, unsigned flags, const void* A, const void* W4, const void* res, const void* C);
 int gemm_w4(const void* A, const void* W4, const void* E4, const void* res, void* C, int M, int N, int K, int lda, int ldc, unsigned flags,
             int out_dtype, hipStream_t st);
+// w4a8 prefill GEMM (gemm_w4a8.hip): the same row-major MXFP4 arrays against quant_rows_fp8's e4m3 activations, on the block-scaled MFMA
+bool gemm_w4a8_ok(int M, int N, int K, int lda, int ldc, unsigned flags, const void* A, const void* W4, const void* E4, const void* res,
+                  const void* C);
+int gemm_w4a8(const void* A8, const float* a_scale, const void* W4, const void* E4, const void* res, void* C, int M, int N, int K, int lda,
+              int ldc, unsigned flags, int out_dtype, hipStream_t st);
 int quant_rows_fp8(const void* x, const void* norm_w, void* q, float* s, int M, int K, int ldx, float eps, hipStream_t st);
 int gemm_sk_workspace_init(void* ws, hipStream_t st);
 // decode GEMV weight formats: the activations' own type, fp8 e4m3 + one fp32 scale per row, MXFP4 (e2m1 codes + one e8m0 byte per

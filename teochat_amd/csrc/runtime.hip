@@ -206,6 +206,24 @@ static int prefill_layer_w4(const teo_llama_desc* d, const PrefillWs& w, int l, 
     return gemm_w4(w.act, d->down_w4[l], d->down_e4[l], w.h, w.h, S, D, Fi, Fi, D, 0, dt, st);
 }
 
+// the same four Linear layers in w4a8 form (gemm_w4a8.hip; `prefill_w4a8` on top of `prefill_w4`, lossy, never a default): the order of
+// prefill_layer_fp8 -- RMSNorm fused into the quantiser for qkv and gate/up -- on the row-major *_w4 / *_e4 arrays, q8 / qs of the workspace
+template <typename F>
+static int prefill_layer_w4a8(const teo_llama_desc* d, const PrefillWs& w, int l, int S, F attend, hipStream_t st) {
+    const int dt = d->dtype;
+    const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim, Fi = d->inter;
+    const int QKV = (H + 2 * Hk) * hd;
+    TEO_TRY(quant_rows_fp8(w.h, d->in_norm_w[l], w.q8, w.qs, S, D, D, d->eps, st));
+    TEO_TRY(gemm_w4a8(w.q8, w.qs, d->qkv_w4[l], d->qkv_e4[l], nullptr, w.qkv, S, QKV, D, D, QKV, 0, dt, st));
+    TEO_TRY(attend());
+    TEO_TRY(quant_rows_fp8(w.attn, nullptr, w.q8, w.qs, S, H * hd, H * hd, d->eps, st));
+    TEO_TRY(gemm_w4a8(w.q8, w.qs, d->o_w4[l], d->o_e4[l], w.h, w.h, S, D, H * hd, H * hd, D, 0, dt, st));
+    TEO_TRY(quant_rows_fp8(w.h, d->post_norm_w[l], w.q8, w.qs, S, D, D, d->eps, st));
+    TEO_TRY(gemm_w4a8(w.q8, w.qs, d->gateup_w4[l], d->gateup_e4[l], nullptr, w.act, S, 2 * Fi, D, D, Fi, TEO_GEMM_SWIGLU16, dt, st));
+    TEO_TRY(quant_rows_fp8(w.act, nullptr, w.q8, w.qs, S, Fi, Fi, d->eps, st));
+    return gemm_w4a8(w.q8, w.qs, d->down_w4[l], d->down_e4[l], w.h, w.h, S, D, Fi, Fi, D, 0, dt, st);
+}
+
 size_t llama_prefill_workspace_bytes(const teo_llama_desc* d, int S) { return prefill_carve(d, S, nullptr, 0).total; }
 // sticky hand-off error word of the GEMM workspace inside a prefill / tower workspace (0 = fine); synchronises the stream
 int llama_prefill_workspace_status(const teo_llama_desc* d, int S, void* ws, size_t ws_bytes, int* host_flag, hipStream_t st) {
@@ -269,6 +287,10 @@ int llama_prefill(const teo_llama_desc* d, const void* embeds, const int* positi
         };
         if (fp8) {
             TEO_TRY(prefill_layer_fp8(d, w, l, S, attend, st));
+            continue;
+        }
+        if (d->prefill_w4 && d->prefill_w4a8) {
+            TEO_TRY(prefill_layer_w4a8(d, w, l, S, attend, st));
             continue;
         }
         if (d->prefill_w4) {
@@ -349,6 +371,10 @@ int llama_prefill_batch(const teo_llama_desc* d, const void* embeds, const int* 
         };
         if (fp8) {
             TEO_TRY(prefill_layer_fp8(d, w, l, S, attend, st));
+            continue;
+        }
+        if (d->prefill_w4 && d->prefill_w4a8) {
+            TEO_TRY(prefill_layer_w4a8(d, w, l, S, attend, st));
             continue;
         }
         if (d->prefill_w4) {

@@ -357,6 +357,7 @@ class TeoEngine:
         cs, sn = rope_tables(hd, c.rope_theta, self.max_pos)
         self.rope_cos, self.rope_sin = cs.to(self.device), sn.to(self.device)
         per = {k: [] for k in ("in_norm", "qkv", "o", "post_norm", "gateup", "down")}
+        self.prefill_mxfp4_a8 = False             # set_options(prefill_mxfp4_a8=True): ... against e4m3 activations (teo_llama_desc.prefill_w4a8)
         self.prefill_mxfp4 = False                # set_options(prefill_mxfp4=True): prefill reads the MXFP4 arrays (teo_llama_desc.prefill_w4)
         fused = {"qkv": lambda p: torch.cat([sd[p + f"self_attn.{n}_proj.weight"] for n in "qkv"], dim=0),
                  "o": lambda p: sd[p + "self_attn.o_proj.weight"],
@@ -461,6 +462,7 @@ class TeoEngine:
             d.gateup_w4, d.gateup_e4 = self._arr(w4["gateup"]), self._arr(e4["gateup"])
             d.down_w4, d.down_e4 = self._arr(w4["down"]), self._arr(e4["down"])
         d.prefill_w4 = 1 if self.prefill_mxfp4 else 0
+        d.prefill_w4a8 = 1 if (self.prefill_mxfp4 and self.prefill_mxfp4_a8) else 0
         d.tune = self.tune.ptr
         self.llama_desc = d
 
@@ -678,6 +680,7 @@ class TeoEngine:
                 if cur is not None:
                     cur["desc"].prefill_fp8, cur["desc"].rope_in_attn = src.prefill_fp8, src.rope_in_attn
                     cur["desc"].prefill_w4 = src.prefill_w4          # (a copy of the engine's descriptor: row-major *_w4 arrays)
+                    cur["desc"].prefill_w4a8 = src.prefill_w4a8
             if not getattr(self, "_fwd_hooked", False):
                 self._option_hooks.append(_sync)
                 self._fwd_hooked = True
@@ -731,7 +734,7 @@ class TeoEngine:
             L.check(self.lib.teo_llama_decode_begin(C.byref(self.llama_desc), C.byref(self.decode_state), _p(ws), ws.numel(),
                                                     st), "teo_llama_decode_begin")
 
-    def set_options(self, prefill_fp8=None, rope_in_attn=None, batch_mxfp4=None, prefill_mxfp4=None):
+    def set_options(self, prefill_fp8=None, rope_in_attn=None, batch_mxfp4=None, prefill_mxfp4=None, prefill_mxfp4_a8=None):
         """Per-engine options of the LLaMA descriptor (include/teo_hip.h teo_llama_desc): `prefill_fp8` = w8a8 prefill on the fp8
         MFMA (lossy, needs weight_format='fp8'), `rope_in_attn` = RoPE + KV append inside the decode attention kernel instead of
         the QKV GEMV epilogue (same values).  Not process-global: two engines in one process can differ.
@@ -741,8 +744,24 @@ class TeoEngine:
         `prefill_mxfp4` (default False; needs weight_format='mxfp4' and hidden / heads * head_dim / intermediate sizes that are multiples
         of 128): the four Linear layers of every prefill run teo_gemm_w4 on the MXFP4 arrays (teo_llama_desc.prefill_w4) -- bit-identical
         to the bf16 prefill on the dequantised matrices.  On an `mxfp4_only` engine prefill_mxfp4 and batch_mxfp4 are on and cannot be
-        switched off (there is no 16-bit matrix to go back to): ValueError."""
+        switched off (there is no 16-bit matrix to go back to): ValueError.
+        `prefill_mxfp4_a8` (default False; needs weight_format='mxfp4', those sizes, and prefill_mxfp4 on -- already, or in the same call):
+        those Linear layers run teo_quant_rows_fp8 + teo_gemm_w4a8 (teo_llama_desc.prefill_w4a8): per-token e4m3 activations against the
+        same MXFP4 arrays on the block-scaled MFMA.  Lossy, never a default; free to switch on and off, also on an `mxfp4_only` engine.
+        Switching prefill_mxfp4 off while it is on: ValueError."""
         d = self.llama_desc
+        a8 = self.prefill_mxfp4_a8 if prefill_mxfp4_a8 is None else bool(prefill_mxfp4_a8)
+        w4 = self.prefill_mxfp4 if prefill_mxfp4 is None else bool(prefill_mxfp4)
+        if prefill_mxfp4_a8:
+            if self.llama_w4 is None:
+                raise ValueError("prefill_mxfp4_a8 needs weight_format='mxfp4' (the MXFP4 weight copies)")
+            self._check_mxfp4_sizes("prefill_mxfp4_a8")
+            if max(self.cfg.hidden_size, self.cfg.intermediate_size, self.cfg.num_attention_heads * self.cfg.head_dim) > 12288:
+                raise ValueError("prefill_mxfp4_a8 quantises rows of at most 12288 elements (hidden / intermediate size)")
+            if not w4:
+                raise ValueError("prefill_mxfp4_a8 needs prefill_mxfp4 on (set_options(prefill_mxfp4=True, prefill_mxfp4_a8=True))")
+        elif a8 and not w4:
+            raise ValueError("prefill_mxfp4 cannot be switched off while prefill_mxfp4_a8 is on: switch prefill_mxfp4_a8 off first (or in the same call)")
         if self.mxfp4_only and ((prefill_mxfp4 is not None and not prefill_mxfp4) or (batch_mxfp4 is not None and not batch_mxfp4)):
             raise ValueError("an mxfp4_only engine holds no 16-bit layer matrices: prefill_mxfp4 / batch_mxfp4 cannot be switched off")
         if prefill_mxfp4 is not None:
@@ -752,6 +771,9 @@ class TeoEngine:
                 self._check_mxfp4_sizes("prefill_mxfp4")
             self.prefill_mxfp4 = bool(prefill_mxfp4)
             d.prefill_w4 = 1 if prefill_mxfp4 else 0
+        if prefill_mxfp4_a8 is not None:
+            self.prefill_mxfp4_a8 = a8
+        d.prefill_w4a8 = 1 if (self.prefill_mxfp4 and self.prefill_mxfp4_a8) else 0
         if batch_mxfp4 is not None:
             if batch_mxfp4 and self.llama_w4 is None:
                 raise ValueError("batch_mxfp4 needs weight_format='mxfp4' (the MXFP4 weight copies)")
