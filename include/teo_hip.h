@@ -139,6 +139,25 @@ int teo_layernorm(const void* d_x, const void* d_w, const void* d_b, void* d_y, 
 int teo_rmsnorm(const void* d_x, const void* d_w, void* d_y, int rows, int dim, float eps, int dtype,
                 teo_stream_t stream);
 
+/* Containment -- holds for EVERY entry point of this header, stated once here (tests/test_containment_gpu.py runs each of them on
+ * operands carved from the middle of guarded buffers):
+ *   - an entry writes only the [rows, cols] it is given, at the given strides: the ld - cols pad columns of a strided output (ldc, ldo,
+ *     o_rs, a cache's rows outside [past, past + S)) and the memory around it are preserved bit for bit;
+ *   - no byte outside the described extents of an input affects a result: the pad columns of a strided input (lda, ldx, ld_qkv, a fused
+ *     buffer's other columns), rows behind the last one, whatever follows a bias / scale / e8m0 / index array, cache rows behind the
+ *     context, and workspace bytes the call has not written itself.  Tiles may LOAD a few such bytes (always inside the allocation the
+ *     rows and pad columns span, see below) and discard them; NaN there is as good as zero;
+ *   - what an entry appends to is an output there: teo_rope_kv_append / teo_attn_decode (rope_cos != NULL) change cache positions
+ *     [past, past + S) / pos[b] of K, V and V^T and nothing else, and do not care what those positions held before;
+ *   - a *_workspace_bytes() figure is exact: the call touches no byte beyond it and needs no particular content in it (the stream-K
+ *     hand-off flags are the one exception: teo_gemm_workspace_init for teo_gemm_ws / teo_gemm_fp8_ws; the composed entry points do
+ *     that themselves).
+ * Readable slack an operand must have (a load that is discarded, never a store):
+ *   - rows of a strided operand are whole: all ld elements of every row, the last row's included, are readable;
+ *   - teo_attention's MFMA form reads V^T in whole 64-key tiles: it runs only when vt_rs >= kv_len rounded up to 64 (what lies in that
+ *     padding is masked, NaN included); with a shorter vt_rs the generic kernel runs instead.
+ * No other slack is asked for: the tile loaders clamp row and element indices to the operand instead of reading behind it. */
+
 /* C[M,N] = act(A[M,K] . W[N,K]^T + bias[N]) + residual[M,N]   (bias/residual may be NULL).
  * A rows have stride lda, C/residual rows stride ldc (elements).  out_dtype may be TEO_F32 with
  * bf16 inputs (logits).  Replaces every nn.Linear on the path: tf CLIPAttention q/k/v/out_proj,

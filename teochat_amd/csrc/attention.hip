@@ -379,7 +379,9 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(const int* __r
         if constexpr (ROPE) {
             float vf[VE];
             Cvt16<T>::cvt(vr[i], vf);
-            if (kw0 + i * RPI + grp == pos) {
+            // key pos: the new token's value.  Keys behind it were loaded from the clamped row -- row pos again, which is not written
+            // yet: they take the registers too (their p is 0, but 0 x whatever an unwritten cache row holds is not 0 when that is NaN)
+            if (kw0 + i * RPI + grp >= pos) {
 #pragma unroll
                 for (int e = 0; e < VE; ++e) vf[e] = vnew[e];
             }
@@ -616,7 +618,8 @@ __global__ __launch_bounds__(AW_WAVES * 64) void attn_decode_whole_kernel(const 
         _Pragma("unroll") for (int e = 0; e < VE; ++e) acc[e] = 0.f;                                                   \
         _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                               \
             const float p = sc[(QT) * KPQ + i * RPI + grp];                                                            \
-            const bool isnew = ROPE && c0 + (QT) * KPQ + i * RPI + grp == pos;                                         \
+            /* >= pos: keys behind pos hold the clamped load of row pos, which is not written yet (p = 0, but 0 x NaN is NaN) */ \
+            const bool isnew = ROPE && c0 + (QT) * KPQ + i * RPI + grp >= pos;                                         \
             uint4 vraw = SLOT[i];                                                                                      \
             vraw.x = isnew ? vnew_pk.x : vraw.x; vraw.y = isnew ? vnew_pk.y : vraw.y;                                  \
             vraw.z = isnew ? vnew_pk.z : vraw.z; vraw.w = isnew ? vnew_pk.w : vraw.w;                                  \

@@ -120,8 +120,8 @@ __global__ __launch_bounds__(256) void vt_append_kernel(const T* __restrict__ qk
 }
 
 // bf16 variant with 16-byte global accesses on both sides: block = (64 positions, one kv head, 128 dims per pass).
-// Positions >= S inside the last 8-position store chunk are written as zeros (slots past the sequence end, rewritten by
-// whoever appends there).  Needs (past + s0) % 8 == 0 for the aligned 16-byte stores.
+// The sequence's last, partial 8-position chunk is stored element by element: positions >= S are NOT written (the header's containment
+// rule: cache columns outside [past, past + S) keep their bits).  Needs (past + s0) % 8 == 0 for the aligned 16-byte stores.
 __device__ __forceinline__ void vt_append_vec_body(const bf16_t* __restrict__ qkv, int ld, bf16_t* __restrict__ vtc, int S,
                                                    int past, int S_max, int v_off, int hd, bf16_t* __restrict__ vc, int bx, int by) {
     __shared__ bf16_t tile[64][136];                       // row stride 272 B: 16-byte aligned rows, column reads spread over banks
@@ -145,7 +145,12 @@ __device__ __forceinline__ void vt_append_vec_body(const bf16_t* __restrict__ qk
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 w[e] = (unsigned)tile[pc * 8 + 2 * e][d] | ((unsigned)tile[pc * 8 + 2 * e + 1][d] << 16);
-            *reinterpret_cast<uint4*>(vtc + ((long long)hk * hd + d0 + d) * S_max + past + s0 + pc * 8) = make_uint4(w[0], w[1], w[2], w[3]);
+            bf16_t* dst = vtc + ((long long)hk * hd + d0 + d) * S_max + past + s0 + pc * 8;
+            if (s0 + pc * 8 + 8 <= S) {
+                *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+            } else {
+                for (int e = 0; s0 + pc * 8 + e < S; ++e) dst[e] = tile[pc * 8 + e][d];
+            }
         }
         __syncthreads();
     }

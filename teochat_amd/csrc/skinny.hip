@@ -458,12 +458,17 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_stream_kernel(const bf16_t*
         }
     }
     // ---- weight ring: set g = (tile g / SPT of this workgroup, steps (g % SPT) * UNR ..).  Sets past the end re-read the
-    // activation buffer (L2-resident, always mapped) so that every load stays unconditional and costs no HBM traffic.
+    // activation buffer (L2-resident, always mapped) so that every load stays unconditional and costs no HBM traffic -- its FIRST ROW
+    // only, wrapped inside its K elements: one lane-wide load is 1 KB, and a one-conversation block with K < 512 is shorter than that (the
+    // bytes behind it belong to somebody else, or to nobody: a caller's x may end its allocation).
     // MXFP4: a dead set re-reads tile 0 of W and its exponents instead (always mapped; an arbitrary activation byte could be E = 255)
     const long long pstep = tiled ? 64 * CB : KS;
     const long long tstride = (long long)nsteps * (64 * CB);
     u32x4 w[NS][UNR];
     unsigned we[NS][UNR];                                // MXFP4: the e8m0 byte of each step's block
+    // (wrapped at the largest power of two <= min(2 K, 1024) bytes -- K % 32 == 0, so at least 64: one scalar shift and a lane mask)
+    const int dead_wrap = K >= 512 ? 1024 : (1 << (31 - __builtin_clz((unsigned)(K * 2))));
+    const WT* const dead_w = reinterpret_cast<const WT*>(reinterpret_cast<const unsigned char*>(x) + ((lane * 16) & (dead_wrap - 1)));
 #define TEO_SS_LOADW(SLOT, GI)                                                                                 \
     {                                                                                                          \
         const int g_ = (GI);                                                                                   \
@@ -478,7 +483,7 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_stream_kernel(const bf16_t*
                 w[SLOT][u] = sk_ldw<true>(live_ ? pw : W + lane * CB);                                         \
                 we[SLOT][u] = e8[live_ ? ((long long)tq * nsteps + st_) * 64 + lane : (long long)lane];        \
             } else {                                                                                           \
-                w[SLOT][u] = sk_ldw<true>(live_ ? pw : reinterpret_cast<const WT*>(x) + lane * CH);            \
+                w[SLOT][u] = sk_ldw<true>(live_ ? pw : dead_w);                                                \
             }                                                                                                  \
         }                                                                                                      \
     }
