@@ -191,6 +191,7 @@ class BatchDecoder:
             eng._check_handoffs("prefill", lambda f: self.lib.teo_llama_prefill_workspace_status(C.byref(d), S, _p(ws), ws.numel(), C.byref(f), sid),
                                 "teo_llama_prefill")
         self.cache_len[slot] = past + S
+        self._armed = False                       # forward_step's device positions are stale for this slot now: it re-arms from cache_len
         return logits
 
     def prefill_all(self, embeds_list, last_only=True, hidden_states=False):

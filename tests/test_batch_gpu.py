@@ -285,3 +285,51 @@ def test_forward_api_batched_continuation_equals_generate_batch(name, dtype):
         model(input_ids=torch.cat([nxt, nxt], dim=1), past_key_values=out2.past_key_values, attention_mask=mask)
     # the training-shape forward (use_cache left None) keeps nothing
     assert model(input_ids=ids_p, attention_mask=mask[:, :W], images=flat).past_key_values is None
+
+
+def test_forward_step_after_a_turn_appended_to_one_slot_uses_the_new_position():
+    """forward_step keeps the device positions of an armed loop; BatchDecoder.prefill(slot, ...) between two steps moves that slot's
+    cache_len.  The next step must run slot 1 at its NEW position: its logits are those of a fresh decoder prefilled with the whole
+    history (prompt, the two stepped tokens, the appended turn) and stepped once -- to FP32_TOL, as its first five rows come from the
+    prefill GEMMs there and from decode steps here -- and slot 0, which nothing touched, continues bit for bit."""
+    from teochat_amd.batch import BatchDecoder
+    model, _ = build("tinyB", torch.float32)
+    dev = model.device
+    vcfg, lcfg, mm = TY.cfgs("tinyB")
+    _, convs = conversations("tinyB", 2, lcfg.vocab_size)
+    embs = []
+    for ids, frames in convs:
+        (_, _, _, _, emb, _) = model.prepare_inputs_labels_for_multimodal(ids.view(1, -1).to(dev), None, None, None, None,
+                                                                          [f.to(dev) for f in frames])
+        embs.append(emb[0])
+    table = model.engine.embed
+    steps = [[5, 9], [17, 3], [40, 41]]                       # the tokens fed to (slot 0, slot 1) in steps 1..3
+    extra = table[torch.tensor([7, 300, 12], device=dev)]     # the appended turn: three embedding rows
+
+    plain = BatchDecoder(model.engine, 2, max_new=16)         # the undisturbed run
+    plain.prefill_all(embs)
+    for t in steps:
+        undisturbed = plain.forward_step(t)
+
+    dec = BatchDecoder(model.engine, 2, max_new=16)
+    dec.prefill_all(embs)
+    dec.forward_step(steps[0])
+    dec.forward_step(steps[1])
+    n1 = dec.cache_len[1]
+    dec.prefill(1, extra)
+    assert dec.cache_len == [dec.cache_len[0], n1 + 3]
+    got = dec.forward_step(steps[2])
+    assert dec.d_pos.tolist() == dec.cache_len                          # the step ran at (and advanced from) the host's positions
+
+    fresh = BatchDecoder(model.engine, 2, max_new=16)
+    history = torch.cat([embs[1], table[torch.tensor([steps[0][1], steps[1][1]], device=dev)], extra])
+    fresh.prefill(0, embs[0])
+    fresh.prefill(1, history)
+    assert fresh.cache_len[1] == n1 + 3
+    want = fresh.forward_step([0, steps[2][1]])
+
+    assert torch.equal(got[0], undisturbed[0]), float((got[0] - undisturbed[0]).abs().max())
+    diff = float((got[1] - want[1]).abs().max())
+    print(f"slot 1 after the appended turn vs a fresh decoder on the whole history: max abs logit diff {diff:.2e}")
+    assert diff < FP32_TOL
+    assert float((got[1] - undisturbed[1]).abs().max()) > 100 * FP32_TOL        # the turn changed the answer: the comparison can fail
