@@ -278,6 +278,23 @@ int teo_attn_decode(const void* d_q, void* d_k_cache, void* d_v_cache, void* d_v
                     int kv_heads, int head_dim, float scale, int dtype, int batch, long long q_stride, long long cache_stride,
                     long long o_stride, teo_stream_t stream);
 
+/* Verify attention (speculative decoding): `rows` <= TEO_MAX_DECODE_BATCH new tokens of ONE conversation at consecutive positions
+ * d_pos[0] .. d_pos[0] + rows - 1 -- the pending token and rows - 1 drafts.  d_qkv holds the raw [q | k | v] rows of the QKV projection,
+ * q_stride elements apart.  The kernel applies RoPE to q and k of every row at its own position, appends the rows' K, V (and V^T when
+ * d_vt_cache != NULL) at cache positions d_pos[0] .. + rows - 1 and attends causally: row i sees keys 0 .. d_pos[0] + i.  The cached keys
+ * and values are streamed once for all rows; the new rows' keys and values never come from the cache, and what cache rows >= d_pos[0]
+ * held before does not matter (NaN included).  d_out [rows][heads*head_dim].  The caller keeps d_pos[0] + rows <= max_seq; rows past
+ * max_seq are neither written nor defined.
+ * Contract: output row i and every cache row written are BIT-identical to teo_attn_decode(batch = rows, rope_cos != NULL) on `rows`
+ * copies of the conversation at positions d_pos[0] + i, copy i's cache holding rows d_pos[0] .. d_pos[0] + i - 1 as the earlier rows
+ * append them (same chunk rule -- "attn_chunk" / "attn_whole" move both --, same score, softmax and summation order, same merge).
+ * Takes what teo_attn_decode takes (bf16 / fp16 / fp32, MHA and GQA, the head sizes of its kernels; TEO_ERR_UNSUPPORTED otherwise);
+ * d_partials is teo_attn_verify_workspace_bytes(...) of scratch. */
+size_t teo_attn_verify_workspace_bytes(int heads, int head_dim, int max_seq, int rows);
+int teo_attn_verify(const void* d_qkv, void* d_k_cache, void* d_v_cache, void* d_vt_cache, const float* d_rope_cos,
+                    const float* d_rope_sin, void* d_out, float* d_partials, const int* d_pos, int max_seq, int heads,
+                    int kv_heads, int head_dim, float scale, int dtype, int rows, long long q_stride, teo_stream_t stream);
+
 /* Training-shape loss: mean over rows with label != ignore_index of (logsumexp(logits[r]) - logits[r, label[r]]) --
  * torch.nn.CrossEntropyLoss as LlamaForCausalLM.forward applies it to the shifted logits/labels (call site
  * videollava/model/language_model/llava_llama.py:88-99).  logits fp32 [rows, ld]; labels int64 [rows] (already shifted
@@ -637,6 +654,61 @@ int teo_llama_decode_batch_step_profile(const teo_llama_desc* d, const teo_decod
                                         float* ms_out /* [TEO_PROF_CLASSES] */, int* count_out /* [TEO_PROF_CLASSES] */, teo_stream_t stream);
 int teo_llama_decode_batch_graph_create(const teo_llama_desc* d, const teo_decode_batch_state* st, void* d_workspace,
                                         size_t workspace_bytes, teo_stream_t stream, teo_graph** out);
+
+/* ---- speculative decoding: verify `rows` tokens of ONE conversation per pass over the weights ----------------------------------
+ * A verify step feeds R = rows <= TEO_MAX_DECODE_BATCH rows -- the pending token d_rows[0] and drafts d_rows[1 .. n_draft], at positions
+ * d_pos[0] .. d_pos[0] + R - 1 of one cache -- through the layer loop of the batched step with B = R (the same teo_gemm_skinny calls and
+ * hand-offs, the per-row GEMV fallback for fp32 / odd K; the weights as teo_decode_batch_state describes them) with teo_attn_verify
+ * as the attention, and produces d_logits [R][vocab].  The tail selects a token behind every row exactly as the decode tail would
+ * (argmax, or the sampler with draw index d_rng[1] + i on the (seed, counter) generator), then:
+ *   a       = the largest number <= *d_n_draft with sel[i] == d_rows[i + 1] for all i < a;
+ *   emitted = sel[0 .. a], cut behind the first token that completes d_stop_ids (suffix of d_out_tokens) or brings *d_out_count to max_new;
+ *   d_out_tokens / d_out_count / d_hist / d_hist_len grow by the emitted tokens, d_pos and d_rng[1] advance by their number,
+ *   d_stats += {1, *d_n_draft, accepted drafts among the emitted}, d_rows[0] = d_token[0] = the last emitted token, d_stop is set on a cut.
+ * Selection is a function of (logits, seed, counter) alone, so the emitted stream is the stream of rows-1-draft-free steps whatever the
+ * drafts were.  Once *d_stop is set a step changes none of these (a graph replay may run past the stop); a step never writes a cache
+ * row at or behind d_pos[0] + R: the caller keeps (position at begin) + max_new + R <= max_seq.  An unused row (i > n_draft) holds the
+ * pending token; its result is ignored.
+ * The proposer (teo_spec_propose; also the last launch of every step, and what teo_llama_verify_begin runs) fills d_rows[1 ..] and
+ * d_n_draft for the next step from the history: for n = ngram_max .. 1 the most recent earlier occurrence of the last n ids of d_hist
+ * that has a following id; the ids behind it are copied, up to R - 1, stopping in front of a negative id (image sentinel) and at the
+ * end of the history; no occurrence for any n: n_draft = 0.  A host that supplies its own drafts overwrites both after each step. */
+typedef struct {
+    int rows;                 /* R: 1..TEO_MAX_DECODE_BATCH */
+    int max_new;              /* capacity of d_out_tokens = most tokens the steps may emit */
+    int ngram_max;            /* longest n-gram the proposer matches (1..8) */
+    int w_tiled, gateup_block8, w_mxfp4;   /* as in teo_decode_batch_state */
+    long long* d_rows;        /* [rows] the pending token, then the drafts (unused rows: the pending token) */
+    int* d_n_draft;           /* [1] 0..rows-1 */
+    long long* d_hist;        /* [>= *d_hist_len at begin + max_new] prompt ids as the caller passed them (sentinels included) + every emitted token */
+    int* d_hist_len;          /* [1] */
+    int* d_stats;             /* [3] {steps, drafts proposed, drafts accepted} */
+    long long* d_token;       /* [1] mirrors d_rows[0] */
+    int* d_pos;               /* [1] position of d_rows[0] == number of tokens in the cache */
+    long long* d_out_tokens;  /* [max_new] */
+    int* d_out_count;         /* [1] */
+    int* d_stop;              /* [1] */
+    const long long* d_stop_ids; int n_stop_ids; /* may be NULL/0 */
+    float* d_logits;          /* [rows][vocab] fp32 logits of the last step */
+    int do_sample; int top_k; float temperature;
+    unsigned long long* d_rng; /* [2] = {seed, draws so far} */
+    float top_p;
+} teo_verify_state;
+size_t teo_llama_verify_workspace_bytes(const teo_llama_desc* d, int rows);
+/* Arm a generation: runs the proposer once (the caller has filled d_rows[0] / d_token, d_pos, d_hist, d_hist_len and zeroed the counters). */
+int teo_llama_verify_begin(const teo_llama_desc* d, const teo_verify_state* st, void* d_workspace, size_t workspace_bytes,
+                           teo_stream_t stream);
+int teo_llama_verify_step(const teo_llama_desc* d, const teo_verify_state* st, void* d_workspace, size_t workspace_bytes,
+                          teo_stream_t stream);
+/* ONE verify step with every launch timed (as teo_llama_decode_batch_step_profile; the embedding of the rows and the select / accept /
+ * propose launches all count as TEO_PROF_TAIL, the verify attention's combine launch as TEO_PROF_ATTN_COMBINE). */
+int teo_llama_verify_step_profile(const teo_llama_desc* d, const teo_verify_state* st, void* d_workspace, size_t workspace_bytes,
+                                  float* ms_out /* [TEO_PROF_CLASSES] */, int* count_out /* [TEO_PROF_CLASSES] */, teo_stream_t stream);
+int teo_llama_verify_graph_create(const teo_llama_desc* d, const teo_verify_state* st, void* d_workspace, size_t workspace_bytes,
+                                  teo_stream_t stream, teo_graph** out);
+/* The proposer alone: d_rows[1 .. rows-1] and *d_n_draft from d_hist[0 .. *d_hist_len) (d_rows[0] is read: the filler of unused rows). */
+int teo_spec_propose(const long long* d_hist, const int* d_hist_len, long long* d_rows, int* d_n_draft, int rows, int ngram_max,
+                     teo_stream_t stream);
 
 /* ---- multi-GPU context and the one collective of the path ---------------------------
  * One process per GPU.  The T-frame tower shards over the ranks (frames are independent through the tower: T is the batch

@@ -93,6 +93,18 @@ class DecodeBatchState(C.Structure):
                 ("top_p", C.c_float)]
 
 
+class VerifyState(C.Structure):
+    _fields_ = [("rows", C.c_int), ("max_new", C.c_int), ("ngram_max", C.c_int), ("w_tiled", C.c_int), ("gateup_block8", C.c_int),
+                ("w_mxfp4", C.c_int),
+                ("d_rows", C.c_void_p), ("d_n_draft", C.c_void_p), ("d_hist", C.c_void_p), ("d_hist_len", C.c_void_p),
+                ("d_stats", C.c_void_p),
+                ("d_token", C.c_void_p), ("d_pos", C.c_void_p), ("d_out_tokens", C.c_void_p),
+                ("d_out_count", C.c_void_p), ("d_stop", C.c_void_p), ("d_stop_ids", C.c_void_p),
+                ("n_stop_ids", C.c_int), ("d_logits", C.c_void_p),
+                ("do_sample", C.c_int), ("top_k", C.c_int), ("temperature", C.c_float), ("d_rng", C.c_void_p),
+                ("top_p", C.c_float)]
+
+
 _SIGS = {
     "teo_version": (C.c_int, []),
     "teo_last_error": (C.c_char_p, []),
@@ -163,11 +175,21 @@ _SIGS = {
                                                       C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_void_p]),
     "teo_llama_decode_batch_graph_create": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeBatchState), C.c_void_p, C.c_size_t,
                                                       C.c_void_p, C.POINTER(C.c_void_p)]),
+    "teo_llama_verify_workspace_bytes": (C.c_size_t, [C.POINTER(LlamaDesc), C.c_int]),
+    "teo_llama_verify_begin": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(VerifyState), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "teo_llama_verify_step": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(VerifyState), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "teo_llama_verify_step_profile": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(VerifyState), C.c_void_p, C.c_size_t,
+                                                C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_void_p]),
+    "teo_llama_verify_graph_create": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(VerifyState), C.c_void_p, C.c_size_t,
+                                                C.c_void_p, C.POINTER(C.c_void_p)]),
+    "teo_spec_propose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "teo_graph_launch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "teo_graph_destroy": (C.c_int, [C.c_void_p]),
     "teo_attn_decode_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "teo_attn_decode": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_int, C.c_longlong, C.c_longlong,
                                                                       C.c_longlong, C.c_void_p]),
+    "teo_attn_verify_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "teo_attn_verify": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_int, C.c_longlong, C.c_void_p]),
     "teo_cross_entropy": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong,
                                     C.c_void_p]),
     "teo_preprocess_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
@@ -224,7 +246,7 @@ def load():
     if lib.teo_version() != ABI_VERSION:
         raise TeoLibraryError(f"ABI version mismatch: library {lib.teo_version()}, binding {ABI_VERSION}; rebuild {LIB_PATH}")
     mirrors = {"teo_vit_desc": VitDesc, "teo_proj_desc": ProjDesc, "teo_llama_desc": LlamaDesc, "teo_decode_state": DecodeState,
-               "teo_decode_batch_state": DecodeBatchState, "teo_attn_args": AttnArgs}
+               "teo_decode_batch_state": DecodeBatchState, "teo_attn_args": AttnArgs, "teo_verify_state": VerifyState}
     for name, cls in mirrors.items():
         want = lib.teo_sizeof(name.encode())
         if want != C.sizeof(cls):

@@ -80,6 +80,13 @@ int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_stat
 int decode_batch_graph_create(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes,
                               hipStream_t st, teo_graph** out);
 
+size_t llama_verify_workspace_bytes(const teo_llama_desc* d, int rows);
+int llama_verify_begin(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, hipStream_t st);
+int llama_verify_step(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, hipStream_t st);
+int llama_verify_step_profile(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, float* ms_out, int* count_out,
+                              hipStream_t st);
+int verify_graph_create(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, hipStream_t st, teo_graph** out);
+
 static bool dtype_ok(int dt) { return dt == TEO_F32 || dt == TEO_BF16 || dt == TEO_F16; }
 
 }  // namespace teo
@@ -167,6 +174,7 @@ size_t teo_sizeof(const char* struct_name) {
     if (!strcmp(struct_name, "teo_decode_state")) return sizeof(teo_decode_state);
     if (!strcmp(struct_name, "teo_decode_batch_state")) return sizeof(teo_decode_batch_state);
     if (!strcmp(struct_name, "teo_attn_args")) return sizeof(teo_attn_args);
+    if (!strcmp(struct_name, "teo_verify_state")) return sizeof(teo_verify_state);
     return 0;
 }
 
@@ -598,6 +606,71 @@ int teo_llama_decode_batch_graph_create(const teo_llama_desc* d, const teo_decod
     return decode_batch_graph_create(d, st, ws, wsb, ST(s), out);
 }
 
+// ---- speculative verify ----
+static int check_verify_state(const teo_llama_desc* d, const teo_verify_state* st) {
+    NEED(d, "desc"); NEED(st, "state"); NEED_DT(d->dtype);
+    TEO_CHECK_ARG(st->rows >= 1 && st->rows <= TEO_MAX_DECODE_BATCH, "verify rows %d outside 1..%d", st->rows, TEO_MAX_DECODE_BATCH);
+    TEO_CHECK_ARG(st->max_new >= 1 && st->ngram_max >= 1 && st->ngram_max <= 8, "verify: max_new %d ngram_max %d (1..8)", st->max_new, st->ngram_max);
+    NEED(st->d_rows, "d_rows"); NEED(st->d_n_draft, "d_n_draft"); NEED(st->d_hist, "d_hist"); NEED(st->d_hist_len, "d_hist_len");
+    NEED(st->d_stats, "d_stats"); NEED(st->d_token, "d_token"); NEED(st->d_pos, "d_pos"); NEED(st->d_out_tokens, "d_out_tokens");
+    NEED(st->d_out_count, "d_out_count"); NEED(st->d_stop, "d_stop"); NEED(st->d_logits, "d_logits");
+    TEO_CHECK_ARG(d->max_seq >= st->rows, "verify: max_seq %d below rows %d", d->max_seq, st->rows);
+    // the rest is the batched step's contract on the same descriptor: sampler, MXFP4 / tiled weights, 4-bit-only descriptors
+    teo_decode_batch_state b;
+    memset(&b, 0, sizeof(b));
+    b.batch = st->rows; b.out_stride = st->max_new; b.cache_stride = 1;
+    b.w_tiled = st->w_tiled; b.gateup_block8 = st->gateup_block8; b.w_mxfp4 = st->w_mxfp4;
+    b.d_token = st->d_rows; b.d_pos = st->d_pos; b.d_out_tokens = st->d_out_tokens; b.d_out_count = st->d_out_count; b.d_stop = st->d_stop;
+    b.d_logits = st->d_logits; b.do_sample = st->do_sample; b.top_k = st->top_k; b.temperature = st->temperature; b.d_rng = st->d_rng;
+    b.top_p = st->top_p;
+    return check_batch_state(d, &b);
+}
+
+size_t teo_llama_verify_workspace_bytes(const teo_llama_desc* d, int rows) {
+    return (d && rows >= 1 && rows <= TEO_MAX_DECODE_BATCH) ? llama_verify_workspace_bytes(d, rows) : 0;
+}
+
+int teo_llama_verify_begin(const teo_llama_desc* d, const teo_verify_state* st, void* ws, size_t wsb, teo_stream_t s) {
+    ENTER();
+    { const int rc = check_verify_state(d, st); if (rc != TEO_OK) return rc; }
+    TuneScope tune_scope(d->tune);
+    NEED(ws, "workspace");
+    return llama_verify_begin(d, st, ws, wsb, ST(s));
+}
+
+int teo_llama_verify_step(const teo_llama_desc* d, const teo_verify_state* st, void* ws, size_t wsb, teo_stream_t s) {
+    ENTER();
+    { const int rc = check_verify_state(d, st); if (rc != TEO_OK) return rc; }
+    TuneScope tune_scope(d->tune);
+    NEED(ws, "workspace");
+    return llama_verify_step(d, st, ws, wsb, ST(s));
+}
+
+int teo_llama_verify_step_profile(const teo_llama_desc* d, const teo_verify_state* st, void* ws, size_t wsb, float* ms_out, int* count_out,
+                                  teo_stream_t s) {
+    ENTER();
+    { const int rc = check_verify_state(d, st); if (rc != TEO_OK) return rc; }
+    TuneScope tune_scope(d->tune);
+    NEED(ws, "workspace"); NEED(ms_out, "ms_out"); NEED(count_out, "count_out");
+    return llama_verify_step_profile(d, st, ws, wsb, ms_out, count_out, ST(s));
+}
+
+int teo_llama_verify_graph_create(const teo_llama_desc* d, const teo_verify_state* st, void* ws, size_t wsb, teo_stream_t s, teo_graph** out) {
+    ENTER();
+    { const int rc = check_verify_state(d, st); if (rc != TEO_OK) return rc; }
+    TuneScope tune_scope(d->tune);
+    NEED(ws, "workspace"); NEED(out, "out");
+    TEO_CHECK_ARG(s != nullptr, "teo_llama_verify_graph_create: needs a non-default stream to capture on");
+    return verify_graph_create(d, st, ws, wsb, ST(s), out);
+}
+
+int teo_spec_propose(const long long* d_hist, const int* d_hist_len, long long* d_rows, int* d_n_draft, int rows, int ngram_max, teo_stream_t s) {
+    ENTER();
+    TEO_CHECK_ARG(rows >= 1 && rows <= TEO_MAX_DECODE_BATCH && ngram_max >= 1 && ngram_max <= 8, "teo_spec_propose: rows %d ngram_max %d", rows, ngram_max);
+    NEED(d_hist, "d_hist"); NEED(d_hist_len, "d_hist_len"); NEED(d_rows, "d_rows"); NEED(d_n_draft, "d_n_draft");
+    return spec_propose(d_hist, d_hist_len, d_rows, d_n_draft, rows, ngram_max, ST(s));
+}
+
 int teo_graph_launch(teo_graph* g, int n_times, teo_stream_t s) {
     ENTER();
     NEED(g, "graph");
@@ -634,6 +707,27 @@ int teo_attn_decode(const void* q, void* k_cache, void* v_cache, void* vt_cache,
     bt.batch = batch; bt.q_stride = q_stride; bt.cache_stride = cache_stride; bt.o_stride = o_stride;
     return attn_decode(q, k_cache, v_cache, vt_cache, rope_cos, rope_sin, out, partials, d_pos, max_seq, heads, kv_heads, head_dim,
                        scale, dtype, ST(s), bt);
+}
+
+size_t teo_attn_verify_workspace_bytes(int heads, int head_dim, int max_seq, int rows) {
+    if (!(heads > 0 && head_dim > 0 && max_seq > 0 && rows > 0)) return 0;
+    return attn_decode_ws_bytes(heads, head_dim, max_seq, rows);
+}
+
+int teo_attn_verify(const void* qkv, void* k_cache, void* v_cache, void* vt_cache, const float* rope_cos, const float* rope_sin,
+                    void* out, float* partials, const int* d_pos, int max_seq, int heads, int kv_heads, int head_dim, float scale,
+                    int dtype, int rows, long long q_stride, teo_stream_t s) {
+    ENTER();
+    NEED_DT(dtype);
+    TEO_CHECK_ARG(rows >= 1 && rows <= TEO_MAX_DECODE_BATCH && heads > 0 && kv_heads > 0 && heads % kv_heads == 0 && max_seq >= rows,
+                  "teo_attn_verify: rows %d (1..%d) heads %d kv_heads %d max_seq %d", rows, TEO_MAX_DECODE_BATCH, heads, kv_heads, max_seq);
+    TEO_CHECK_ARG(head_dim > 0, "teo_attn_verify: head_dim %d", head_dim);
+    NEED(qkv, "qkv"); NEED(k_cache, "k_cache"); NEED(v_cache, "v_cache"); NEED(out, "out"); NEED(partials, "partials"); NEED(d_pos, "d_pos");
+    NEED(rope_cos, "rope_cos"); NEED(rope_sin, "rope_sin");
+    TEO_CHECK_ARG(q_stride >= (long long)(heads + 2 * kv_heads) * head_dim && q_stride % (dtype == TEO_F32 ? 4 : 8) == 0,
+                  "teo_attn_verify: q_stride %lld (whole [q|k|v] rows, 16-byte aligned)", q_stride);
+    return attn_verify(qkv, k_cache, v_cache, vt_cache, rope_cos, rope_sin, out, partials, d_pos, max_seq, heads, kv_heads, head_dim,
+                       scale, dtype, rows, q_stride, ST(s));
 }
 
 int teo_cross_entropy(const float* logits, long long ld, const long long* labels, float* loss_row, float* out, int rows, int vocab,

@@ -6,6 +6,9 @@
 //  attn_decode_*           : q_len == 1 (decode).  Split over the KV length (grid heads x splits, fixed for hipGraph
 //                            replay; kv_len comes from device memory), then a combine kernel.  HBM-bound:
 //                            algorithmic bytes = 2 * kv_heads * kv_len * head_dim * sizeof(T) per layer.
+//  attn_verify_*           : R <= 16 new rows of ONE conversation at consecutive positions (speculative verify): the decode kernel's
+//                            arithmetic with the row loop inside the workgroup -- the cache is streamed once for all rows; bit-identical
+//                            to attn_decode(batch = R) on staggered copies of the conversation.
 #include "common.h"
 #include "ops.h"
 
@@ -775,44 +778,65 @@ static int attn_whole_launch(const void* q, void* kc, void* vc, void* vtc, const
 #undef TEO_AWL
 }
 
+// The geometry attn_decode() runs a step of `batch` conversations with: keys per split record (`chunk`, `nsplit` records per head) of the
+// split + combine pair, and whether the whole-context form runs instead (`whole`, then with `cw` keys per record).  One rule, read by
+// attn_decode and by attn_verify (which must form the records attn_decode would): tune().attn_chunk / attn_whole move both.
+struct AttnDecodePlan {
+    int lpr, chunk, nsplit;
+    bool ok;                       // the split pair takes the shape
+    bool whole;                    // the whole-context form takes the step
+    int cw;
+    size_t lds_whole;
+};
+static AttnDecodePlan attn_decode_plan(int batch, int heads, int hd, int S_max, int dtype) {
+    AttnDecodePlan p;
+    int chunk = tune().attn_chunk ? tune().attn_chunk : (batch > 1 ? 128 : 64);
+    const int esz = dtype == TEO_F32 ? 4 : 2;
+    const int lpr = hd * esz / 16;
+    if (chunk / 4 < 64 / lpr) chunk = 4 * (64 / lpr);          // every wave needs at least one load instruction of keys
+    if (chunk != 32 && chunk != 64 && chunk != 128 && chunk != 256) chunk = 128;
+    while (chunk < 256 && cdiv(S_max, chunk) > 256) chunk *= 2;        // the combine handles at most 256 splits
+    p.lpr = lpr; p.chunk = chunk; p.nsplit = cdiv(S_max, chunk);
+    p.ok = !(p.nsplit > 256 || (hd * esz) % 16 != 0 || (lpr != 2 && lpr != 4 && lpr != 8 && lpr != 16 && lpr != 32));
+    p.whole = false; p.cw = 0; p.lds_whole = 0;
+    if (!p.ok) return p;
+    // whole-context form (batched steps with at least one workgroup per CU: B >= 8 at 32 heads; with the reductions on DPP the split form
+    // wins below that -- B = 4: 30.1 vs 31.8 us, profiles/r04_attn_probe_b4.txt).  Its default chunk is 64 keys (quarter-chunks of 4 load instructions: a 4-slot ring of 64
+    // VGPRs; with 128-key chunks the bf16 / head_dim 128 kernel needs more than 256 registers), "attn_chunk" forces another.
+    int cw = tune().attn_chunk ? tune().attn_chunk : 64;
+    if (cw / 4 < 64 / lpr) cw = 4 * (64 / lpr);
+    while (cw < 128 && cdiv(S_max, cw) > 256) cw *= 2;
+    const int nsw = cdiv(S_max, cw);
+    const int ni = cw / 4 / (64 / lpr);
+    const size_t lds = ((size_t)8 * cw + (size_t)nsw * (hd + 2) + 784) * sizeof(float);
+    const int cus = device_cu_count();
+    const bool fits = ni >= 1 && ni <= 8 && (hd & (hd - 1)) == 0 && hd <= 256 && lds <= 96 * 1024 && nsw <= 256 && (cw == 32 || cw == 64 || cw == 128);
+    // one workgroup per (conversation, head): whole rounds of the CUs only -- with 9..13 conversations x 32 heads the CUs that get a second
+    // workgroup finish 1.3x later than the rest and the split form wins (B = 9: 4.45 vs 4.85 ms per step, B = 10: 4.55 vs 4.99,
+    // B = 13: 5.25 vs 5.34; from 7/4 rounds on the imbalance amortises: B = 14: 5.52 vs 5.56; profiles/r06_batch_sweep_attn_{whole,split}.md)
+    const int ncu = cus > 0 ? cus : 256, wgs = batch * heads;
+    const bool balanced = wgs >= ncu && (wgs % ncu == 0 || 4 * wgs >= 7 * ncu);
+    // (the whole-context kernel is built for 4..32 lanes per row)
+    p.whole = fits && lpr >= 4 && (tune().attn_whole == 2 || (tune().attn_whole == 1 && batch > 1 && balanced));
+    p.cw = cw; p.lds_whole = lds;
+    return p;
+}
+
 // rope_cos != NULL: q is the raw qkv row; RoPE and the KV append of the new token happen inside the kernel
 // bt: batched step (bt.batch conversations: q/o rows, caches, positions and partial slabs strided per conversation)
 int attn_decode(const void* q, void* kc, void* vc, void* vtc, const float* rope_cos, const float* rope_sin, void* o,
                 float* part, const int* d_pos, int S_max, int heads, int kv_heads, int hd, float scale, int dtype,
                 hipStream_t st, AttnBatch bt) {
     const bool rope = rope_cos != nullptr;
-    int chunk = tune().attn_chunk ? tune().attn_chunk : (bt.batch > 1 ? 128 : 64);
-    const int esz = dtype == TEO_F32 ? 4 : 2;
-    const int lpr = hd * esz / 16;
-    if (chunk / 4 < 64 / lpr) chunk = 4 * (64 / lpr);          // every wave needs at least one load instruction of keys
-    if (chunk != 32 && chunk != 64 && chunk != 128 && chunk != 256) chunk = 128;
-    while (chunk < 256 && cdiv(S_max, chunk) > 256) chunk *= 2;        // the combine handles at most 256 splits
-    const int nsplit = cdiv(S_max, chunk);
-    if (nsplit > 256 || (hd * esz) % 16 != 0 || (lpr != 2 && lpr != 4 && lpr != 8 && lpr != 16 && lpr != 32)) {
+    const AttnDecodePlan pl = attn_decode_plan(bt.batch, heads, hd, S_max, dtype);
+    const int lpr = pl.lpr, chunk = pl.chunk, nsplit = pl.nsplit;
+    if (!pl.ok) {
         set_error("attn_decode: unsupported head_dim %d / max_seq %d", hd, S_max);
         return TEO_ERR_UNSUPPORTED;
     }
-    // whole-context form (batched steps with at least one workgroup per CU: B >= 8 at 32 heads; with the reductions on DPP the split form
-    // wins below that -- B = 4: 30.1 vs 31.8 us, profiles/r04_attn_probe_b4.txt).  Its default chunk is 64 keys (quarter-chunks of 4 load instructions: a 4-slot ring of 64
-    // VGPRs; with 128-key chunks the bf16 / head_dim 128 kernel needs more than 256 registers), "attn_chunk" forces another.
-    {
-        int cw = tune().attn_chunk ? tune().attn_chunk : 64;
-        if (cw / 4 < 64 / lpr) cw = 4 * (64 / lpr);
-        while (cw < 128 && cdiv(S_max, cw) > 256) cw *= 2;
-        const int nsw = cdiv(S_max, cw);
-        const int ni = cw / 4 / (64 / lpr);
-        const size_t lds = ((size_t)8 * cw + (size_t)nsw * (hd + 2) + 784) * sizeof(float);
-        const int cus = device_cu_count();
-        const bool fits = ni >= 1 && ni <= 8 && (hd & (hd - 1)) == 0 && hd <= 256 && lds <= 96 * 1024 && nsw <= 256 && (cw == 32 || cw == 64 || cw == 128);
-        // one workgroup per (conversation, head): whole rounds of the CUs only -- with 9..13 conversations x 32 heads the CUs that get a second
-        // workgroup finish 1.3x later than the rest and the split form wins (B = 9: 4.45 vs 4.85 ms per step, B = 10: 4.55 vs 4.99,
-        // B = 13: 5.25 vs 5.34; from 7/4 rounds on the imbalance amortises: B = 14: 5.52 vs 5.56; profiles/r06_batch_sweep_attn_{whole,split}.md)
-        const int ncu = cus > 0 ? cus : 256, wgs = bt.batch * heads;
-        const bool balanced = wgs >= ncu && (wgs % ncu == 0 || 4 * wgs >= 7 * ncu);
-        if (fits && (tune().attn_whole == 2 || (tune().attn_whole == 1 && bt.batch > 1 && balanced))) {
-            const int rcw = attn_whole_launch(q, kc, vc, vtc, rope_cos, rope_sin, o, d_pos, S_max, heads, kv_heads, hd, scale, cw, lpr, dtype, bt, lds, st);
-            if (rcw != TEO_ERR_UNSUPPORTED) return rcw;
-        }
+    if (pl.whole) {
+        const int rcw = attn_whole_launch(q, kc, vc, vtc, rope_cos, rope_sin, o, d_pos, S_max, heads, kv_heads, hd, scale, pl.cw, lpr, dtype, bt, pl.lds_whole, st);
+        if (rcw != TEO_ERR_UNSUPPORTED) return rcw;
     }
 #define TEO_DEC(TT, LL) attn_decode_launch<TT, LL>(q, kc, vc, vtc, rope_cos, rope_sin, o, part, d_pos, S_max, heads, kv_heads, hd, scale, nsplit, chunk, rope, bt, st)
     if (dtype == TEO_F32) {
@@ -827,6 +851,255 @@ int attn_decode(const void* q, void* kc, void* vc, void* vtc, const float* rope_
     }
 #undef TEO_DEC
     TEO_LAUNCH_CHECK("attn_decode");
+    return TEO_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// verify: R new rows of ONE conversation at consecutive positions pos .. pos+R-1 (speculative decoding: the pending token and
+// R-1 drafts), attended causally -- row r sees keys 0 .. pos+r.  The contract is bit-identity with attn_decode(batch = R, rope) on R
+// staggered copies of the conversation (copy r at position pos+r, its cache holding the earlier rows as they would have been
+// appended), so the kernel is attn_decode_partial_kernel's arithmetic with the row loop moved inside the workgroup:
+//   * grid (heads, nsplit) with attn_decode_plan(R)'s chunk: a workgroup loads its chunk of cached K and V ONCE (clamped to row
+//     pos-1, the last row that is not written by this launch) and keeps it in registers for all R rows -- R launches of the decode
+//     kernel would stream the cache R times;
+//   * the rotated queries, and the rotated keys / values of the new rows, are built once per workgroup in LDS (the storage type:
+//     exactly what the staggered copies would have found in their caches); keys >= pos come from there, never from the cache;
+//   * per row: the decode kernel's score expression, chunk max / exp / sum, per-wave partial PV sums added in its order -> the same
+//     (m, l, o[hd]) record; records [R][heads][nsplit], merged per (row, head) by attn_merge_records.
+// VALU like the decode kernel: the MFMA forms sum a dot product in another order (4 x 8-element blocks across lanes' k groups) than
+// v_dot2 chains + the xor-shuffle tree, so they cannot reproduce its bits.
+// The workgroup whose chunk holds key `pos` appends the R rows (K, V, V^T), once per kv head.
+// ------------------------------------------------------------------------------------------------
+template <typename T, int LPR, int DEC_CHUNK>
+__global__ __launch_bounds__(256) void attn_verify_partial_kernel(const int* __restrict__ d_pos, T* __restrict__ kc, T* __restrict__ vc,
+                                                                  const T* __restrict__ qkv, int S_max, int heads, int kv_heads, int nsplit,
+                                                                  T* __restrict__ vtc, const float* __restrict__ cs,
+                                                                  const float* __restrict__ sn, float* __restrict__ part, float scale,
+                                                                  int rows, long long q_stride) {
+    constexpr int VE = Cvt16<T>::N;
+    constexpr int HD = LPR * VE;
+    constexpr int RPI = 64 / LPR;                       // rows (keys) per wave-wide load instruction
+    constexpr int KPW = DEC_CHUNK / 4;                  // keys per wave
+    constexpr int NI = KPW / RPI;                       // load instructions per wave per operand
+    constexpr int MAXR = TEO_MAX_DECODE_BATCH;
+    const int pos = d_pos[0];                           // keys 0 .. pos-1 are cached
+    __shared__ float sc[DEC_CHUNK];
+    __shared__ float pstrip[4][DEC_CHUNK];
+    __shared__ float obuf[4][HD];
+    __shared__ uint4 qrot[MAXR][LPR], knew[MAXR][LPR], vnew[MAXR][LPR];
+    const int h = blockIdx.x, sp = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int gq = heads / kv_heads;
+    const int hk = h / gq;
+    const int c0 = sp * DEC_CHUNK;
+    const int nr = min(rows, S_max - pos);              // rows that have a cache position (the caller keeps pos + rows <= max_seq)
+    // rows whose context ends in front of this chunk: neutral records
+    for (int r = 0; r < rows; ++r) {
+        if (r < nr && c0 < pos + r + 1) continue;
+        float* out = part + (((long long)r * heads + h) * nsplit + sp) * (HD + 2);
+        if (tid == 0) { out[0] = -INFINITY; out[1] = 0.f; }
+        for (int d = tid; d < HD; d += 256) out[2 + d] = 0.f;
+    }
+    if (c0 >= pos + nr) return;
+    const int sub = lane % LPR, grp = lane / LPR;
+    const T* kb = kc + (long long)hk * S_max * HD + sub * VE;
+    const T* vb = vc + (long long)hk * S_max * HD + sub * VE;
+    const int kw0 = c0 + wid * KPW;                     // first key of this wave
+    uint4 kr[NI], vr[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) { kr[i] = make_uint4(0, 0, 0, 0); vr[i] = make_uint4(0, 0, 0, 0); }
+    if (pos > 0 && c0 < pos) {                          // rows >= pos are written by this launch: never loaded
+#pragma unroll
+        for (int i = 0; i < NI; ++i) kr[i] = ld_kv(kb + (long long)min(kw0 + i * RPI + grp, pos - 1) * HD);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) vr[i] = ld_kv(vb + (long long)min(kw0 + i * RPI + grp, pos - 1) * HD);
+    }
+    // ---- rotated q of every row; rotated k and v of the new rows when this chunk reaches them
+    const bool has_new = c0 + DEC_CHUNK > pos;
+    for (int idx = tid; idx < nr * LPR; idx += 256) {
+        const int r = idx / LPR, s_ = idx % LPR, p_ = pos + r;
+        const T* row = qkv + (long long)r * q_stride;
+        constexpr int HL = LPR / 2;
+        const int psub = s_ ^ HL, ci = (s_ % HL) * VE;
+        const float sgn = (s_ < HL) ? -1.f : 1.f;
+        float cf[VE], sf[VE];
+#pragma unroll
+        for (int e = 0; e < VE; e += 4) {
+            const float4 c4 = *reinterpret_cast<const float4*>(cs + (long long)p_ * (HD / 2) + ci + e);
+            const float4 s4 = *reinterpret_cast<const float4*>(sn + (long long)p_ * (HD / 2) + ci + e);
+            cf[e] = c4.x; cf[e + 1] = c4.y; cf[e + 2] = c4.z; cf[e + 3] = c4.w;
+            sf[e] = s4.x; sf[e + 1] = s4.y; sf[e + 2] = s4.z; sf[e + 3] = s4.w;
+        }
+        float own[VE], oth[VE], rot[VE];
+        Cvt16<T>::cvt(*reinterpret_cast<const uint4*>(row + h * HD + s_ * VE), own);
+        Cvt16<T>::cvt(*reinterpret_cast<const uint4*>(row + h * HD + psub * VE), oth);
+#pragma unroll
+        for (int e = 0; e < VE; ++e) rot[e] = Elem<T>::round(own[e] * cf[e] + sgn * oth[e] * sf[e]);
+        qrot[r][s_] = Cvt16<T>::pack(rot);              // exact: the values are already rounded to T
+        if (has_new) {
+            const T* kraw = row + (long long)(heads + hk) * HD;
+            Cvt16<T>::cvt(*reinterpret_cast<const uint4*>(kraw + s_ * VE), own);
+            Cvt16<T>::cvt(*reinterpret_cast<const uint4*>(kraw + psub * VE), oth);
+#pragma unroll
+            for (int e = 0; e < VE; ++e) rot[e] = Elem<T>::round(own[e] * cf[e] + sgn * oth[e] * sf[e]);
+            knew[r][s_] = Cvt16<T>::pack(rot);
+            vnew[r][s_] = *reinterpret_cast<const uint4*>(row + (long long)(heads + kv_heads + hk) * HD + s_ * VE);
+        }
+    }
+    __syncthreads();
+    // ---- KV append of the R rows: the workgroup of key `pos`, one q head per kv head
+    if (c0 <= pos && pos < c0 + DEC_CHUNK && h % gq == 0) {
+        for (int idx = tid; idx < nr * LPR; idx += 256) {
+            const int r = idx / LPR, s_ = idx % LPR;
+            const long long p_ = pos + r;
+            *reinterpret_cast<uint4*>(kc + ((long long)hk * S_max + p_) * HD + s_ * VE) = knew[r][s_];
+            const uint4 pv = vnew[r][s_];
+            *reinterpret_cast<uint4*>(vc + ((long long)hk * S_max + p_) * HD + s_ * VE) = pv;
+            if (vtc) {
+                const T* pe = reinterpret_cast<const T*>(&pv);
+#pragma unroll
+                for (int e = 0; e < VE; ++e) vtc[((long long)hk * HD + s_ * VE + e) * S_max + p_] = pe[e];
+            }
+        }
+    }
+    constexpr bool DOT2 = sizeof(T) == 2;
+    constexpr int SPL = (DEC_CHUNK + 63) / 64;
+    for (int r = 0; r < nr; ++r) {
+        const int kv_len = pos + r + 1;                 // row r sees keys 0 .. pos + r
+        if (c0 >= kv_len) continue;                     // (uniform; its neutral record is written above)
+        const uint4 qpk = qrot[r][sub];
+        float qf[VE];
+        Cvt16<T>::cvt(qpk, qf);
+        // ---- scores
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int j = kw0 + i * RPI + grp;
+            uint4 kraw = kr[i];
+            if (j >= pos && j < kv_len) kraw = knew[j - pos][sub];      // a new row's key: LDS, not the cache
+            float s = 0.f;
+            if (DOT2) {
+                s = attn_dot2(kraw.x, qpk.x, s); s = attn_dot2(kraw.y, qpk.y, s);
+                s = attn_dot2(kraw.z, qpk.z, s); s = attn_dot2(kraw.w, qpk.w, s);
+            } else {
+                float kf[VE];
+                Cvt16<T>::cvt(kraw, kf);
+#pragma unroll
+                for (int e = 0; e < VE; ++e) s = fmaf(qf[e], kf[e], s);
+            }
+            s = group_sum<LPR>(s);
+            if (sub == 0) sc[j - c0] = (j < kv_len) ? s * scale : -INFINITY;
+        }
+        __syncthreads();
+        // ---- chunk max / exp / sum (the decode kernel's expressions)
+        float sv[SPL];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < SPL; ++i) {
+            sv[i] = (DEC_CHUNK >= 64 || lane + 64 * i < DEC_CHUNK) ? sc[(lane + 64 * i) % DEC_CHUNK] : -INFINITY;
+            mx = fmaxf(mx, sv[i]);
+        }
+        mx = wave_max(mx);
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < SPL; ++i) { sv[i] = expf(sv[i] - mx); sum += sv[i]; }      // -inf -> 0
+        sum = wave_sum(sum);
+#pragma unroll
+        for (int i = 0; i < SPL; ++i)
+            if (DEC_CHUNK >= 64 || lane + 64 * i < DEC_CHUNK) pstrip[wid][lane + 64 * i] = Elem<T>::round(sv[i]);
+        // ---- PV on this wave's keys
+        float acc[VE];
+#pragma unroll
+        for (int e = 0; e < VE; ++e) acc[e] = 0.f;
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int j = kw0 + i * RPI + grp;
+            const float p = pstrip[wid][wid * KPW + i * RPI + grp];      // 0 for keys >= kv_len
+            uint4 vraw = vr[i];
+            // keys >= pos: the new rows' values; keys behind the row's own take its value too (p = 0: what the decode kernel multiplies by 0)
+            if (j >= pos) vraw = vnew[min(j, kv_len - 1) - pos][sub];
+            float vf[VE];
+            Cvt16<T>::cvt(vraw, vf);
+#pragma unroll
+            for (int e = 0; e < VE; ++e) acc[e] = fmaf(p, vf[e], acc[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < VE; ++e) acc[e] = cross_group_sum<LPR>(acc[e]);
+        if (grp == 0) {
+#pragma unroll
+            for (int e = 0; e < VE; ++e) obuf[wid][sub * VE + e] = acc[e];
+        }
+        __syncthreads();
+        float* out = part + (((long long)r * heads + h) * nsplit + sp) * (HD + 2);
+        for (int d = tid; d < HD; d += 256) out[2 + d] = obuf[0][d] + obuf[1][d] + obuf[2][d] + obuf[3][d];
+        if (tid == 0) { out[0] = mx; out[1] = sum; }
+    }
+}
+
+// one workgroup (512 threads) per (head, row): attn_decode_combine_kernel with the row's position pos + r
+template <typename T>
+__global__ __launch_bounds__(512) void attn_verify_combine_kernel(const int* __restrict__ d_pos, const float* __restrict__ part,
+                                                                  T* __restrict__ o, int hd_log2, int nsplit, int chunk_log2) {
+    __shared__ float w[256];
+    __shared__ float red[16];
+    __shared__ float accs[512];
+    const int pos = d_pos[0] + blockIdx.y;
+    const int h = blockIdx.x;
+    const int hd = 1 << hd_log2;
+    const int stride = hd + 2;
+    const float* pb = part + ((long long)blockIdx.y * gridDim.x + h) * nsplit * stride;
+    const int nact = min(nsplit, (pos + (1 << chunk_log2)) >> chunk_log2);  // splits that hold keys (<= 256)
+    attn_merge_records<T>(pb, stride, nact, hd_log2, o + ((long long)blockIdx.y * gridDim.x + h) * hd, w, red, accs);
+}
+
+template <typename T, int LPR>
+static void attn_verify_launch(const void* qkv, void* kc, void* vc, void* vtc, const float* cs, const float* sn, void* o, float* part,
+                               const int* d_pos, int S_max, int heads, int kv_heads, int hd, float scale, int nsplit, int chunk, int rows,
+                               long long q_stride, hipStream_t st) {
+    dim3 grid(heads, nsplit);
+#define TEO_VPART(CH)                                                                                                  \
+    TEO_KLAUNCH((attn_verify_partial_kernel<T, LPR, CH>), grid, 256, 0, st, d_pos, (T*)kc, (T*)vc, (const T*)qkv, S_max, heads, kv_heads, \
+                nsplit, (T*)vtc, cs, sn, part, scale, rows, q_stride)
+    if constexpr (32 / 4 >= 64 / LPR) {
+        if (chunk == 32) { TEO_VPART(32); } else if (chunk == 64) { TEO_VPART(64); } else if (chunk == 256) { TEO_VPART(256); } else { TEO_VPART(128); }
+    } else if constexpr (64 / 4 >= 64 / LPR) {
+        if (chunk == 64) { TEO_VPART(64); } else if (chunk == 256) { TEO_VPART(256); } else { TEO_VPART(128); }
+    } else {
+        if (chunk == 256) { TEO_VPART(256); } else { TEO_VPART(128); }
+    }
+#undef TEO_VPART
+    prof_bump(1);
+    TEO_KLAUNCH((attn_verify_combine_kernel<T>), dim3(heads, rows), 512, 0, st, d_pos, part, (T*)o, __builtin_ctz((unsigned)hd), nsplit,
+                __builtin_ctz((unsigned)chunk));
+    prof_bump(-1);
+}
+
+// qkv: `rows` raw [q | k | v] rows (stride q_stride elements) of one conversation at positions d_pos[0] .. d_pos[0] + rows - 1;
+// o: [rows][heads * hd]; part: attn_decode_ws_bytes(heads, hd, S_max, rows)
+int attn_verify(const void* qkv, void* kc, void* vc, void* vtc, const float* rope_cos, const float* rope_sin, void* o, float* part,
+                const int* d_pos, int S_max, int heads, int kv_heads, int hd, float scale, int dtype, int rows, long long q_stride,
+                hipStream_t st) {
+    const AttnDecodePlan pl = attn_decode_plan(rows, heads, hd, S_max, dtype);
+    if (!pl.ok) {
+        set_error("attn_verify: unsupported head_dim %d / max_seq %d", hd, S_max);
+        return TEO_ERR_UNSUPPORTED;
+    }
+    // the records attn_decode(batch = rows) forms: the whole-context form's chunk where it would take the step
+    const int chunk = pl.whole ? pl.cw : pl.chunk;
+    const int nsplit = cdiv(S_max, chunk);
+#define TEO_VER(TT, LL) attn_verify_launch<TT, LL>(qkv, kc, vc, vtc, rope_cos, rope_sin, o, part, d_pos, S_max, heads, kv_heads, hd, scale, nsplit, chunk, rows, q_stride, st)
+    if (dtype == TEO_F32) {
+        switch (pl.lpr) { case 2: TEO_VER(float, 2); break; case 4: TEO_VER(float, 4); break; case 8: TEO_VER(float, 8); break;
+                          case 16: TEO_VER(float, 16); break; default: TEO_VER(float, 32); }
+    } else if (dtype == TEO_F16) {
+        switch (pl.lpr) { case 2: TEO_VER(f16_t, 2); break; case 4: TEO_VER(f16_t, 4); break; case 8: TEO_VER(f16_t, 8); break;
+                          case 16: TEO_VER(f16_t, 16); break; default: TEO_VER(f16_t, 32); }
+    } else {
+        switch (pl.lpr) { case 2: TEO_VER(bf16_t, 2); break; case 4: TEO_VER(bf16_t, 4); break; case 8: TEO_VER(bf16_t, 8); break;
+                          case 16: TEO_VER(bf16_t, 16); break; default: TEO_VER(bf16_t, 32); }
+    }
+#undef TEO_VER
+    note_kernel("attn_verify");
+    TEO_LAUNCH_CHECK("attn_verify");
     return TEO_OK;
 }
 

@@ -886,6 +886,138 @@ int embed_token(const long long* tok, const void* embed, void* h, int dim, int d
     return TEO_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// speculative verify: tail of a verify step (include/teo_hip.h teo_verify_state) and the n-gram proposer
+// ------------------------------------------------------------------------------------------------
+// one workgroup per row: the token the decode tail would select behind that row -- its argmax (first index on ties), or its sampler with
+// draw index d_rng[1] + row
+__global__ __launch_bounds__(1024) void verify_select_kernel(const float* __restrict__ logits, int vocab, teo_verify_state st,
+                                                             long long* __restrict__ sel) {
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    __shared__ __attribute__((aligned(16))) unsigned hist[256];
+    __shared__ int sel_idx[TOPK_CAP];
+    __shared__ float sel_val[TOPK_CAP];
+    __shared__ int s_misc[4];
+    const int row = blockIdx.x;
+    logits += (long long)row * vocab;
+    if (st.do_sample) {
+        const int pick = sample_topk_block(logits, vocab, st.temperature, st.top_k, st.top_p, uniform01(st.d_rng[0], st.d_rng[1] + row), hist,
+                                           sel_idx, sel_val, s_misc);
+        if (threadIdx.x == 0) sel[row] = pick;
+        return;
+    }
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    const int nv4 = vocab >> 2;
+    const float4* l4 = reinterpret_cast<const float4*>(logits);
+    for (int i = threadIdx.x; i < nv4; i += 1024) {
+        const float4 v = l4[i];
+        const int b = i << 2;
+        if (v.x > best || bi == 0x7fffffff) { best = v.x; bi = b; }
+        if (v.y > best) { best = v.y; bi = b + 1; }
+        if (v.z > best) { best = v.z; bi = b + 2; }
+        if (v.w > best) { best = v.w; bi = b + 3; }
+    }
+    for (int i = (nv4 << 2) + threadIdx.x; i < vocab; i += 1024) {
+        const float v = logits[i];
+        if (v > best || bi == 0x7fffffff) { best = v; bi = i; }
+    }
+    wave_argmax(best, bi);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sv[w] = best; si[w] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 16; ++k)
+            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
+        sel[row] = bi;
+    }
+}
+
+// acceptance + state update, one thread (at most 16 rows): the rule of teochat_amd/speculative.py::accept_run
+__global__ void verify_accept_kernel(teo_verify_state st, const long long* __restrict__ sel) {
+    if (threadIdx.x != 0 || *st.d_stop) return;
+    const int n_draft = min(max(*st.d_n_draft, 0), st.rows - 1);
+    int a = 0;
+    while (a < n_draft && sel[a] == st.d_rows[a + 1]) ++a;
+    int n = *st.d_out_count, hl = *st.d_hist_len, emitted = 0;
+    bool stop = false;
+    long long last = st.d_rows[0];
+    for (int i = 0; i <= a; ++i) {
+        if (n >= st.max_new) { stop = true; break; }
+        last = sel[i];
+        st.d_out_tokens[n] = last;
+        st.d_hist[hl++] = last;
+        ++n; ++emitted;
+        if (st.d_stop_ids && st.n_stop_ids > 0 && n >= st.n_stop_ids) {
+            bool eq = true;
+            for (int k = 0; k < st.n_stop_ids; ++k) eq = eq && (st.d_out_tokens[n - st.n_stop_ids + k] == st.d_stop_ids[k]);
+            if (eq) { stop = true; break; }
+        }
+        if (n >= st.max_new) { stop = true; break; }
+    }
+    *st.d_out_count = n;
+    *st.d_hist_len = hl;
+    *st.d_pos = *st.d_pos + emitted;
+    if (st.do_sample) st.d_rng[1] += (unsigned long long)emitted;
+    st.d_stats[0] += 1; st.d_stats[1] += n_draft; st.d_stats[2] += min(emitted, a);
+    st.d_rows[0] = last;
+    *st.d_token = last;
+    if (stop) *st.d_stop = 1;
+}
+
+// n-gram proposer, one workgroup of 256 threads: teochat_amd/speculative.py::propose_ngram on the device
+__global__ __launch_bounds__(256) void spec_propose_kernel(const long long* __restrict__ hist, const int* __restrict__ d_hist_len,
+                                                           long long* __restrict__ rows_out, int* __restrict__ d_n_draft, int rows,
+                                                           int ngram_max) {
+    __shared__ int s_best;
+    const int hl = *d_hist_len;
+    int start = -1, nn = 0;
+    for (int n = ngram_max; n >= 1; --n) {
+        if (hl < n + 1) continue;
+        if (threadIdx.x == 0) s_best = -1;
+        __syncthreads();
+        int mine = -1;
+        for (int s = threadIdx.x; s <= hl - n - 1; s += 256) {              // s + n <= hl - 1: a following id exists
+            bool eq = true;
+            for (int k = 0; k < n; ++k) eq = eq && (hist[s + k] == hist[hl - n + k]);
+            if (eq) mine = s;                                               // ascending per thread: the last hit is its most recent
+        }
+        if (mine >= 0) atomicMax(&s_best, mine);
+        __syncthreads();
+        const int b = s_best;
+        __syncthreads();
+        if (b >= 0) { start = b; nn = n; break; }
+    }
+    if (threadIdx.x == 0) {
+        const long long fill = rows_out[0];
+        int nd = 0;
+        if (start >= 0) {
+            for (int i = 0; i < rows - 1; ++i) {
+                const int j = start + nn + i;
+                if (j >= hl || hist[j] < 0) break;
+                rows_out[1 + nd++] = hist[j];
+            }
+        }
+        for (int i = nd; i < rows - 1; ++i) rows_out[1 + i] = fill;
+        *d_n_draft = nd;
+    }
+}
+
+int spec_propose(const long long* hist, const int* d_hist_len, long long* rows_out, int* d_n_draft, int rows, int ngram_max, hipStream_t st) {
+    TEO_KLAUNCH(spec_propose_kernel, 1, 256, 0, st, hist, d_hist_len, rows_out, d_n_draft, rows, ngram_max);
+    TEO_LAUNCH_CHECK("spec_propose");
+    return TEO_OK;
+}
+
+// select (one workgroup per row) -> accept / advance (one thread) -> propose the next step's drafts; sel: [rows] scratch
+int verify_tail(const float* logits, const teo_verify_state* s, long long* sel, int vocab, hipStream_t st) {
+    TEO_KLAUNCH(verify_select_kernel, s->rows, 1024, 0, st, logits, vocab, *s, sel);
+    TEO_KLAUNCH(verify_accept_kernel, 1, 64, 0, st, *s, (const long long*)sel);
+    TEO_LAUNCH_CHECK("verify_tail");
+    return spec_propose(s->d_hist, s->d_hist_len, s->d_rows, s->d_n_draft, s->rows, s->ngram_max, st);
+}
+
 // ---- training-shape loss: CrossEntropyLoss(ignore_index) of LlamaForCausalLM.forward with labels
 // (the call at videollava/model/language_model/llava_llama.py:88-99).  One workgroup per row: max, log-sum-exp, picked
 // logit -> loss_row[r] (0 for ignored rows); a single workgroup then sums rows and counts in a fixed order (deterministic).

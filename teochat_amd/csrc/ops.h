@@ -32,6 +32,12 @@ int attn_decode(const void* q, void* kc, void* vc, void* vtc, const float* rope_
                 float* part, const int* d_pos, int S_max, int heads, int kv_heads, int hd, float scale, int dtype,
                 hipStream_t st, AttnBatch bt = AttnBatch());
 
+// `rows` new rows of ONE conversation at positions d_pos[0] .. d_pos[0] + rows - 1 (speculative verify): RoPE, KV append and causal attention,
+// the cache streamed once; every row and every cache row bit-identical to attn_decode(batch = rows) on staggered copies (attention.hip)
+int attn_verify(const void* qkv, void* kc, void* vc, void* vtc, const float* rope_cos, const float* rope_sin, void* o, float* part,
+                const int* d_pos, int S_max, int heads, int kv_heads, int hd, float scale, int dtype, int rows, long long q_stride,
+                hipStream_t st);
+
 int rope_kv_append(void* qkv, int ld, const int* positions, const float* cs, const float* sn, void* kc, void* vc,
                    void* vtc, int S, int past, const int* d_past, int S_max, int heads, int kv_heads, int hd, int dtype,
                    hipStream_t st);
@@ -49,6 +55,9 @@ int sample_topk(const float* logits, long long* tok, int vocab, float temperatur
 int decode_tail(const float* logits, const teo_decode_state* s, const void* embed, void* h, int vocab, int dim, int dtype,
                 hipStream_t st, int batch = 1, int out_stride = 0, const void* g0 = nullptr, void* hg = nullptr,
                 float* ssq = nullptr, int nparts = 0);
+// speculative verify (include/teo_hip.h teo_verify_state): the step's tail and the n-gram proposer
+int verify_tail(const float* logits, const teo_verify_state* s, long long* sel, int vocab, hipStream_t st);
+int spec_propose(const long long* hist, const int* d_hist_len, long long* rows_out, int* d_n_draft, int rows, int ngram_max, hipStream_t st);
 int embed_token(const long long* tok, const void* embed, void* h, int dim, int dtype, hipStream_t st, int batch = 1);
 int embed_token_emit(const long long* tok, const void* embed, void* h, int dim, int dtype, hipStream_t st, int batch,
                      const void* g, void* hg, float* ssq, int nparts);

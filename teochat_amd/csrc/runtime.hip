@@ -567,29 +567,28 @@ int llama_decode_batch_begin(const teo_llama_desc* d, const teo_decode_batch_sta
     return embed_token(s->d_token, d->embed, w.h, d->hidden, d->dtype, st, s->batch);
 }
 
-int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
-    const int B = s->batch;
-    const DecodeBatchWs w = decode_batch_carve(d, B, ws, ws_bytes);
-    if (w.total > ws_bytes) {
-        set_error("teo_llama_decode_batch_step: workspace %zu < %zu", ws_bytes, w.total);
-        return TEO_ERR_WORKSPACE;
-    }
+// The layer loop and the lm_head of a step over B rows -- B conversations of a batched step, or the B rows of one conversation's verify
+// step: every weight matrix streamed once (skinny GEMM with the RMSNorm hand-offs, or the per-row GEMV fallback for fp32 / odd K).
+// attend(l) runs layer l's attention on w.qkv -> w.attn.  *skinny_out: which of the two forms ran (the tail feeds the next step's norm).
+struct BatchLoopOpts { int B; bool w_tiled, gateup_block8, w_mxfp4; };
+template <typename Attend>
+static int decode_batch_layers(const teo_llama_desc* d, const BatchLoopOpts& o, const DecodeBatchWs& w, float* d_logits, Attend attend,
+                               bool* skinny_out, const char* who, hipStream_t st) {
+    const int B = o.B;
     const int dt = d->dtype;
     const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim, F = d->inter;
     const int QKV = (H + 2 * Hk) * hd;
     // w4: the four layer matrices are the descriptor's tiled MXFP4 copies (teo_decode_batch_state.w_mxfp4; the C entry points have
     // checked that they are all there, tiled, bf16 and without fp8 copies); lm_head stays 16-bit
-    const bool w4 = s->w_mxfp4 != 0;
+    const bool w4 = o.w_mxfp4;
     const bool w8 = d->qkv_w8 != nullptr, h8 = d->lm_head8 != nullptr;
     const int wf = w4 ? SK_W_MXFP4 : (w8 ? SK_W_FP8 : SK_W_16);
     const bool skinny = batch_uses_skinny(d, B, w4);
-    if (!skinny && (s->w_tiled || s->gateup_block8 || w4)) {
-        set_error("teo_llama_decode_batch_step: tiled weights need bf16 activations and K %% %d == 0", w4 ? 128 : (w8 ? 64 : 32));
+    if (!skinny && (o.w_tiled || o.gateup_block8 || w4)) {
+        set_error("%s: tiled weights need bf16 activations and K %% %d == 0", who, w4 ? 128 : (w8 ? 64 : 32));
         return TEO_ERR_UNSUPPORTED;
     }
-    const unsigned tl = s->w_tiled ? TEO_GEMM_WTILED : 0u;
-    AttnBatch bt;
-    bt.batch = B; bt.q_stride = QKV; bt.cache_stride = s->cache_stride; bt.o_stride = (long long)H * hd;
+    const unsigned tl = o.w_tiled ? TEO_GEMM_WTILED : 0u;
     // w.h holds the residual stream; on the skinny path w.hg = bf16(h * g) and w.ssq = partial sum(h^2) of the norm that
     // comes next -- written by the producer of h (embed / o / down GEMM epilogue), consumed by the next GEMM.
     SkinnyFuse take;                                       // consumer side
@@ -611,10 +610,9 @@ int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_stat
         } else {
             TEO_TRY(batch_linear_rows(B, w.h, D, qkv_w, qkv_s, w8, d->in_norm_w[l], nullptr, w.qkv, QKV, QKV, D, d->eps, 0, dt, dt, st));
         }
-        // RoPE + KV append of the B new tokens inside the attention kernel, each conversation at its own position
+        // RoPE + KV append of the B new rows inside the attention kernel (w.qkv -> w.attn)
         prof_class(TEO_PROF_ATTN);
-        TEO_TRY(attn_decode(w.qkv, d->k_cache[l], d->v_cache[l], d->vt_cache[l], d->rope_cos, d->rope_sin, w.attn, w.part,
-                            s->d_pos, d->max_seq, H, Hk, hd, 1.0f / sqrtf((float)hd), dt, st, bt));
+        TEO_TRY(attend(l));
         if (skinny) {
             SkinnyFuse give;                               // h += attn Wo^T; hand post_norm its inputs
             give.f16 = dt == TEO_F16;
@@ -623,7 +621,7 @@ int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_stat
             TEO_TRY(skinny_gemm(w.attn, o_w, o_s, wf, nullptr, 0.f, w.h, w.h, B, D, H * hd, H * hd, D, tl, dt, st, give));
             prof_class(TEO_PROF_GATEUP);
             TEO_TRY(skinny_gemm(w.hg, gu_w, gu_s, wf, nullptr, 0.f, nullptr, w.act, B, 2 * F, D, D, F,
-                                tl | (s->gateup_block8 ? TEO_GEMM_SWIGLU8 : TEO_GEMM_SWIGLU16), dt, st, take));
+                                tl | (o.gateup_block8 ? TEO_GEMM_SWIGLU8 : TEO_GEMM_SWIGLU16), dt, st, take));
             give.next_g = (const unsigned short*)(l + 1 < d->layers ? d->in_norm_w[l + 1] : d->final_norm_w);
             prof_class(TEO_PROF_DOWN);
             TEO_TRY(skinny_gemm(w.act, dn_w, dn_s, wf, nullptr, 0.f, w.h, w.h, B, D, F, F, D, tl, dt, st, give));
@@ -641,11 +639,34 @@ int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_stat
     const float* head_s = h8 ? d->lm_head_s : nullptr;
     prof_class(TEO_PROF_LM_HEAD);
     if (skinny) {
-        TEO_TRY(skinny_gemm(w.hg, head_w, head_s, h8, nullptr, 0.f, nullptr, s->d_logits, B, d->vocab, D, D, d->vocab, tl, TEO_F32, st, take));
+        TEO_TRY(skinny_gemm(w.hg, head_w, head_s, h8, nullptr, 0.f, nullptr, d_logits, B, d->vocab, D, D, d->vocab, tl, TEO_F32, st, take));
     } else {
-        TEO_TRY(batch_linear_rows(B, w.h, D, head_w, head_s, h8, d->final_norm_w, nullptr, s->d_logits, d->vocab, d->vocab, D, d->eps, 0,
+        TEO_TRY(batch_linear_rows(B, w.h, D, head_w, head_s, h8, d->final_norm_w, nullptr, d_logits, d->vocab, d->vocab, D, d->eps, 0,
                                   dt, TEO_F32, st));
     }
+    *skinny_out = skinny;
+    return TEO_OK;
+}
+
+int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
+    const int B = s->batch;
+    const DecodeBatchWs w = decode_batch_carve(d, B, ws, ws_bytes);
+    if (w.total > ws_bytes) {
+        set_error("teo_llama_decode_batch_step: workspace %zu < %zu", ws_bytes, w.total);
+        return TEO_ERR_WORKSPACE;
+    }
+    const int dt = d->dtype;
+    const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim;
+    AttnBatch bt;
+    bt.batch = B; bt.q_stride = (H + 2 * Hk) * hd; bt.cache_stride = s->cache_stride; bt.o_stride = (long long)H * hd;
+    // each conversation at its own position
+    auto attend = [&](int l) {
+        return attn_decode(w.qkv, d->k_cache[l], d->v_cache[l], d->vt_cache[l], d->rope_cos, d->rope_sin, w.attn, w.part, s->d_pos,
+                           d->max_seq, H, Hk, hd, 1.0f / sqrtf((float)hd), dt, st, bt);
+    };
+    bool skinny = false;
+    const BatchLoopOpts o = {B, s->w_tiled != 0, s->gateup_block8 != 0, s->w_mxfp4 != 0};
+    TEO_TRY(decode_batch_layers(d, o, w, s->d_logits, attend, &skinny, "teo_llama_decode_batch_step", st));
     const teo_decode_state t = batch_as_state(s);
     prof_class(TEO_PROF_TAIL);
     if (skinny)
@@ -661,6 +682,59 @@ int llama_decode_begin(const teo_llama_desc* d, const teo_decode_state* s, void*
         return TEO_ERR_WORKSPACE;
     }
     return embed_token(s->d_token, d->embed, w.h, d->hidden, d->dtype, st);
+}
+
+// ------------------------------------------------------------------------------------------------
+// speculative verify step: R rows of ONE conversation per pass over the weights (include/teo_hip.h teo_verify_state)
+// ------------------------------------------------------------------------------------------------
+struct VerifyWs {
+    DecodeBatchWs b;
+    long long* sel;             // [rows] the token selected behind every row
+    size_t total;
+};
+static VerifyWs verify_carve(const teo_llama_desc* d, int R, void* ws, size_t cap) {
+    VerifyWs v;
+    v.b = decode_batch_carve(d, R, ws, cap);
+    v.sel = ws ? (long long*)((unsigned char*)ws + v.b.total) : nullptr;
+    v.total = v.b.total + align_up((size_t)R * sizeof(long long));
+    return v;
+}
+size_t llama_verify_workspace_bytes(const teo_llama_desc* d, int rows) { return verify_carve(d, rows, nullptr, 0).total; }
+
+int llama_verify_begin(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (verify_carve(d, s->rows, ws, ws_bytes).total > ws_bytes) {
+        set_error("teo_llama_verify_begin: workspace too small");
+        return TEO_ERR_WORKSPACE;
+    }
+    return spec_propose(s->d_hist, s->d_hist_len, s->d_rows, s->d_n_draft, s->rows, s->ngram_max, st);
+}
+
+int llama_verify_step(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
+    const int R = s->rows;
+    const VerifyWs v = verify_carve(d, R, ws, ws_bytes);
+    if (v.total > ws_bytes) {
+        set_error("teo_llama_verify_step: workspace %zu < %zu", ws_bytes, v.total);
+        return TEO_ERR_WORKSPACE;
+    }
+    const DecodeBatchWs& w = v.b;
+    const int dt = d->dtype;
+    const int H = d->heads, Hk = d->kv_heads, hd = d->head_dim;
+    // embed the R rows (the rows come from the proposer, not from the previous step's tail); on the skinny path also layer 0's norm inputs
+    prof_class(TEO_PROF_TAIL);
+    if (batch_uses_skinny(d, R, s->w_mxfp4 != 0))
+        TEO_TRY(embed_token_emit(s->d_rows, d->embed, w.h, d->hidden, dt, st, R, d->in_norm_w[0], w.hg, w.ssq, w.nparts));
+    else
+        TEO_TRY(embed_token(s->d_rows, d->embed, w.h, d->hidden, dt, st, R));
+    // one cache, R consecutive positions from *d_pos: the cache is streamed once for all rows
+    auto attend = [&](int l) {
+        return attn_verify(w.qkv, d->k_cache[l], d->v_cache[l], d->vt_cache[l], d->rope_cos, d->rope_sin, w.attn, w.part, s->d_pos,
+                           d->max_seq, H, Hk, hd, 1.0f / sqrtf((float)hd), dt, R, (long long)(H + 2 * Hk) * hd, st);
+    };
+    bool skinny = false;
+    const BatchLoopOpts o = {R, s->w_tiled != 0, s->gateup_block8 != 0, s->w_mxfp4 != 0};
+    TEO_TRY(decode_batch_layers(d, o, w, s->d_logits, attend, &skinny, "teo_llama_verify_step", st));
+    prof_class(TEO_PROF_TAIL);
+    return verify_tail(s->d_logits, s, v.sel, d->vocab, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -762,6 +836,16 @@ int decode_graph_create(const teo_llama_desc* d, const teo_decode_state* s, void
 int decode_batch_graph_create(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes,
                               hipStream_t st, teo_graph** out) {
     return capture_graph(st, [&]() { return llama_decode_batch_step(d, s, ws, ws_bytes, st); }, out);
+}
+
+int llama_verify_step_profile(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, float* ms_out, int* count_out,
+                              hipStream_t st) {
+    return profiled_step([&]() { return llama_verify_step(d, s, ws, ws_bytes, st); }, ms_out, count_out, st,
+                         8 * (size_t)d->layers * (size_t)std::max(1, s->rows) + 16);
+}
+
+int verify_graph_create(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, hipStream_t st, teo_graph** out) {
+    return capture_graph(st, [&]() { return llama_verify_step(d, s, ws, ws_bytes, st); }, out);
 }
 
 }  // namespace teo

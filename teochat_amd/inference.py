@@ -37,7 +37,7 @@ def build_prompt(inp, image_paths, conv_mode="v1", prompt_strategy="interleave",
 
 def run_inference_single(model, processor, tokenizer, inp, image_paths, conv_mode="v1", timestamps=[],
                          prompt_strategy="interleave", chronological_prefix=True, temperature=0.2, max_new_tokens=256,
-                         do_sample=True):
+                         do_sample=True, prompt_lookup_num_tokens=None, max_matching_ngram_size=None):
     if len(timestamps) > 0:
         order = sorted(range(len(image_paths)), key=lambda i: datetime.strptime(timestamps[i], "%Y-%m-%d"))
         image_paths = [image_paths[i] for i in order]
@@ -48,8 +48,13 @@ def run_inference_single(model, processor, tokenizer, inp, image_paths, conv_mod
     input_ids = tokenizer_image_token(prompt, tokenizer, IMAGE_TOKEN_INDEX, return_tensors="pt").unsqueeze(0).to(model.device)
     stopping = KeywordsStoppingCriteria([stop_str], tokenizer, input_ids)
     with torch.inference_mode():
+        spec = {}                                  # prompt-lookup speculative decoding (model.generate): passed on only when asked for
+        if prompt_lookup_num_tokens is not None:
+            spec["prompt_lookup_num_tokens"] = prompt_lookup_num_tokens
+        if max_matching_ngram_size is not None:
+            spec["max_matching_ngram_size"] = max_matching_ngram_size
         output_ids = model.generate(input_ids=input_ids, images=frames, do_sample=do_sample, temperature=temperature,
-                                    max_new_tokens=max_new_tokens, use_cache=True, stopping_criteria=[stopping])
+                                    max_new_tokens=max_new_tokens, use_cache=True, stopping_criteria=[stopping], **spec)
     return tokenizer.decode(output_ids[0, input_ids.shape[1]:]).replace("</s>", "").strip()
 
 

@@ -237,6 +237,8 @@ class LlavaLlamaForCausalLM:
         self.generation_config = SimpleNamespace(eos_token_id=getattr(config, "eos_token_id", None), do_sample=False, top_k=50,
                                                  top_p=1.0, temperature=1.0)
         self.training = False
+        # {steps, proposed, accepted, emitted} of the last generate(prompt_lookup_num_tokens=K) call; None after any other generate()
+        self.last_generation_stats = None
 
     # --- nn.Module-ish surface the harness touches
     @property
@@ -504,9 +506,16 @@ class LlavaLlamaForCausalLM:
 
     def _generate(self, input_ids=None, images=None, do_sample=None, temperature=None, top_k=None, top_p=None,
                   max_new_tokens=20, use_cache=True, stopping_criteria=None, eos_token_id="config", attention_mask=None,
-                  generator=None, chunk=16, **kwargs):
+                  generator=None, chunk=16, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, **kwargs):
         """Greedy or sampled (temperature / top-k, device sampler) decoding of ONE sequence; the loop is device-resident
         and replayed from a hipGraph.
+
+        prompt_lookup_num_tokens=K (1..15; HF's keyword, one conversation only): prompt-lookup speculative decoding -- every pass over the
+        weights verifies the pending token and up to K drafts copied from behind the most recent earlier occurrence of the last
+        max_matching_ngram_size (.. 1) tokens (teochat_amd/speculative.py).  The tokens do not depend on the drafts; the weights stream
+        through the batched step's kernels.  `last_generation_stats` holds {steps, proposed, accepted, emitted} afterwards: the DEVICE's
+        totals -- when a host-side criterion (several stop candidates, a custom StoppingCriteria) ends the call inside a chunk of replays
+        they include the steps and tokens the device ran behind that token.  Any other generate() call sets it to None.  0 or None: off.
 
         Returns int64 [1, n_prompt + n_generated]; the prompt part still contains the -200 sentinels, as with the
         reference (eval/inference.py:75 slices at input_ids.shape[1]).  `eos_token_id=None` disables EOS stopping.
@@ -517,6 +526,12 @@ class LlavaLlamaForCausalLM:
         temperature = float(getattr(gc, "temperature", 1.0) or 1.0) if temperature is None else temperature
         top_k = getattr(gc, "top_k", 50) if top_k is None else top_k
         top_p = getattr(gc, "top_p", 1.0) if top_p is None else top_p
+        self.last_generation_stats = None
+        K = int(prompt_lookup_num_tokens or 0)
+        if K and not 1 <= K <= 15:
+            raise ValueError(f"prompt_lookup_num_tokens {K} outside 1..15")
+        if K and input_ids.shape[0] != 1:
+            raise ValueError("prompt_lookup_num_tokens applies to one conversation (batch 1)")
         if input_ids.shape[0] != 1:
             # batch of conversations: rows are cut by attention_mask, `images` is a list with one entry per conversation
             B = input_ids.shape[0]
@@ -548,10 +563,21 @@ class LlavaLlamaForCausalLM:
                                                                                None, images)
         if embeds is None:
             embeds = self.get_model().embed_tokens(input_ids)
-        eng.reset_cache()
-        if embeds.shape[1] + max_new_tokens > eng.max_seq:
-            raise ValueError(f"prompt ({embeds.shape[1]}) + max_new_tokens ({max_new_tokens}) exceeds max_seq {eng.max_seq}")
-        logits = eng.prefill(embeds[0], last_only=True)
+        spec = None
+        if K:
+            # one verify step writes K + 1 cache rows from the pending token's position on, whatever it accepts
+            if embeds.shape[1] + max_new_tokens - 1 + K + 1 > eng.max_seq:
+                raise ValueError(f"prompt ({embeds.shape[1]}) + max_new_tokens ({max_new_tokens}) - 1 + prompt_lookup_num_tokens + 1 "
+                                 f"({K + 1}) exceeds max_seq {eng.max_seq}")
+            spec = self.spec_decoder(K + 1, max_new=max_new_tokens, ngram_max=int(max_matching_ngram_size)) if max_new_tokens > 1 else None
+        if spec is not None:
+            spec.reset()
+            logits = spec.prefill(embeds[0], last_only=True)
+        else:
+            eng.reset_cache()
+            if embeds.shape[1] + max_new_tokens > eng.max_seq:
+                raise ValueError(f"prompt ({embeds.shape[1]}) + max_new_tokens ({max_new_tokens}) exceeds max_seq {eng.max_seq}")
+            logits = eng.prefill(embeds[0], last_only=True)
         if do_sample:
             tp = 1.0 if top_p is None else float(top_p)
             k = int(top_k or 0)                    # 0 = top-k filter off (HF: top_k=0 / None disables TopKLogitsWarper)
@@ -585,6 +611,22 @@ class LlavaLlamaForCausalLM:
             if ids not in uniq:
                 uniq.append(ids)
         stop_ids = uniq[0] if len(uniq) == 1 else None
+        if spec is not None:
+            # verify steps: the same device-resident loop, up to K + 1 tokens per replay; the host looks once per chunk of replays
+            spec.begin(first, input_ids[0].tolist() + [first], stop_ids, do_sample=do_sample, temperature=temperature, top_k=k, seed=seed,
+                       draws_done=1, top_p=tp, max_new=max_new_tokens - 1)
+            stop_here = False
+            while not stop_here and len(new_tokens) < max_new_tokens:
+                spec.steps(chunk)
+                got = spec.generated().tolist()
+                for t in got[len(new_tokens) - 1:]:
+                    new_tokens.append(int(t))
+                    if done(new_tokens):
+                        stop_here = True
+                        break
+                stop_here = stop_here or spec.stopped()
+            self.last_generation_stats = spec.stats()
+            return self._finish(input_ids, new_tokens)
         eng.decode_begin(first, stop_ids, do_sample=do_sample, temperature=temperature, top_k=k, seed=seed, draws_done=1, top_p=tp)
         remaining = max_new_tokens - 1
         while remaining > 0:
@@ -602,6 +644,20 @@ class LlavaLlamaForCausalLM:
             if stop_here:
                 break
         return self._finish(input_ids, new_tokens)
+
+    # --- speculative verify steps (prompt lookup): R rows of one conversation per pass over the weights
+    def spec_decoder(self, rows, max_new=1024, ngram_max=2):
+        from .speculative import SpecDecoder
+        w4 = bool(getattr(self.engine, "batch_mxfp4", False))
+        cur = getattr(self, "_spec_decoder", None)
+        if cur is None or cur.R != rows or cur.max_new < max_new or cur.ngram_max != ngram_max or cur.w4_requested != w4:
+            self._spec_decoder = None           # free the old cache first
+            bd = getattr(self, "_batch_decoder", None)
+            if bd is not None and bd.w4_requested != w4:
+                bd = None                       # (its copies are in the other weight format)
+            cur = SpecDecoder(self.engine, rows, max_new=max(max_new, 64), ngram_max=ngram_max, batch_decoder=bd)
+            self._spec_decoder = cur
+        return cur
 
     # --- batched decode (config C5's variant): B conversations, one pass over the weights per generated token
     def batch_decoder(self, batch, max_new=1024):
