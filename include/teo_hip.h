@@ -67,7 +67,8 @@ const char* teo_gemm_w4_plan(int M, int N, int K, unsigned flags, int out_dtype,
  * TEO_F16 output included).  From M, N, the flags and the CU count alone: no teo_tune key, no workspace. */
 const char* teo_gemm_w4a8_plan(int M, int N, int K, unsigned flags, int out_dtype, int cu_count);
 /* Size of a struct of this header as the LIBRARY was built with it (0 for an unknown name): a binding checks its own layout against it
- * at load time -- "teo_vit_desc", "teo_proj_desc", "teo_llama_desc", "teo_decode_state", "teo_decode_batch_state", "teo_attn_args". */
+ * at load time -- "teo_vit_desc", "teo_proj_desc", "teo_llama_desc", "teo_decode_state", "teo_decode_batch_state", "teo_attn_args",
+ * "teo_verify_state", "teo_decode_stream_state". */
 size_t teo_sizeof(const char* struct_name);
 /* Performance tuning knobs.  PERF-ONLY: every key selects among kernels / geometries that compute the same values (bit-identical
  * unless noted "fp32 order": the fp32 summation order of a reduction may change, nothing else).  Result- or path-selecting options
@@ -271,6 +272,9 @@ int teo_embed_splice(const int* d_plan, const void* d_embed, const void* d_visua
  *   rope_cos == NULL : d_q holds the rotated query [heads*head_dim]; the caches already contain the new token's K/V.
  *   rope_cos != NULL : d_q holds the raw [q | k | v] row of the QKV projection; the kernel applies RoPE at d_pos[b] to q
  *                      and k and appends k, v (and V^T when d_vt_cache != NULL) to the caches before attending.
+ * A conversation with d_pos[b] < 0 is PARKED (a free slot of the stream decoder below): its workgroups issue no K / V load, append
+ * nothing to K, V or V^T, write a zero output row and exit; the other conversations' outputs and appended rows are the bits they would be
+ * with every conversation live.
  * KV-split partials + combine; d_partials is teo_attn_decode_workspace_bytes(...) of scratch. */
 size_t teo_attn_decode_workspace_bytes(int heads, int head_dim, int max_seq, int batch);
 int teo_attn_decode(const void* d_q, void* d_k_cache, void* d_v_cache, void* d_vt_cache, const float* d_rope_cos,
@@ -578,6 +582,14 @@ int teo_llama_prefill_batch(const teo_llama_desc* d, const void* d_embeds, const
                             int last_only, float* d_logits, void* d_workspace, size_t workspace_bytes, teo_stream_t stream,
                             void* d_hidden_states /* NULL or [layers + 1][sum(seq_lens)][hidden], as teo_llama_prefill */);
 
+/* teo_llama_prefill_batch with sequence i written into cache slot slots[i] (a HOST array of distinct slot numbers, each
+ * 0..TEO_MAX_DECODE_BATCH-1 and inside the caller's [B][...] allocation; nseq <= TEO_MAX_DECODE_BATCH) instead of slot i: every
+ * slot a stream decoder freed in one round is refilled in ONE pass over the weights.  Logits row i belongs to sequence i.  Slots
+ * that are not named are not touched.  Row for row the results equal teo_llama_prefill's into that slot. */
+int teo_llama_prefill_slots(const teo_llama_desc* d, const void* d_embeds, const int* seq_lens, const int* slots, int nseq,
+                            long long cache_stride, int last_only, float* d_logits, void* d_workspace, size_t workspace_bytes,
+                            teo_stream_t stream, void* d_hidden_states /* NULL or as teo_llama_prefill_batch */);
+
 size_t teo_llama_decode_workspace_bytes(const teo_llama_desc* d);
 /* Arm a generation: workspace.h <- embed[*d_token] (call once after filling d_token/d_pos; every step's tail then
  * prepares the next step's embedding itself). */
@@ -618,7 +630,7 @@ int teo_graph_destroy(teo_graph* g);
  * prefill except that k_cache/v_cache/vt_cache[l] point at conversation 0 of a [B][...] allocation and
  * `cache_stride` (elements) separates consecutive conversations; with w_tiled = 1 its weight matrices (qkv/o/gateup/
  * down/lm_head, bf16 or fp8; with w_mxfp4 = 1 the four MXFP4 layer matrices and the 16-bit lm_head) are in the TEO_GEMM_WTILED layout.  Finished conversations keep stepping (their d_stop
- * is set; the host truncates), exactly like the single-conversation loop. */
+ * is set; the host truncates), exactly like the single-conversation loop; the stream step below parks them instead. */
 #define TEO_MAX_DECODE_BATCH 16
 typedef struct {
     int batch;                /* 1..TEO_MAX_DECODE_BATCH */
@@ -654,6 +666,39 @@ int teo_llama_decode_batch_step_profile(const teo_llama_desc* d, const teo_decod
                                         float* ms_out /* [TEO_PROF_CLASSES] */, int* count_out /* [TEO_PROF_CLASSES] */, teo_stream_t stream);
 int teo_llama_decode_batch_graph_create(const teo_llama_desc* d, const teo_decode_batch_state* st, void* d_workspace,
                                         size_t workspace_bytes, teo_stream_t stream, teo_graph** out);
+
+/* ---- stream decode (continuous batching): the batched step over SLOTS that finish, park and are refilled independently ---------
+ * The state is teo_decode_batch_state plus d_limit; the step is the batched step (same launches, same arithmetic: a live slot's
+ * logits, cache rows, tokens and positions are bit for bit what teo_llama_decode_batch_step gives that conversation at the same
+ * batch) with two differences:
+ *   - a slot with d_pos[b] < 0 is PARKED: the attention skips it (teo_attn_decode above) and the tail changes none of its d_token,
+ *     d_pos, d_out_tokens, d_out_count and d_rng; it re-emits the embedding row of its last token, so the slot's row of the residual
+ *     stream stays finite over any number of replays (its GEMM rows still run; its d_logits row is meaningless);
+ *   - a live slot selects, appends, advances and runs the stop test as the batched tail does, and then, if the stop suffix matched or
+ *     d_out_count[b] has reached d_limit[b], sets d_stop[b] = 1 and parks ITSELF: d_pos[b] = -1 - (its advanced position = the number
+ *     of tokens in its cache).  A chunk of graph replays may therefore run past any slot's end.
+ * The host parks a slot by writing a negative d_pos[b] (every unused slot starts parked) and revives one by refilling its cache
+ * (teo_llama_prefill_slots), writing d_token / d_pos / d_out_count = 0 / d_stop = 0 / d_limit / d_rng for that slot and calling
+ * teo_llama_decode_stream_arm, which embeds d_token[slot] into row `slot` of the workspace's residual stream (on the skinny path
+ * also layer 0's norm inputs of that row) and touches no other row: the previous step's tail has prepared theirs.  d_limit[b] >= 1;
+ * the caller keeps position + d_limit[b] <= max_seq and d_limit[b] <= out_stride. */
+typedef struct {
+    int batch; int out_stride; long long cache_stride; int w_tiled; int gateup_block8; int w_mxfp4;   /* as teo_decode_batch_state */
+    long long* d_token; int* d_pos; long long* d_out_tokens; int* d_out_count; int* d_stop;
+    const long long* d_stop_ids; int n_stop_ids;
+    float* d_logits;
+    int do_sample; int top_k; float temperature;
+    unsigned long long* d_rng;
+    float top_p;
+    int* d_limit;             /* [batch] slot b stops once d_out_count[b] reaches d_limit[b] */
+} teo_decode_stream_state;
+size_t teo_llama_decode_stream_workspace_bytes(const teo_llama_desc* d, int batch);
+int teo_llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* st, void* d_workspace, size_t workspace_bytes,
+                                 teo_stream_t stream);
+int teo_llama_decode_stream_graph_create(const teo_llama_desc* d, const teo_decode_stream_state* st, void* d_workspace,
+                                         size_t workspace_bytes, teo_stream_t stream, teo_graph** out);
+int teo_llama_decode_stream_arm(const teo_llama_desc* d, const teo_decode_stream_state* st, int slot, void* d_workspace,
+                                size_t workspace_bytes, teo_stream_t stream);
 
 /* ---- speculative decoding: verify `rows` tokens of ONE conversation per pass over the weights ----------------------------------
  * A verify step feeds R = rows <= TEO_MAX_DECODE_BATCH rows -- the pending token d_rows[0] and drafts d_rows[1 .. n_draft], at positions

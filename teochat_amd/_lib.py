@@ -93,6 +93,10 @@ class DecodeBatchState(C.Structure):
                 ("top_p", C.c_float)]
 
 
+class DecodeStreamState(C.Structure):
+    _fields_ = DecodeBatchState._fields_ + [("d_limit", C.c_void_p)]
+
+
 class VerifyState(C.Structure):
     _fields_ = [("rows", C.c_int), ("max_new", C.c_int), ("ngram_max", C.c_int), ("w_tiled", C.c_int), ("gateup_block8", C.c_int),
                 ("w_mxfp4", C.c_int),
@@ -175,6 +179,14 @@ _SIGS = {
                                                       C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_void_p]),
     "teo_llama_decode_batch_graph_create": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeBatchState), C.c_void_p, C.c_size_t,
                                                       C.c_void_p, C.POINTER(C.c_void_p)]),
+    "teo_llama_prefill_slots": (C.c_int, [C.POINTER(LlamaDesc), C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_longlong,
+                                          C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "teo_llama_decode_stream_workspace_bytes": (C.c_size_t, [C.POINTER(LlamaDesc), C.c_int]),
+    "teo_llama_decode_stream_step": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeStreamState), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "teo_llama_decode_stream_graph_create": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeStreamState), C.c_void_p, C.c_size_t,
+                                                       C.c_void_p, C.POINTER(C.c_void_p)]),
+    "teo_llama_decode_stream_arm": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeStreamState), C.c_int, C.c_void_p, C.c_size_t,
+                                              C.c_void_p]),
     "teo_llama_verify_workspace_bytes": (C.c_size_t, [C.POINTER(LlamaDesc), C.c_int]),
     "teo_llama_verify_begin": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(VerifyState), C.c_void_p, C.c_size_t, C.c_void_p]),
     "teo_llama_verify_step": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(VerifyState), C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -246,7 +258,8 @@ def load():
     if lib.teo_version() != ABI_VERSION:
         raise TeoLibraryError(f"ABI version mismatch: library {lib.teo_version()}, binding {ABI_VERSION}; rebuild {LIB_PATH}")
     mirrors = {"teo_vit_desc": VitDesc, "teo_proj_desc": ProjDesc, "teo_llama_desc": LlamaDesc, "teo_decode_state": DecodeState,
-               "teo_decode_batch_state": DecodeBatchState, "teo_attn_args": AttnArgs, "teo_verify_state": VerifyState}
+               "teo_decode_batch_state": DecodeBatchState, "teo_attn_args": AttnArgs, "teo_verify_state": VerifyState,
+               "teo_decode_stream_state": DecodeStreamState}
     for name, cls in mirrors.items():
         want = lib.teo_sizeof(name.encode())
         if want != C.sizeof(cls):

@@ -61,7 +61,8 @@ size_t llama_prefill_workspace_bytes(const teo_llama_desc* d, int S);
 int llama_prefill(const teo_llama_desc* d, const void* embeds, const int* positions, int S, int past, int last_only,
                   float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, void* attentions);
 int llama_prefill_batch(const teo_llama_desc* d, const void* embeds, const int* seq_lens, int nseq, long long cache_stride,
-                        int last_only, float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states);
+                        int last_only, float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states,
+                        const int* slots = nullptr);
 size_t llama_decode_workspace_bytes(const teo_llama_desc* d);
 int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st);
 int llama_decode_step_profile(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, float* ms_out, int* count_out,
@@ -79,6 +80,11 @@ int llama_decode_batch_begin(const teo_llama_desc* d, const teo_decode_batch_sta
 int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes, hipStream_t st);
 int decode_batch_graph_create(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes,
                               hipStream_t st, teo_graph** out);
+
+int llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st);
+int llama_decode_stream_arm(const teo_llama_desc* d, const teo_decode_stream_state* s, int slot, void* ws, size_t ws_bytes, hipStream_t st);
+int decode_stream_graph_create(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
+                               teo_graph** out);
 
 size_t llama_verify_workspace_bytes(const teo_llama_desc* d, int rows);
 int llama_verify_begin(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, hipStream_t st);
@@ -175,6 +181,7 @@ size_t teo_sizeof(const char* struct_name) {
     if (!strcmp(struct_name, "teo_decode_batch_state")) return sizeof(teo_decode_batch_state);
     if (!strcmp(struct_name, "teo_attn_args")) return sizeof(teo_attn_args);
     if (!strcmp(struct_name, "teo_verify_state")) return sizeof(teo_verify_state);
+    if (!strcmp(struct_name, "teo_decode_stream_state")) return sizeof(teo_decode_stream_state);
     return 0;
 }
 
@@ -478,6 +485,24 @@ int teo_llama_prefill_batch(const teo_llama_desc* d, const void* emb, const int*
     return llama_prefill_batch(d, emb, seq_lens, nseq, cache_stride, last_only, logits, ws, wsb, ST(s), hidden_states);
 }
 
+int teo_llama_prefill_slots(const teo_llama_desc* d, const void* emb, const int* seq_lens, const int* slots, int nseq, long long cache_stride,
+                            int last_only, float* logits, void* ws, size_t wsb, teo_stream_t s, void* hidden_states) {
+    ENTER();
+    NEED(d, "desc"); NEED_DT(d->dtype); NEED(seq_lens, "seq_lens"); NEED(slots, "slots");
+    TuneScope tune_scope(d->tune);
+    TEO_CHECK_ARG(nseq >= 0 && nseq <= TEO_MAX_DECODE_BATCH && cache_stride > 0, "teo_llama_prefill_slots: nseq %d cache_stride %lld", nseq,
+                  cache_stride);
+    if (nseq == 0) return TEO_OK;
+    for (int i = 0; i < nseq; ++i) {
+        TEO_CHECK_ARG(slots[i] >= 0 && slots[i] < TEO_MAX_DECODE_BATCH, "teo_llama_prefill_slots: slots[%d] = %d outside 0..%d", i, slots[i],
+                      TEO_MAX_DECODE_BATCH - 1);
+        for (int j = 0; j < i; ++j) TEO_CHECK_ARG(slots[j] != slots[i], "teo_llama_prefill_slots: slot %d named twice", slots[i]);
+    }
+    NEED(emb, "embeds"); NEED(logits, "logits"); NEED(ws, "workspace");
+    { const int rc = check_prefill_weights(d); if (rc != TEO_OK) return rc; }
+    return llama_prefill_batch(d, emb, seq_lens, nseq, cache_stride, last_only, logits, ws, wsb, ST(s), hidden_states, slots);
+}
+
 size_t teo_llama_decode_workspace_bytes(const teo_llama_desc* d) { return d ? llama_decode_workspace_bytes(d) : 0; }
 int teo_llama_decode_step(const teo_llama_desc* d, const teo_decode_state* st, void* ws, size_t wsb, teo_stream_t s) {
     ENTER();
@@ -604,6 +629,54 @@ int teo_llama_decode_batch_graph_create(const teo_llama_desc* d, const teo_decod
     NEED(ws, "workspace"); NEED(out, "out");
     TEO_CHECK_ARG(s != nullptr, "teo_llama_decode_batch_graph_create: needs a non-default stream to capture on");
     return decode_batch_graph_create(d, st, ws, wsb, ST(s), out);
+}
+
+// ---- stream decode: the batched step over slots that park themselves ----
+static teo_decode_batch_state stream_batch_view(const teo_decode_stream_state* st) {
+    teo_decode_batch_state b;
+    memset(&b, 0, sizeof(b));
+    b.batch = st->batch; b.out_stride = st->out_stride; b.cache_stride = st->cache_stride;
+    b.w_tiled = st->w_tiled; b.gateup_block8 = st->gateup_block8; b.w_mxfp4 = st->w_mxfp4;
+    b.d_token = st->d_token; b.d_pos = st->d_pos; b.d_out_tokens = st->d_out_tokens; b.d_out_count = st->d_out_count; b.d_stop = st->d_stop;
+    b.d_stop_ids = st->d_stop_ids; b.n_stop_ids = st->n_stop_ids; b.d_logits = st->d_logits;
+    b.do_sample = st->do_sample; b.top_k = st->top_k; b.temperature = st->temperature; b.d_rng = st->d_rng; b.top_p = st->top_p;
+    return b;
+}
+static int check_stream_state(const teo_llama_desc* d, const teo_decode_stream_state* st) {
+    NEED(d, "desc"); NEED(st, "state"); NEED(st->d_limit, "d_limit");
+    const teo_decode_batch_state b = stream_batch_view(st);         // the rest is the batched step's contract
+    return check_batch_state(d, &b);
+}
+
+size_t teo_llama_decode_stream_workspace_bytes(const teo_llama_desc* d, int batch) {
+    return (d && batch >= 1 && batch <= TEO_MAX_DECODE_BATCH) ? llama_decode_batch_workspace_bytes(d, batch) : 0;
+}
+
+int teo_llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* st, void* ws, size_t wsb, teo_stream_t s) {
+    ENTER();
+    { const int rc = check_stream_state(d, st); if (rc != TEO_OK) return rc; }
+    TuneScope tune_scope(d->tune);
+    NEED(ws, "workspace");
+    return llama_decode_stream_step(d, st, ws, wsb, ST(s));
+}
+
+int teo_llama_decode_stream_graph_create(const teo_llama_desc* d, const teo_decode_stream_state* st, void* ws, size_t wsb, teo_stream_t s,
+                                         teo_graph** out) {
+    ENTER();
+    { const int rc = check_stream_state(d, st); if (rc != TEO_OK) return rc; }
+    TuneScope tune_scope(d->tune);
+    NEED(ws, "workspace"); NEED(out, "out");
+    TEO_CHECK_ARG(s != nullptr, "teo_llama_decode_stream_graph_create: needs a non-default stream to capture on");
+    return decode_stream_graph_create(d, st, ws, wsb, ST(s), out);
+}
+
+int teo_llama_decode_stream_arm(const teo_llama_desc* d, const teo_decode_stream_state* st, int slot, void* ws, size_t wsb, teo_stream_t s) {
+    ENTER();
+    { const int rc = check_stream_state(d, st); if (rc != TEO_OK) return rc; }
+    TuneScope tune_scope(d->tune);
+    NEED(ws, "workspace");
+    TEO_CHECK_ARG(slot >= 0 && slot < st->batch, "teo_llama_decode_stream_arm: slot %d outside 0..%d", slot, st->batch - 1);
+    return llama_decode_stream_arm(d, st, slot, ws, wsb, ST(s));
 }
 
 // ---- speculative verify ----

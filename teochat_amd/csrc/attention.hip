@@ -262,6 +262,8 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(const int* __r
     const int hk = (heads == kv_heads) ? h : h / (heads / kv_heads);      // MHA: no integer division in front of the first request
     const int c0 = sp * DEC_CHUNK;
     float* out = part + ((long long)h * nsplit + sp) * (HD + 2);
+    // (a PARKED conversation, d_pos < 0, has kv_len <= 0: every one of its workgroups takes this exit -- no K / V request, no append;
+    //  the combine launch writes its zero output row)
     if (c0 >= kv_len) {                                 // nothing here: neutral partial
         if (tid == 0) { out[0] = -INFINITY; out[1] = 0.f; }
         for (int d = tid; d < HD; d += 256) out[2 + d] = 0.f;
@@ -478,6 +480,10 @@ __global__ __launch_bounds__(512) void attn_decode_combine_kernel(const int* __r
     const int stride = hd + 2;
     part += (long long)blockIdx.y * gridDim.x * nsplit * stride;
     o += (long long)blockIdx.y * o_stride;
+    if (pos < 0) {                                                          // parked conversation: no record holds keys; a zero output row
+        if ((int)threadIdx.x < hd) Elem<T>::st(o + h * hd + threadIdx.x, 0.f);
+        return;
+    }
     const float* pb = part + (long long)h * nsplit * stride;
     const int nact = min(nsplit, (pos + (1 << chunk_log2)) >> chunk_log2);  // splits that hold keys (<= 256)
     attn_merge_records<T>(pb, stride, nact, hd_log2, o + h * hd, w, red, accs);
@@ -525,6 +531,10 @@ __global__ __launch_bounds__(AW_WAVES * 64) void attn_decode_whole_kernel(const 
     const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int hk = (heads == kv_heads) ? h : h / (heads / kv_heads);      // MHA: no integer division in front of the first request
     const int kv_len = *d_pos + 1;
+    if (kv_len <= 0) {                                  // parked conversation (d_pos < 0): no K / V request, no append, a zero output row
+        if (!PROBE && tid < HD) Elem<T>::st(o + h * HD + tid, 0.f);
+        return;
+    }
     const int nact = (kv_len + DEC_CHUNK - 1) / DEC_CHUNK;
     const int sub = lane % LPR, grp = lane / LPR;
     // uniform head bases + 32-bit byte offsets (one head's cache is far below 4 GB): SGPR-base addressing, no 64-bit address per load

@@ -733,11 +733,13 @@ __device__ __forceinline__ void embed_row_emit(const T* __restrict__ embed, long
 // Decode tail in one launch: argmax over the fp32 logits (float4 loads), then thread 0 appends the token, advances the
 // position and runs the id-suffix stop test, then the whole workgroup copies the next token's embedding row into h.
 // (embed_next: the NEXT step's embedding lookup is hoisted here; the first step of a generation runs embed_token.)
-template <typename T>
-__global__ __launch_bounds__(1024) void decode_tail_kernel(const float* __restrict__ logits, teo_decode_state st,
-                                                           const T* __restrict__ embed, T* __restrict__ h, int vocab,
-                                                           int dim, int out_stride, const T* __restrict__ g0,
-                                                           T* __restrict__ hg, float* __restrict__ ssq, int nparts) {
+// STREAM (teo_llama_decode_stream_step, include/teo_hip.h): d_limit[b] bounds the slot's d_out_count; a slot whose stop suffix matched or
+// whose limit is reached parks itself (d_pos = -1 - position), and a parked slot (d_pos < 0 on entry) changes none of its state and only
+// re-emits the embedding row of its last token, which keeps its row of the residual stream finite over any number of replays.
+template <typename T, bool STREAM>
+__device__ __forceinline__ void decode_tail_body(const float* __restrict__ logits, teo_decode_state st, const T* __restrict__ embed,
+                                                 T* __restrict__ h, int vocab, int dim, int out_stride, const T* __restrict__ g0,
+                                                 T* __restrict__ hg, float* __restrict__ ssq, int nparts, const int* __restrict__ d_limit) {
     {   // conversation blockIdx.x of a batched step (out_stride = row length of d_out_tokens)
         const long long b = blockIdx.x;
         logits += b * vocab;
@@ -746,8 +748,13 @@ __global__ __launch_bounds__(1024) void decode_tail_kernel(const float* __restri
         st.d_token += b; st.d_pos += b; st.d_out_count += b; st.d_stop += b;
         st.d_out_tokens += b * out_stride;
         if (st.d_rng) st.d_rng += 2 * b;
+        if (STREAM) d_limit += b;
     }
     __shared__ float sv[16];
+    if (STREAM && *st.d_pos < 0) {                          // parked (uniform over the workgroup: nothing has been written yet)
+        embed_row_emit<T>(embed, *st.d_token, h, dim, g0, hg, ssq, nparts, sv);
+        return;
+    }
     __shared__ int si[16];
     __shared__ long long s_tok;
     __shared__ __attribute__((aligned(16))) unsigned hist[256];
@@ -796,11 +803,47 @@ __global__ __launch_bounds__(1024) void decode_tail_kernel(const float* __restri
                 eq = eq && (st.d_out_tokens[n + 1 - st.n_stop_ids + k] == st.d_stop_ids[k]);
             if (eq) *st.d_stop = 1;
         }
+        if (STREAM && (*st.d_stop != 0 || n + 1 >= *d_limit)) {           // finished: park, keeping the final position recoverable
+            *st.d_stop = 1;
+            *st.d_pos = -1 - *st.d_pos;
+        }
         s_tok = t;
     }
     __syncthreads();
     const long long t = s_tok;
     embed_row_emit<T>(embed, t, h, dim, g0, hg, ssq, nparts, sv);
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void decode_tail_kernel(const float* __restrict__ logits, teo_decode_state st,
+                                                           const T* __restrict__ embed, T* __restrict__ h, int vocab,
+                                                           int dim, int out_stride, const T* __restrict__ g0,
+                                                           T* __restrict__ hg, float* __restrict__ ssq, int nparts) {
+    decode_tail_body<T, false>(logits, st, embed, h, vocab, dim, out_stride, g0, hg, ssq, nparts, nullptr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void decode_stream_tail_kernel(const float* __restrict__ logits, teo_decode_state st,
+                                                                  const T* __restrict__ embed, T* __restrict__ h, int vocab,
+                                                                  int dim, int out_stride, const T* __restrict__ g0,
+                                                                  T* __restrict__ hg, float* __restrict__ ssq, int nparts,
+                                                                  const int* __restrict__ d_limit) {
+    decode_tail_body<T, true>(logits, st, embed, h, vocab, dim, out_stride, g0, hg, ssq, nparts, d_limit);
+}
+
+int decode_stream_tail(const float* logits, const teo_decode_state* s, const int* d_limit, const void* embed, void* h, int vocab, int dim,
+                       int dtype, hipStream_t st, int batch, int out_stride, const void* g0, void* hg, float* ssq, int nparts) {
+    if (dtype == TEO_F32)
+        TEO_KLAUNCH((decode_stream_tail_kernel<float>), batch, 1024, 0, st, logits, *s, (const float*)embed, (float*)h, vocab, dim, out_stride,
+                    (const float*)g0, (float*)hg, ssq, nparts, d_limit);
+    else if (dtype == TEO_F16)
+        TEO_KLAUNCH((decode_stream_tail_kernel<f16_t>), batch, 1024, 0, st, logits, *s, (const f16_t*)embed, (f16_t*)h, vocab, dim, out_stride,
+                    (const f16_t*)g0, (f16_t*)hg, ssq, nparts, d_limit);
+    else
+        TEO_KLAUNCH((decode_stream_tail_kernel<bf16_t>), batch, 1024, 0, st, logits, *s, (const bf16_t*)embed, (bf16_t*)h, vocab, dim, out_stride,
+                    (const bf16_t*)g0, (bf16_t*)hg, ssq, nparts, d_limit);
+    TEO_LAUNCH_CHECK("decode_stream_tail");
+    return TEO_OK;
 }
 
 int decode_tail(const float* logits, const teo_decode_state* s, const void* embed, void* h, int vocab, int dim, int dtype,

@@ -55,6 +55,9 @@ int sample_topk(const float* logits, long long* tok, int vocab, float temperatur
 int decode_tail(const float* logits, const teo_decode_state* s, const void* embed, void* h, int vocab, int dim, int dtype,
                 hipStream_t st, int batch = 1, int out_stride = 0, const void* g0 = nullptr, void* hg = nullptr,
                 float* ssq = nullptr, int nparts = 0);
+// the stream step's tail (include/teo_hip.h teo_decode_stream_state): decode_tail + the per-slot limit, self-parking, inert parked slots
+int decode_stream_tail(const float* logits, const teo_decode_state* s, const int* d_limit, const void* embed, void* h, int vocab, int dim,
+                       int dtype, hipStream_t st, int batch, int out_stride, const void* g0, void* hg, float* ssq, int nparts);
 // speculative verify (include/teo_hip.h teo_verify_state): the step's tail and the n-gram proposer
 int verify_tail(const float* logits, const teo_verify_state* s, long long* sel, int vocab, hipStream_t st);
 int spec_propose(const long long* hist, const int* d_hist_len, long long* rows_out, int* d_n_draft, int rows, int ngram_max, hipStream_t st);

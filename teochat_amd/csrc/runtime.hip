@@ -319,8 +319,10 @@ int llama_prefill(const teo_llama_desc* d, const void* embeds, const int* positi
 // GEMMs run once over sum(S_b) rows (better tile quantisation than nseq separate M = S_b problems); RoPE + KV append and
 // the causal attention run per sequence on its row block and its own cache slot (slot b = cache pointer + b*cache_stride
 // elements, fresh caches: past = 0).  logits [nseq, vocab]: last position of every sequence.
+// slots != NULL (teo_llama_prefill_slots): sequence i goes into cache slot slots[i] instead of slot i -- the refill pass of the stream
+// decoder, every slot freed in a round in one pass over the weights.
 int llama_prefill_batch(const teo_llama_desc* d, const void* embeds, const int* seq_lens, int nseq, long long cache_stride,
-                        int last_only, float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states) {
+                        int last_only, float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, const int* slots) {
     int total = 0;
     for (int b = 0; b < nseq; ++b) {
         TEO_CHECK_ARG(seq_lens[b] >= 1 && seq_lens[b] <= d->max_seq, "teo_llama_prefill_batch: seq_lens[%d] = %d", b, seq_lens[b]);
@@ -348,9 +350,10 @@ int llama_prefill_batch(const teo_llama_desc* d, const void* embeds, const int* 
         for (int b = 0; b < nseq; ++b) {
             const int Sb = seq_lens[b];
             unsigned char* qkv_b = (unsigned char*)w.qkv + (size_t)row0 * QKV * e;
-            unsigned char* kc = (unsigned char*)d->k_cache[l] + (size_t)b * cache_stride * e;
-            unsigned char* vc = (unsigned char*)d->v_cache[l] + (size_t)b * cache_stride * e;
-            unsigned char* vtc = (unsigned char*)d->vt_cache[l] + (size_t)b * cache_stride * e;
+            const size_t slot = slots ? (size_t)slots[b] : (size_t)b;
+            unsigned char* kc = (unsigned char*)d->k_cache[l] + slot * cache_stride * e;
+            unsigned char* vc = (unsigned char*)d->v_cache[l] + slot * cache_stride * e;
+            unsigned char* vtc = (unsigned char*)d->vt_cache[l] + slot * cache_stride * e;
             TEO_TRY(rope_kv_append(qkv_b, QKV, nullptr, d->rope_cos, d->rope_sin, kc, vc, vtc, Sb, 0, nullptr, d->max_seq, H, Hk,
                                    hd, dt, st));
             teo_attn_args a;
@@ -648,11 +651,14 @@ static int decode_batch_layers(const teo_llama_desc* d, const BatchLoopOpts& o, 
     return TEO_OK;
 }
 
-int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
+// d_limit == NULL: the batched step.  d_limit != NULL: the stream step (teo_decode_stream_state) -- the same launches with the
+// self-parking tail; the attention kernels skip parked conversations (d_pos < 0) by themselves.
+static int decode_batch_step_impl(const teo_llama_desc* d, const teo_decode_batch_state* s, const int* d_limit, void* ws, size_t ws_bytes,
+                                  const char* who, hipStream_t st) {
     const int B = s->batch;
     const DecodeBatchWs w = decode_batch_carve(d, B, ws, ws_bytes);
     if (w.total > ws_bytes) {
-        set_error("teo_llama_decode_batch_step: workspace %zu < %zu", ws_bytes, w.total);
+        set_error("%s: workspace %zu < %zu", who, ws_bytes, w.total);
         return TEO_ERR_WORKSPACE;
     }
     const int dt = d->dtype;
@@ -666,12 +672,53 @@ int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_stat
     };
     bool skinny = false;
     const BatchLoopOpts o = {B, s->w_tiled != 0, s->gateup_block8 != 0, s->w_mxfp4 != 0};
-    TEO_TRY(decode_batch_layers(d, o, w, s->d_logits, attend, &skinny, "teo_llama_decode_batch_step", st));
+    TEO_TRY(decode_batch_layers(d, o, w, s->d_logits, attend, &skinny, who, st));
     const teo_decode_state t = batch_as_state(s);
     prof_class(TEO_PROF_TAIL);
+    if (d_limit) {
+        if (skinny)
+            return decode_stream_tail(s->d_logits, &t, d_limit, d->embed, w.h, d->vocab, D, dt, st, B, s->out_stride, d->in_norm_w[0], w.hg,
+                                      w.ssq, w.nparts);
+        return decode_stream_tail(s->d_logits, &t, d_limit, d->embed, w.h, d->vocab, D, dt, st, B, s->out_stride, nullptr, nullptr, nullptr, 0);
+    }
     if (skinny)
         return decode_tail(s->d_logits, &t, d->embed, w.h, d->vocab, D, dt, st, B, s->out_stride, d->in_norm_w[0], w.hg, w.ssq, w.nparts);
     return decode_tail(s->d_logits, &t, d->embed, w.h, d->vocab, D, dt, st, B, s->out_stride);
+}
+
+int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
+    return decode_batch_step_impl(d, s, nullptr, ws, ws_bytes, "teo_llama_decode_batch_step", st);
+}
+
+// ---- stream step: the batched step over slots that park themselves (include/teo_hip.h teo_decode_stream_state)
+static teo_decode_batch_state stream_as_batch(const teo_decode_stream_state* s) {
+    teo_decode_batch_state b;
+    b.batch = s->batch; b.out_stride = s->out_stride; b.cache_stride = s->cache_stride;
+    b.w_tiled = s->w_tiled; b.gateup_block8 = s->gateup_block8; b.w_mxfp4 = s->w_mxfp4;
+    b.d_token = s->d_token; b.d_pos = s->d_pos; b.d_out_tokens = s->d_out_tokens; b.d_out_count = s->d_out_count; b.d_stop = s->d_stop;
+    b.d_stop_ids = s->d_stop_ids; b.n_stop_ids = s->n_stop_ids; b.d_logits = s->d_logits;
+    b.do_sample = s->do_sample; b.top_k = s->top_k; b.temperature = s->temperature; b.d_rng = s->d_rng; b.top_p = s->top_p;
+    return b;
+}
+
+int llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
+    const teo_decode_batch_state b = stream_as_batch(s);
+    return decode_batch_step_impl(d, &b, s->d_limit, ws, ws_bytes, "teo_llama_decode_stream_step", st);
+}
+
+// row `slot` of the residual stream <- embed[d_token[slot]] (skinny path: also layer 0's norm inputs for that row).  No other row is
+// touched: the previous step's tail has prepared theirs.
+int llama_decode_stream_arm(const teo_llama_desc* d, const teo_decode_stream_state* s, int slot, void* ws, size_t ws_bytes, hipStream_t st) {
+    const DecodeBatchWs w = decode_batch_carve(d, s->batch, ws, ws_bytes);
+    if (w.total > ws_bytes) {
+        set_error("teo_llama_decode_stream_arm: workspace %zu < %zu", ws_bytes, w.total);
+        return TEO_ERR_WORKSPACE;
+    }
+    const size_t row = (size_t)slot * d->hidden * esize(d->dtype);
+    if (batch_uses_skinny(d, s->batch, s->w_mxfp4 != 0))
+        return embed_token_emit(s->d_token + slot, d->embed, (unsigned char*)w.h + row, d->hidden, d->dtype, st, 1, d->in_norm_w[0],
+                                (unsigned char*)w.hg + row, w.ssq + (size_t)slot * w.nparts, w.nparts);
+    return embed_token(s->d_token + slot, d->embed, (unsigned char*)w.h + row, d->hidden, d->dtype, st, 1);
 }
 
 // h <- embed[*d_token]: arms the first step of a generation (later steps get it from the previous step's tail)
@@ -836,6 +883,11 @@ int decode_graph_create(const teo_llama_desc* d, const teo_decode_state* s, void
 int decode_batch_graph_create(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes,
                               hipStream_t st, teo_graph** out) {
     return capture_graph(st, [&]() { return llama_decode_batch_step(d, s, ws, ws_bytes, st); }, out);
+}
+
+int decode_stream_graph_create(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
+                               teo_graph** out) {
+    return capture_graph(st, [&]() { return llama_decode_stream_step(d, s, ws, ws_bytes, st); }, out);
 }
 
 int llama_verify_step_profile(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, float* ms_out, int* count_out,

@@ -60,14 +60,23 @@ def run_inference_single(model, processor, tokenizer, inp, image_paths, conv_mod
 
 def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, conv_mode="v1", timestamps_list=None,
                         prompt_strategy="interleave", chronological_prefix=True, temperature=0.2, max_new_tokens=256,
-                        do_sample=True):
+                        do_sample=True, continuous=False, slots=None):
     """run_inference_single for up to 16 examples at once (not in the reference, whose loop is one example at a time,
     inference.py:100-113): the same prompt construction, frame order, tokenisation and stop keyword per example, then ONE
     batched generation -- every frame of every example through the tower together, one prefill per example, and a decode loop
     that streams each weight matrix once per step for all examples (LlavaLlamaForCausalLM.generate_batch).  Greedy decoding
     gives the single-example answers; sampling draws from per-example Philox streams seeded from torch's global generator,
-    so a sampled run is reproducible under torch.manual_seed but is not the single-example loop's stream."""
+    so a sampled run is reproducible under torch.manual_seed but is not the single-example loop's stream.
+
+    continuous=True (extra trailing keyword): ANY number of examples through one LlavaLlamaForCausalLM.generate_stream over
+    `slots` (default min(number of examples, 16)) conversation slots -- a slot whose answer has finished is refilled with the next
+    example instead of idling until the longest answer of its group ends.  The same prompts, frames and stop keywords, each
+    prepared when its example is admitted to a slot (inps, image_paths_list and timestamps_list may be lazy sequences); greedy
+    answers equal the static path's, sampled ones draw from per-EXAMPLE Philox streams."""
     B = len(inps)
+    if continuous:
+        return _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, conv_mode, timestamps_list, prompt_strategy,
+                                     chronological_prefix, temperature, max_new_tokens, do_sample, slots)
     if timestamps_list is None:
         timestamps_list = [[] for _ in range(B)]
     if len(image_paths_list) != B or len(timestamps_list) != B:
@@ -88,6 +97,62 @@ def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, con
         outs = model.generate_batch(ids_list, frames_list, do_sample=do_sample, temperature=temperature,
                                     max_new_tokens=max_new_tokens, stopping_criteria=crits)
     return [tokenizer.decode(o[n:]).replace("</s>", "").strip() for o, n in zip(outs, n_prompt)]
+
+
+class _Prepared:
+    """Example i's (input ids, frames, criteria), built when first asked for; the last `keep` examples are kept, so that the ids, the
+    frames and the criteria of one example come from one preparation while no more than a lookahead of them is held."""
+
+    def __init__(self, prepare, n, keep):
+        self.prepare, self.n, self.keep, self.cache = prepare, n, keep, {}
+
+    def get(self, i):
+        if i not in self.cache:
+            self.cache[i] = self.prepare(i)
+            for j in list(self.cache)[:-self.keep]:          # insertion order: the oldest preparations go
+                del self.cache[j]
+        return self.cache[i]
+
+    def column(self, k):
+        outer = self
+
+        class Column:
+            def __len__(self):
+                return outer.n
+
+            def __getitem__(self, i):
+                return outer.get(i)[k]
+        return Column()
+
+
+def _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, conv_mode, timestamps_list, prompt_strategy,
+                          chronological_prefix, temperature, max_new_tokens, do_sample, slots):
+    N = len(inps)
+    if N == 0:
+        return []
+    if len(image_paths_list) != N or (timestamps_list is not None and len(timestamps_list) != N):
+        raise ValueError("run_inference_batch: one image list and one timestamp list per question")
+    slots = min(N, 16) if slots is None else int(slots)
+    n_prompt = {}
+
+    def prepare(i):
+        image_paths = image_paths_list[i]
+        timestamps = timestamps_list[i] if timestamps_list is not None else []
+        if len(timestamps) > 0:
+            order = sorted(range(len(image_paths)), key=lambda k: datetime.strptime(timestamps[k], "%Y-%m-%d"))
+            image_paths = [image_paths[k] for k in order]
+        frames = [processor.preprocess(p, return_tensors="pt")["pixel_values"][0] for p in image_paths]
+        frames = [f.to(model.device, dtype=model.dtype) for f in frames]
+        prompt, stop_str = build_prompt(inps[i], image_paths, conv_mode, prompt_strategy, chronological_prefix)
+        input_ids = tokenizer_image_token(prompt, tokenizer, IMAGE_TOKEN_INDEX, return_tensors="pt").unsqueeze(0).to(model.device)
+        n_prompt[i] = input_ids.shape[1]
+        return input_ids[0], frames, [KeywordsStoppingCriteria([stop_str], tokenizer, input_ids)]
+
+    prepared = _Prepared(prepare, N, 2 * slots)
+    with torch.inference_mode():
+        outs = model.generate_stream(prepared.column(0), prepared.column(1), slots=slots, do_sample=do_sample, temperature=temperature,
+                                     max_new_tokens=max_new_tokens, stopping_criteria=prepared.column(2))
+    return [tokenizer.decode(o[n_prompt[i]:]).replace("</s>", "").strip() for i, o in enumerate(outs)]
 
 
 _BBOX = re.compile(r"\[(\d+), (\d+), (\d+), (\d+)\]")
@@ -117,14 +182,33 @@ def _record(example, response, dataset):
 
 
 def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronological_prefix, conv_mode, temperature,
-                  max_new_tokens, batch_size=1):
+                  max_new_tokens, batch_size=1, continuous=False):
     """Dataset loop with the bookkeeping the metrics need (inference.py:88-137): response / ground truth / task per example,
     the example's polygon when it has one, and the integer boxes quoted in the question and in the reference answer.
     batch_size (extra trailing keyword, default 1 = the reference's loop): answer that many consecutive examples per
-    generation (run_inference_batch, <= 16); the records come out in dataset order either way."""
+    generation (run_inference_batch, <= 16); the records come out in dataset order either way.
+    continuous=True (extra trailing keyword, default off): the whole dataset goes through ONE generate_stream over batch_size
+    conversation slots (run_inference_batch(continuous=True)); examples are read and prepared as slots free up."""
     if not 1 <= int(batch_size) <= 16:
         raise ValueError(f"batch_size {batch_size}: 1..16 examples per generation")
     outputs = []
+    if continuous:
+        n = len(dataset)
+
+        class Field:
+            def __init__(self, get):
+                self.get = get
+
+            def __len__(self):
+                return n
+
+            def __getitem__(self, i):
+                return self.get(dataset[i])
+        responses = run_inference_batch(model, processor, tokenizer, Field(lambda e: e["conversations"][0]["value"]),
+                                        Field(lambda e: e["video"]), conv_mode=conv_mode, timestamps_list=Field(lambda e: e["timestamp"]),
+                                        prompt_strategy=prompt_strategy, chronological_prefix=chronological_prefix, temperature=temperature,
+                                        max_new_tokens=max_new_tokens, continuous=True, slots=int(batch_size))
+        return [_record(dataset[i], r, dataset) for i, r in enumerate(responses)]
     if batch_size == 1:
         for example in dataset:
             response = run_inference_single(model, processor, tokenizer, example["conversations"][0]["value"], example["video"],

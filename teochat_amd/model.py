@@ -765,6 +765,142 @@ class LlavaLlamaForCausalLM:
         return [torch.cat([input_ids_list[b].view(-1), torch.tensor(new_tokens[b], dtype=input_ids_list[b].dtype,
                                                                      device=input_ids_list[b].device)]) for b in range(B)]
 
+    # --- continuous batching: the batched step over slots that park when they finish and are refilled from a queue of requests
+    def stream_decoder(self, slots, max_new=1024):
+        from .stream import StreamDecoder
+        bd = self.batch_decoder(slots, max_new)   # its caches and weight copies are shared: no second copy of the weights
+        cur = getattr(self, "_stream_decoder", None)
+        if cur is None or cur.bd is not bd:
+            cur = StreamDecoder(self.engine, slots, max_new=bd.max_new, batch_decoder=bd)
+            self._stream_decoder = cur
+        return cur
+
+    @torch.no_grad()
+    def generate_stream(self, *args, **kwargs):
+        with self.engine.phase():
+            return self._generate_stream(*args, **kwargs)
+
+    def _generate_stream(self, input_ids_list, images_list=None, slots=8, max_new_tokens=20, do_sample=False, temperature=None,
+                         top_k=None, top_p=None, stopping_criteria=None, eos_token_id="config", generator=None, chunk=16):
+        """Answer N requests (any N >= 1) over `slots` <= 16 conversation slots of the batched decode step: a slot whose request has
+        finished parks -- the attention kernels skip it -- and is refilled with the next request, so a step's work follows the requests
+        that are still being answered instead of the longest answer of a fixed group (teochat_amd/stream.py).
+
+        input_ids_list / images_list / stopping_criteria: one entry per request, as generate_batch() takes them; any sequence with
+        len() and [] will do -- entry i is read when request i is admitted to a slot, so a lazy sequence keeps only the requests in
+        flight in memory.  max_new_tokens: an int or one int per request.  Returns N 1-D tensors prompt + generated in request order,
+        each cut at its own stop: greedy, exactly what generate_batch() returns for that request in a group of `slots` conversations.
+        Sampling: request i draws from the Philox stream seeded by (the generator's seed, i), so a sampled answer does not depend on
+        slots, chunk or the slot the request landed in.  The device stop is armed while every admitted request's stop candidates
+        (keyword id lists and EOS, folded as generate() folds them) are one and the same id sequence; otherwise the host applies the
+        criteria once per chunk, at the exact token.  `last_generation_stats` = {requests, steps, live_slot_steps, slot_steps,
+        prefill_passes} afterwards."""
+        from .stream import request_seed, run_stream
+        N = len(input_ids_list)
+        slots = int(slots)
+        if N < 1:
+            raise ValueError("generate_stream: no requests")
+        if not 1 <= slots <= L.MAX_DECODE_BATCH:
+            raise ValueError(f"slots {slots} outside 1..{L.MAX_DECODE_BATCH}")
+        if eos_token_id == "config":
+            eos_token_id = self._config_eos()
+        max_new = [int(max_new_tokens)] * N if isinstance(max_new_tokens, int) else [int(m) for m in max_new_tokens]
+        if len(max_new) != N:
+            raise ValueError("max_new_tokens must be an int or hold one int per request")
+        if stopping_criteria is not None and len(stopping_criteria) != N:
+            raise ValueError("stopping_criteria must hold one list per request")
+        gc = self.generation_config
+        temperature = float(getattr(gc, "temperature", 1.0) or 1.0) if temperature is None else temperature
+        top_k = getattr(gc, "top_k", 50) if top_k is None else top_k
+        top_p = getattr(gc, "top_p", 1.0) if top_p is None else top_p
+        tp = 1.0 if (top_p is None or not do_sample) else float(top_p)
+        k = int(top_k or 0) if do_sample else 0
+        base_seed = 0
+        if do_sample:
+            base_seed = generator.initial_seed() if generator is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+        eng = self.engine
+        dec = self.stream_decoder(slots, max(max(max_new), 1))
+        dec.reset()
+        ids_of, crits_of = {}, {}                 # the requests in flight (and, for ids, the finished ones: a few integers each)
+        dev_stop = {"ids": None, "off": False}    # the device stop: one id sequence shared by every request admitted so far, or off
+
+        def stop_candidates(r):
+            cands = [ids for c in crits_of[r] for ids in getattr(c, "keyword_id_lists", []) if ids]
+            if eos_token_id is not None:
+                cands.append([int(eos_token_id)])
+            uniq = []
+            for ids in cands:
+                ids = [int(t) for t in ids]
+                if ids not in uniq:
+                    uniq.append(ids)
+            return uniq
+
+        def admit(reqs, slot_list):
+            B = len(reqs)
+            rows, flat = [], []
+            for r in reqs:
+                ids_of[r] = input_ids_list[r].view(-1)
+                crits_of[r] = list(stopping_criteria[r]) if stopping_criteria is not None else []
+                rows.append(ids_of[r])
+                imgs = images_list[r] if images_list is not None else None
+                if imgs is not None:
+                    flat.extend(list(imgs))
+                uniq = stop_candidates(r)
+                if not dev_stop["off"]:
+                    if len(uniq) == 1 and dev_stop["ids"] in (None, uniq[0]):
+                        dev_stop["ids"] = uniq[0]
+                    else:
+                        dev_stop["off"] = True
+            dec.configure(None if dev_stop["off"] else dev_stop["ids"], do_sample=do_sample, temperature=temperature, top_k=k, top_p=tp)
+            # one multimodal preparation for the round, as generate_batch() does it for a group
+            dev_ids = rows[0].device
+            width = max(int(ids.numel()) for ids in rows)
+            ids_p = torch.zeros(B, width, dtype=torch.long, device=dev_ids)
+            mask_p = torch.zeros(B, width, dtype=torch.long, device=dev_ids)
+            for b, ids in enumerate(rows):
+                ids_p[b, :ids.numel()] = ids
+                mask_p[b, :ids.numel()] = 1
+            (_, _, new_mask, _, embeds, _) = self.prepare_inputs_labels_for_multimodal(ids_p, None, mask_p, None, None, flat or None)
+            if embeds is None:
+                embeds, new_mask = self.get_model().embed_tokens(ids_p), mask_p
+            seqs = []
+            for b, r in enumerate(reqs):
+                on = torch.nonzero(new_mask[b].to(torch.bool), as_tuple=False).flatten()
+                lo, hi = int(on[0]), int(on[-1]) + 1
+                if max_new[r] > 0 and hi - lo + max_new[r] > eng.max_seq:
+                    raise ValueError(f"request {r}: prompt ({hi - lo}) + max_new_tokens ({max_new[r]}) exceeds max_seq {eng.max_seq}")
+                seqs.append(embeds[b, lo:hi])
+            logits = dec.refill(slot_list, seqs)
+            out = []
+            for b, r in enumerate(reqs):
+                seed = request_seed(base_seed, r)
+                first = eng.sample(logits[b], temperature, k, seed, 0, top_p=tp) if do_sample else self._argmax(logits[b])
+                out.append((first, min(max_new[r] - 1, eng.max_seq - int(seqs[b].shape[0])), seed))
+            return out
+
+        def host_done(r, toks):
+            if eos_token_id is not None and toks[-1] == eos_token_id:
+                return True
+            if crits_of[r]:
+                row = torch.cat([ids_of[r].cpu(), torch.tensor(toks, dtype=torch.long)]).unsqueeze(0)
+                return any(bool(c(row, None)) for c in crits_of[r])
+            return False
+
+        todo = [r for r in range(N) if max_new[r] > 0]
+        results, stats = run_stream(dec, len(todo), slots, lambda reqs, sl: admit([todo[i] for i in reqs], sl),
+                                    lambda i, toks: host_done(todo[i], toks), chunk=chunk) if todo else ([], None)
+        outs = []
+        new_of = {todo[i]: toks for i, toks in enumerate(results)}
+        for r in range(N):
+            ids = ids_of[r] if r in ids_of else input_ids_list[r].view(-1)
+            new = new_of.get(r, [])
+            outs.append(torch.cat([ids, torch.tensor(new, dtype=ids.dtype, device=ids.device)]) if new else ids.clone())
+        if stats is None:
+            stats = dict(requests=0, steps=0, live_slot_steps=0, slot_steps=0, prefill_passes=0)
+        stats["requests"] = N
+        self.last_generation_stats = stats
+        return outs
+
     def _config_eos(self):
         """GenerationMixin semantics: generation_config.eos_token_id (generation_config.json of the checkpoint, or of model_base
         on the LoRA / projector branches) wins; config.json's eos_token_id is what generation_config is seeded from."""

@@ -1,0 +1,309 @@
+"""Continuous batching: the batched decode step over SLOTS that finish, park and are refilled independently.
+
+`generate_batch` steps a group of B conversations until its longest answer has finished, and a finished conversation keeps
+streaming its KV cache through the attention kernel.  Here a slot that finishes PARKS (d_pos < 0: the attention kernels skip it,
+include/teo_hip.h teo_attn_decode) -- by itself, inside a chunk of graph replays, when its stop ids matched or its own limit is
+reached (teo_decode_stream_state) -- and the host refills parked slots from a queue of requests: one prefill pass for all slots
+freed in a round (teo_llama_prefill_slots), one arm call per slot (teo_llama_decode_stream_arm), and the step goes on.  A live
+slot's arithmetic is the batched step's, bit for bit.
+
+  StreamDecoder  the device side: a BatchDecoder's caches, descriptors and weight copies + d_limit, the stream state and its graph
+  run_stream     the scheduler loop over anything with StreamDecoder's methods (the host tests drive it with a fake)
+"""
+import ctypes as C
+from collections import deque
+
+import torch
+
+from . import _lib as L
+from .engine import _p
+
+SEED_STRIDE = 0x9E3779B97F4A7C15              # request i draws from the Philox stream seeded (base + i * SEED_STRIDE) mod 2^63
+
+
+def request_seed(base_seed, i):
+    return (int(base_seed) + SEED_STRIDE * int(i)) & (2 ** 63 - 1)
+
+
+class StreamDecoder:
+    """`slots` conversation slots over one engine.  batch_decoder: a BatchDecoder of that engine with B == slots whose caches, per-slot
+    descriptors and tiled weight copies are borrowed (no second copy of the weights; its own begin()/steps() state is invalidated by a
+    refill here); left out, one is created and owned."""
+
+    def __init__(self, engine, slots, max_new=1024, batch_decoder=None):
+        from .batch import BatchDecoder
+        slots = int(slots)
+        if not 1 <= slots <= L.MAX_DECODE_BATCH:
+            raise ValueError(f"slots {slots} outside 1..{L.MAX_DECODE_BATCH}")
+        bd = batch_decoder
+        if bd is None:
+            bd = BatchDecoder(engine, slots, max_new=max(int(max_new), 64))
+        if bd.eng is not engine or bd.B != slots:
+            raise ValueError("batch_decoder belongs to another engine or has another number of slots")
+        if bd.max_new < int(max_new):
+            raise ValueError(f"batch_decoder's output buffer ({bd.max_new} tokens) is below max_new {max_new}")
+        self.eng, self.lib, self.bd, self.B = engine, engine.lib, bd, slots
+        self.tune = engine.tune
+        self.max_new = bd.max_new
+        dev = engine.device
+        self.d_limit = torch.ones(slots, dtype=torch.int32, device=dev)
+        s = L.DecodeStreamState()
+        for name, _ in L.DecodeBatchState._fields_:
+            setattr(s, name, getattr(bd.state, name))
+        s.n_stop_ids, s.do_sample, s.top_k, s.temperature, s.top_p = 0, 0, 0, 1.0, 1.0
+        s.d_limit = self.d_limit.data_ptr()
+        self.state = s
+        self._graph = None
+        self._graph_ws = None
+        # the step's workspace holds the slots' residual rows BETWEEN steps: this decoder's own, never a buffer another decoder writes
+        self._ws = torch.empty(max(int(self.lib.teo_llama_decode_stream_workspace_bytes(C.byref(bd.desc), slots)), 256), dtype=torch.uint8, device=dev)
+        import weakref
+        me = weakref.ref(self)
+
+        def _changed(*_):                        # a knob (tune_set) or an option (set_options): the captured step keeps its capture's choices
+            o = me()
+            if o is not None:
+                o._drop_graph()
+        engine._tune_hooks.append(_changed)
+        engine._option_hooks.append(_changed)
+        self.reset()
+
+    # ------------------------------------------------------------------ state
+    def reset(self):
+        """Every slot parked and free; counters zeroed."""
+        bd = self.bd
+        with self.eng.phase():
+            bd.d_pos.fill_(-1)
+            bd.d_count.zero_()
+            bd.d_stop.fill_(1)
+            bd.d_token.zero_()
+            self.d_limit.fill_(1)
+        bd.reset()
+        ws = self._workspace()                   # a fresh workspace holds anything: give every row of the residual stream a finite start
+        with self.eng.phase() as st:
+            for slot in range(self.B):
+                L.check(self.lib.teo_llama_decode_stream_arm(C.byref(bd.desc), C.byref(self.state), slot, _p(ws), ws.numel(), st),
+                        "teo_llama_decode_stream_arm")
+        self.live = [False] * self.B             # armed and not yet seen parked by poll() / parked by park()
+        self.pos = [-1] * self.B                 # host mirror of d_pos / d_out_count as of the last poll
+        self.count = [0] * self.B
+        self._stats = dict(steps=0, slot_steps=0, live_slot_steps=0, prefill_passes=0, arms=0)
+
+    def configure(self, stop_ids=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0):
+        """The step's shared options: the device stop (an id sequence every live slot stops on, or None) and the sampler."""
+        s, bd = self.state, self.bd
+        n = 0
+        with self.eng.phase():
+            if stop_ids:
+                n = min(len(stop_ids), 16)
+                bd.d_stop_ids[:n] = torch.tensor(list(stop_ids)[-n:], dtype=torch.int64, device=self.eng.device)
+        key = (n, int(bool(do_sample)), int(top_k or 0), C.c_float(float(temperature)).value, C.c_float(float(top_p or 1.0)).value)
+        if key != (s.n_stop_ids, s.do_sample, s.top_k, float(s.temperature), float(s.top_p)):
+            s.n_stop_ids, s.do_sample, s.top_k, s.temperature, s.top_p = key
+            self._drop_graph()
+
+    def _workspace(self):
+        return self._ws
+
+    def residual_rows(self):
+        """Views of the step's hand-over state in the workspace, as the library carves it (csrc/runtime.hip decode_batch_carve: h, hg,
+        ssq first, each padded to 256 bytes): h [B, D] the residual stream, hg [B, D] and ssq [B, ceil(D / 16)] layer 0's norm inputs
+        on the skinny path (unused otherwise).  For inspection and the tests."""
+        ws, D = self._workspace(), self.eng.cfg.hidden_size
+        e = torch.empty(0, dtype=self.eng.dtype).element_size()
+        row = (self.B * D * e + 255) // 256 * 256
+        nparts = (D + 15) // 16
+        h = ws[:self.B * D * e].view(self.eng.dtype).view(self.B, D)
+        hg = ws[row:row + self.B * D * e].view(self.eng.dtype).view(self.B, D)
+        ssq = ws[2 * row:2 * row + self.B * nparts * 4].view(torch.float32).view(self.B, nparts)
+        return h, hg, ssq
+
+    def _drop_graph(self):
+        if self._graph is not None:
+            self.lib.teo_graph_destroy(self._graph)
+            self._graph = None
+
+    # ------------------------------------------------------------------ refill + arm
+    def refill(self, slot_list, embeds_list, last_only=True):
+        """Prefill embeds_list[i] ([S_i, D]) into cache slot slot_list[i] from position 0: ONE pass over the weights for all of them
+        (teo_llama_prefill_slots).  Returns the fp32 last-position logits [len(slot_list), V]."""
+        eng, bd = self.eng, self.bd
+        slot_list = [int(s) for s in slot_list]
+        if len(slot_list) != len(embeds_list) or not slot_list:
+            raise ValueError("refill: one sequence per slot, at least one")
+        if len(set(slot_list)) != len(slot_list) or min(slot_list) < 0 or max(slot_list) >= self.B:
+            raise ValueError(f"refill: slots {slot_list} are not distinct numbers in 0..{self.B - 1}")
+        if any(self.live[s] for s in slot_list):
+            raise ValueError(f"refill: slot(s) {[s for s in slot_list if self.live[s]]} are live")
+        lens = [int(e.shape[0]) for e in embeds_list]
+        if min(lens) < 1 or max(lens) > eng.max_seq:
+            raise ValueError(f"sequence lengths {lens} outside 1..max_seq {eng.max_seq}")
+        total, n = sum(lens), len(lens)
+        with eng.phase() as st:
+            rows = torch.cat([e.to(device=eng.device, dtype=eng.dtype) for e in embeds_list], dim=0).contiguous()
+            logits = torch.empty(n if last_only else total, eng.cfg.vocab_size, dtype=torch.float32, device=eng.device)
+            eng._flush_handoff_checks("prefill")
+            d0 = bd.slot_desc[0]
+            ws = eng._workspace("prefill", self.lib.teo_llama_prefill_workspace_bytes(C.byref(d0), total))
+            L.check(self.lib.teo_llama_prefill_slots(C.byref(d0), _p(rows), (C.c_int * n)(*lens), (C.c_int * n)(*slot_list), n,
+                                                     bd.k_cache.stride(1), 1 if last_only else 0, _p(logits), _p(ws), ws.numel(), st, None),
+                    "teo_llama_prefill_slots")
+            sid = C.c_void_p(eng.stream.cuda_stream)
+            eng._check_handoffs("prefill", lambda f: self.lib.teo_llama_prefill_workspace_status(C.byref(d0), total, _p(ws), ws.numel(), C.byref(f), sid),
+                                "teo_llama_prefill_slots")
+        for s, n_ in zip(slot_list, lens):
+            bd.cache_len[s] = n_
+        bd._armed = False
+        self._stats["prefill_passes"] += 1
+        return logits
+
+    def arm(self, slot, first_token, seed=0, limit=1, draws_done=1):
+        """Make `slot` live: its next step takes first_token at position cache length; it parks itself after `limit` steps (or on the
+        device stop).  Touches no other slot's state and no other row of the residual stream."""
+        slot, limit = int(slot), int(limit)
+        bd, eng = self.bd, self.eng
+        if self.live[slot]:
+            raise ValueError(f"arm: slot {slot} is live")
+        pos = bd.cache_len[slot]
+        if not 1 <= limit <= self.max_new:
+            raise ValueError(f"arm: limit {limit} outside 1..{self.max_new} (the output buffer)")
+        if pos < 1 or pos + limit > eng.max_seq:
+            raise ValueError(f"arm: position {pos} + limit {limit} exceeds max_seq {eng.max_seq} (or the slot was never refilled)")
+        ws = self._workspace()
+        with eng.phase() as st:
+            bd.d_token[slot] = int(first_token)
+            bd.d_pos[slot] = pos
+            bd.d_count[slot] = 0
+            bd.d_stop[slot] = 0
+            self.d_limit[slot] = limit
+            bd.d_rng[slot] = torch.tensor([int(seed) & (2 ** 63 - 1), int(draws_done)], dtype=torch.int64, device=eng.device)
+            L.check(self.lib.teo_llama_decode_stream_arm(C.byref(bd.desc), C.byref(self.state), slot, _p(ws), ws.numel(), st),
+                    "teo_llama_decode_stream_arm")
+        self.live[slot] = True
+        self.pos[slot], self.count[slot] = pos, 0
+        self._stats["arms"] += 1
+
+    # ------------------------------------------------------------------ step
+    def steps(self, n, use_graph=True):
+        """n stream steps: every live slot advances until it parks itself; parked slots cost their GEMM rows only."""
+        eng, bd = self.eng, self.bd
+        n = int(n)
+        ws = self._workspace()
+        with eng.phase() as st:
+            if use_graph:
+                if self._graph is None or self._graph_ws != ws.data_ptr():
+                    self._drop_graph()
+                    g = C.c_void_p()
+                    L.check(self.lib.teo_llama_decode_stream_graph_create(C.byref(bd.desc), C.byref(self.state), _p(ws), ws.numel(), st,
+                                                                          C.byref(g)), "teo_llama_decode_stream_graph_create")
+                    self._graph, self._graph_ws = g, ws.data_ptr()
+                L.check(self.lib.teo_graph_launch(self._graph, n, st), "teo_graph_launch")
+                eng.stream.synchronize()          # drain the replays before anything is queued behind them (engine.py _Phase.__exit__)
+            else:
+                for _ in range(n):
+                    L.check(self.lib.teo_llama_decode_stream_step(C.byref(bd.desc), C.byref(self.state), _p(ws), ws.numel(), st),
+                            "teo_llama_decode_stream_step")
+        self._stats["steps"] += n
+        self._stats["slot_steps"] += n * self.B
+
+    def poll(self):
+        """One small device-to-host copy of d_pos / d_out_count.  Returns the slots that were live and have parked since the last poll
+        (their final position is -1 - d_pos); `pos` / `count` mirror the device afterwards."""
+        bd = self.bd
+        with self.eng.phase():
+            both = torch.stack([bd.d_pos, bd.d_count]).cpu()
+        pos, cnt = both[0].tolist(), both[1].tolist()
+        parked = []
+        for s in range(self.B):
+            if self.live[s]:
+                self._stats["live_slot_steps"] += cnt[s] - self.count[s]
+                if pos[s] < 0:
+                    self.live[s] = False
+                    parked.append(s)
+            self.pos[s], self.count[s] = pos[s], cnt[s]
+        return parked
+
+    def tokens(self, slot, start=0):
+        """The tokens slot `slot` has produced by steps (its first token excluded), from index `start`, as of the last poll."""
+        n = self.count[slot]
+        if start >= n:
+            return []
+        with self.eng.phase():
+            return self.bd.d_out[slot, start:n].tolist()
+
+    def park(self, slot):
+        """Park a live slot from the host (a host-side criterion fired).  The next steps skip it."""
+        slot = int(slot)
+        if not self.live[slot]:
+            return
+        with self.eng.phase():
+            p = int(self.bd.d_pos[slot].item())
+            if p >= 0:
+                self.bd.d_pos[slot] = -1 - p
+                self.bd.d_stop[slot] = 1
+                self.pos[slot] = -1 - p
+        self.live[slot] = False
+
+    def stats(self):
+        return dict(self._stats)
+
+    def __del__(self):
+        try:
+            self._drop_graph()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def run_stream(dec, n_requests, slots, admit, host_done, chunk=16):
+    """The scheduler.  dec: refill / arm / steps / poll / tokens / park as StreamDecoder has them.
+      admit(reqs, slot_list) -> per request (first_token, limit, seed): runs the tower over the requests' frames in one call, ONE
+                                dec.refill(slot_list, ...) pass and picks the first tokens; limit = steps the slot may run (<= 0: none)
+      host_done(req, tokens) -> True when the host criteria stop request `req` at the last of `tokens`
+    Requests are taken in order; one that is finished at its first token is completed on the spot and its slot stays free.  Returns
+    (tokens per request, stats)."""
+    queue = deque(range(int(n_requests)))
+    free = list(range(int(slots)))
+    live = {}                                     # slot -> [request, tokens, limit]
+    results = [None] * int(n_requests)
+    stats = dict(requests=int(n_requests), steps=0, live_slot_steps=0, slot_steps=0, prefill_passes=0)
+    while queue or live:
+        while queue and free:
+            take = min(len(queue), len(free))
+            reqs = [queue.popleft() for _ in range(take)]
+            sl = free[:take]
+            firsts = admit(reqs, sl)
+            stats["prefill_passes"] += 1
+            for r, s, (tok, limit, seed) in zip(reqs, sl, firsts):
+                toks = [int(tok)]
+                if limit <= 0 or host_done(r, toks):
+                    results[r] = toks             # finished at its first token: never armed
+                    continue
+                if s in live:
+                    raise RuntimeError(f"slot {s} armed while live")
+                dec.arm(s, tok, seed, limit)
+                live[s] = [r, toks, int(limit)]
+                free.remove(s)
+        if not live:
+            continue
+        n = min(int(chunk), max(lim - (len(toks) - 1) for _, toks, lim in live.values()))
+        dec.steps(n)
+        stats["steps"] += n
+        stats["slot_steps"] += n * int(slots)
+        parked = set(dec.poll())
+        for s in sorted(live):
+            r, toks, lim = live[s]
+            fired = False
+            for t in dec.tokens(s, len(toks) - 1):
+                toks.append(int(t))
+                stats["live_slot_steps"] += 1
+                if host_done(r, toks):
+                    fired = True
+                    break
+            if fired and s not in parked:
+                dec.park(s)
+            if fired or s in parked:
+                results[r] = toks
+                del live[s]
+                free.append(s)
+        free.sort()
+    return results, stats
