@@ -9,7 +9,13 @@ Here every operand of an entry point is carved from the middle of a guarded aren
 Every case asserts the same three things: (1) `.check()` on every output arena, (2) the view is BIT-identical to the same ABI call (same
 knobs) on ordinary contiguous, unpoisoned tensors -- whose correctness the value tests establish; no tolerance is added here --, and
 (3) where a kernel is forced, teo_last_kernel() names it (the rule of tests/test_gemm_fuzz_gpu.py).  Nothing here is meant to fault: the
-guards are what keeps a wrong store inside memory the test owns.  tests/test_arena_host.py shows that the arena itself can fail."""
+guards are what keeps a wrong store inside memory the test owns.  tests/test_arena_host.py shows that the arena itself can fail.
+
+The verify, stream and proposer cases run on tinyB515, a configuration local to this file: tinyB's shapes at vocab_size 515 = 32 x 16 + 3.
+It exists because every other model-level test uses a vocabulary that is a multiple of 4 (300, 512, 32000): at 515 the tiled lm_head has
+a ragged 16-row tile, the tails' float4 loops leave a remainder of 3, and rows b >= 1 of the [B, 515] fp32 logits are only 4-byte aligned
+(the reference's builder resizes the embeddings to 32002, 32004 or 32006).  tests/test_containment_table.py keeps this file in step with
+the header."""
 import ctypes as C
 import functools
 import itertools
@@ -1044,15 +1050,37 @@ _VARIANTS = {"bf16": (BF, None, {}), "fp16": (HF, None, {}), "fp32": (F32, None,
              "mxfp4": (BF, "mxfp4", {"prefill_mxfp4": True}), "mxfp4_a8": (BF, "mxfp4", {"prefill_mxfp4": True, "prefill_mxfp4_a8": True})}
 
 
+# Configurations that exist for this file and tests/test_ragged_vocab_gpu.py only (NOT in tests/_tiny.py::TINY, which is tied to the
+# golden generator): a tiny configuration at vocab_size 515 = 32 x 16 + 3 -- a ragged 16-row tile of the tiled lm_head, a remainder loop
+# of 3 behind the float4 loops of the tails, and rows of the [B, 515] fp32 logits that are only 4-byte aligned.  The verify, stream and
+# proposer cases below run on tinyB515; tinyC515 is the anchored form (tests/_tiny.py::apply_anchors) with its 16 anchors on the LAST 16
+# ids, 499 .. 514, so that the successor cycle walks through the remainder columns 512, 513 and 514.
+RAGGED_VOCAB = 515
+_LOCAL_TINY = {"tinyB515": ("tinyB", None), "tinyC515": ("tinyC", dict(count=16, base=RAGGED_VOCAB - 16, embed_scale=0.3, gain=2.0, seed=77))}
+
+
+@functools.lru_cache(maxsize=None)
+def _tiny(name):
+    """(vit kwargs, llm kwargs, fp32 state dict) of a configuration of tests/_tiny.py or of _LOCAL_TINY"""
+    from oracle import teo_oracle as O
+    from tests import _tiny as TY
+    if name in TY.TINY:
+        return TY.TINY[name]["vit"], TY.TINY[name]["llm"], TY.state_dict(name)
+    base, anchors = _LOCAL_TINY[name]
+    vit, llm = TY.TINY[base]["vit"], dict(TY.TINY[base]["llm"], vocab_size=RAGGED_VOCAB)
+    v, l = O.VitCfg(**vit), O.LlamaCfg(**llm)
+    sd = O.make_state_dict(v, l, O.MMCfg(mm_hidden_size=v.hidden_size), seed=2, std=TY.TINY_STD)
+    return vit, llm, (TY.apply_anchors(sd, anchors) if anchors else sd)
+
+
 @functools.lru_cache(maxsize=None)
 def _engine(variant, name="tinyB"):
     from teochat_amd.config import LlavaConfig, VisionConfig
     from teochat_amd.engine import TeoEngine
-    from tests import _tiny as TY
     dt, wf, opts = _VARIANTS[variant]
-    t = TY.TINY[name]
-    cfg = LlavaConfig(**t["llm"], mm_hidden_size=t["vit"]["hidden_size"], max_position_embeddings=1024, vision_config=VisionConfig(**t["vit"]))
-    eng = TeoEngine(TY.state_dict(name), cfg, dtype=dt, device="cuda:0", max_seq=MAX_SEQ, weight_format=wf)
+    vit, llm, sd = _tiny(name)
+    cfg = LlavaConfig(**llm, mm_hidden_size=vit["hidden_size"], max_position_embeddings=1024, vision_config=VisionConfig(**vit))
+    eng = TeoEngine(sd, cfg, dtype=dt, device="cuda:0", max_seq=MAX_SEQ, weight_format=wf)
     if opts:
         eng.set_options(**opts)
     torch.cuda.synchronize()
@@ -1353,6 +1381,422 @@ def test_stage_llama_decode_batch_begin_and_steps_on_their_declared_workspace(va
         _cache_rows(eng, [t[:, b] for t in runs[True][4]], n, n + steps, [t[:, b] for t in runs[False][4]], [t[:, b] for t in runs[True][3]], what + (b, "decode"))
     if variant == "mxfp4":
         eng.set_options(batch_mxfp4=False)
+
+
+# ======================================================================================================== verify and stream steps, the proposer
+# The entry points that own device memory between calls (speculative decoding, continuous batching), on tinyB515.  Beyond the stage rule
+# above, the KV caches themselves are arenas here (the descriptors' cache pointers are repointed), so a row appended behind the last row
+# of the last head is seen as well as one that lands in the next head's row 0, and the runs end AT the cache end.
+def _first_max(row):
+    """first index of the maximum of a host row: the token a greedy tail must pick (argmax's tie order is not promised)"""
+    return int((row == row.max()).nonzero()[0])
+
+
+def _side_replays(create, n):
+    """capture a step on a side stream (the captures need a non-default stream) and replay it n times there, as the decoders' steps() do"""
+    lib = G.lib()
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        st = C.c_void_p(side.cuda_stream)
+        g = C.c_void_p()
+        L.check(create(st, C.byref(g)), "graph_create")
+        L.check(lib.teo_graph_launch(g, n, st), "teo_graph_launch")
+        side.synchronize()
+        L.check(lib.teo_graph_destroy(g), "teo_graph_destroy")
+    torch.cuda.synchronize()
+
+
+def _arrays(spec, guarded):
+    hold = {k: (_out(s, t) if guarded else None) for k, s, t in spec}
+    ten = {k: (hold[k].view if guarded else torch.empty(s, dtype=t, device=DEV)) for k, s, t in spec}
+    return hold, ten
+
+
+def _cache_arenas(shape_kv, shape_vt, dt, guarded):
+    """K, V and V^T as arenas (interior = the arena's random pattern) or as zeroed plain tensors"""
+    if guarded:
+        hold = [_out(shape_kv, dt), _out(shape_kv, dt), _out(shape_vt, dt)]
+        return hold, [a.view for a in hold]
+    return None, [torch.zeros(shape_kv, dtype=dt, device=DEV), torch.zeros(shape_kv, dtype=dt, device=DEV), torch.zeros(shape_vt, dtype=dt, device=DEV)]
+
+
+def _repoint(descs, caches, layer_view, keep):
+    """point the cache arrays of descriptor copies at `caches` (layer_view(t, l) = what layer l's pointer addresses)"""
+    Lr = caches[0].shape[0]
+    arrs = [L.ptr_array([layer_view(t, l).data_ptr() for l in range(Lr)]) for t in caches]
+    keep.append(arrs)
+    for d in descs:
+        d.k_cache, d.v_cache, d.vt_cache = arrs[0][1], arrs[1][1], arrs[2][1]
+
+
+_VERIFY_SAMPLER = dict(do_sample=1, top_k=20, temperature=1.5, top_p=1.0, seed=0x5EED5)
+
+
+def _verify_selected(logits, sample, rng_before):
+    """the token behind every row of a verify step's logits (host copy for greedy; the stand-alone sampler on an aligned copy of the row
+    with draw index d_rng[1] + row when sampling: the library's own contract for the two forms of the sampler)"""
+    if not sample:
+        lg = logits.cpu()
+        return [_first_max(lg[i]) for i in range(lg.shape[0])]
+    lib, out = G.lib(), []
+    tok = torch.zeros(1, dtype=I64, device=DEV)
+    for i in range(logits.shape[0]):
+        row = logits[i].clone()
+        assert row.data_ptr() % 16 == 0
+        L.check(lib.teo_sample_topk(G.p(row), G.p(tok), row.numel(), _VERIFY_SAMPLER["temperature"], _VERIFY_SAMPLER["top_k"],
+                                    _VERIFY_SAMPLER["top_p"], int(rng_before[0]), int(rng_before[1]) + i, G.stream()), "teo_sample_topk")
+        out.append(int(tok.item()))
+    return out
+
+
+def _verify_run(eng, sdec, R, max_new, P, e0, history_of, sample, guarded, stop_fill=None, stop_ids=(1, 2)):
+    """prefill P rows, teo_llama_verify_begin, steps until the max_new cut sets d_stop, then three more (one plain, two graph replays)"""
+    lib, dt, c = G.lib(), eng.dtype, eng.cfg
+    Lr, Hk, hd, V = c.num_hidden_layers, c.num_key_value_heads, c.head_dim, c.vocab_size
+    keep = []
+    pd, d = L.LlamaDesc.from_buffer_copy(sdec.prefill_desc), L.LlamaDesc.from_buffer_copy(sdec.desc)
+    chold, caches = _cache_arenas((Lr, Hk, MAX_SEQ, hd), (Lr, Hk, hd, MAX_SEQ), dt, guarded)
+    _repoint((pd, d), caches, lambda t, l: t[l], keep)
+    ws_p, lg = _ws_generous(lib.teo_llama_prefill_workspace_bytes(C.byref(pd), P)), _nan((1, V), F32)
+    _prefill(eng, pd, e0, torch.arange(P, dtype=I32, device=DEV), P, 0, 1, lg, ws_p, ws_p.numel())
+    first = _first_max(lg[0].cpu())
+    before = [t.clone() for t in caches]
+    hist = [int(t) for t in history_of(first)]
+    hl = len(hist)
+    spec = (("rows", (R,), I64), ("n_draft", (1,), I32), ("hist", (hl + max_new,), I64), ("hist_len", (1,), I32), ("stats", (3,), I32),
+            ("token", (1,), I64), ("pos", (1,), I32), ("out", (max_new,), I64), ("count", (1,), I32), ("stop", (1,), I32),
+            ("logits", (R, V), F32), ("rng", (2,), I64))
+    hold, ten = _arrays(spec, guarded)
+    for k in ("n_draft", "stats", "out", "count", "stop"):
+        ten[k].zero_()
+    ten["rows"].fill_(first)
+    ten["token"].fill_(first)
+    ten["pos"].fill_(P)
+    ten["hist"].fill_(-7)
+    ten["hist"][:hl] = torch.tensor(hist, dtype=I64)
+    ten["hist_len"].fill_(hl)
+    ten["logits"].fill_(float("nan"))
+    ten["rng"].copy_(torch.tensor([_VERIFY_SAMPLER["seed"], 1], dtype=I64))
+    stops = torch.tensor(stop_ids, dtype=I64)
+    stop_arena = _in(stops, fill=stop_fill) if guarded else None
+    stop_t = stop_arena.view if guarded else stops.to(DEV)
+    s = L.VerifyState.from_buffer_copy(sdec.state)
+    s.rows, s.max_new, s.ngram_max = R, max_new, 2
+    s.d_rows, s.d_n_draft, s.d_hist, s.d_hist_len = ten["rows"].data_ptr(), ten["n_draft"].data_ptr(), ten["hist"].data_ptr(), ten["hist_len"].data_ptr()
+    s.d_stats, s.d_token, s.d_pos, s.d_out_tokens = ten["stats"].data_ptr(), ten["token"].data_ptr(), ten["pos"].data_ptr(), ten["out"].data_ptr()
+    s.d_out_count, s.d_stop, s.d_stop_ids, s.n_stop_ids = ten["count"].data_ptr(), ten["stop"].data_ptr(), stop_t.data_ptr(), len(stop_ids)
+    s.d_logits, s.d_rng = ten["logits"].data_ptr(), ten["rng"].data_ptr()
+    s.do_sample, s.top_k, s.temperature, s.top_p = (1, _VERIFY_SAMPLER["top_k"], _VERIFY_SAMPLER["temperature"], _VERIFY_SAMPLER["top_p"]) if sample \
+        else (0, 0, 1.0, 1.0)
+    need = lib.teo_llama_verify_workspace_bytes(C.byref(d), R)
+    assert need > lib.teo_llama_decode_batch_workspace_bytes(C.byref(d), R)              # sel[R] lies behind the batched carve
+    ws = _ws_exact(need) if guarded else None
+    wsp, nbytes = (ws.view, need) if guarded else (_ws_generous(need), need + (1 << 20))
+    L.check(lib.teo_llama_verify_begin(C.byref(d), C.byref(s), G.p(wsp), nbytes, G.stream()), "teo_llama_verify_begin")
+    log = []                                                 # per step: what the host needs to judge the acceptance
+    while not int(ten["stop"].item()):
+        assert len(log) < 2 * max_new, "the max_new cut never came"
+        b4 = dict(pos=int(ten["pos"].item()), count=int(ten["count"].item()), n_draft=int(ten["n_draft"].item()), rows=ten["rows"].tolist(),
+                  rng=ten["rng"].tolist())
+        L.check(lib.teo_llama_verify_step(C.byref(d), C.byref(s), G.p(wsp), nbytes, G.stream()), "teo_llama_verify_step")
+        b4["selected"] = _verify_selected(ten["logits"], sample, b4["rng"]) if not guarded else None
+        b4["emitted"] = int(ten["count"].item()) - b4["count"]
+        log.append(b4)
+    frozen = {k: t.clone() for k, t in ten.items()}
+    hi = max(x["pos"] for x in log) + R
+    hi = max(hi, int(ten["pos"].item()) + R)                 # the steps behind the stop run at the final position
+    L.check(lib.teo_llama_verify_step(C.byref(d), C.byref(s), G.p(wsp), nbytes, G.stream()), "teo_llama_verify_step")
+    _side_replays(lambda st, out: lib.teo_llama_verify_graph_create(C.byref(d), C.byref(s), G.p(wsp), nbytes, st, out), 2)
+    for k, t in ten.items():                                 # (d_logits is an output, not state: these steps ran on the NEXT proposal's rows)
+        assert k == "logits" or torch.equal(_bits(t), _bits(frozen[k])), ("a step behind the stop changed", k, guarded)
+    return dict(ten=ten, hold=hold, ws=ws, need=need, before=before, caches=[t.clone() for t in caches], chold=chold, log=log, hi=hi,
+                first=first, d=d, s=s, stop_arena=stop_arena, keep=keep, hist=hist)
+
+
+_VERIFY_CASES = [("bf16", 8, 0), ("fp16", 8, 0), ("fp32", 8, 0), ("fp8", 8, 0), ("mxfp4", 8, 0), ("bf16", 1, 0), ("bf16", 16, 0), ("bf16", 8, 1)]
+
+
+@pytest.mark.parametrize("variant,R,sample", _VERIFY_CASES, ids=[f"{v}-R{r}" + ("-sampled" if s else "") for v, r, s in _VERIFY_CASES])
+def test_stage_llama_verify_begin_and_steps_on_their_declared_workspace(variant, R, sample):
+    """teo_llama_verify_begin + teo_llama_verify_step on tinyB515 AT THE CACHE END: P = MAX_SEQ - max_new - R rows are prefilled, so the
+    contract (position at begin) + max_new + R <= max_seq holds with equality and the steps behind the stop write the cache's last row.
+    Every state array is an arena of exactly its declared length (d_hist: the history at begin + max_new), the two stop ids sit in an
+    input arena run on two fills, the workspace is exactly teo_llama_verify_workspace_bytes() (NaN before begin, never again), the caches
+    are arenas.  State, logits and cache rows equal the plain run bit for bit; three steps behind the stop change nothing.
+
+    The history is built from the stream of a pilot run of the same plain call (a verify step selects by (logits, seed, counter) alone,
+    so the stream does not depend on the drafts): [F, first, t0, t1, BAD, t1 .. t7, F, first] makes the first step propose two right
+    drafts and a wrong one, and the next proposal a run that max_new = 8 cuts.  Both are asserted on the plain run (R > 1)."""
+    from teochat_amd.speculative import SpecDecoder
+    eng = _engine(variant, "tinyB515")
+    if variant == "mxfp4":
+        eng.set_options(batch_mxfp4=True)
+    try:
+        lib, dt, c = G.lib(), eng.dtype, eng.cfg
+        V, max_new = c.vocab_size, 8
+        assert V == RAGGED_VOCAB
+        sdec = SpecDecoder(eng, R, max_new=max_new)
+        assert sdec.state.w_mxfp4 == int(variant == "mxfp4") and sdec.state.w_tiled == int(variant != "fp32")
+        P = MAX_SEQ - max_new - R
+        e0 = (torch.randn(P, c.hidden_size, generator=_gen(P, 47)) * 0.5).to(dt).to(DEV)
+        pilot = _verify_run(eng, sdec, R, max_new, P, e0, lambda first: [first], sample, False)
+        t = pilot["ten"]["out"].tolist()
+        assert int(pilot["ten"]["count"].item()) == max_new and all(0 <= x < V for x in t)
+
+        def history_of(first):
+            assert first == pilot["first"]
+            used = set(t) | {first}
+            filler = next(i for i in range(3, V) if i not in used)
+            bad = next(i for i in range(3, V) if i not in used and i != filler)
+            return [filler, first, t[0], t[1], bad] + t[1:] + [filler, first]
+
+        plain = _verify_run(eng, sdec, R, max_new, P, e0, history_of, sample, False)
+        what = ("teo_llama_verify_step", variant, R, sample)
+        tp = plain["ten"]
+        assert tp["out"].tolist() == t, what + ("the stream depends on the drafts", tp["out"].tolist(), t)
+        steps, proposed, accepted = tp["stats"].tolist()
+        assert steps == len(plain["log"]) and int(tp["count"].item()) == max_new and int(tp["pos"].item()) == P + max_new
+        assert plain["hi"] == MAX_SEQ and not bool(torch.isnan(tp["logits"]).any())
+        if R > 1:
+            assert accepted > 0 and proposed > accepted, what + (tp["stats"].tolist(),)
+            last = plain["log"][-1]                          # the step that max_new cut: its accepted run is longer than what it emitted
+            a = 0
+            while a < last["n_draft"] and last["selected"][a] == last["rows"][a + 1]:
+                a += 1
+            assert a >= 1 and last["emitted"] <= a and last["count"] + last["emitted"] == max_new, what + ("the cut is not inside an accepted run", last, a)
+        else:
+            assert proposed == 0 and accepted == 0 and steps == max_new
+        for x in plain["log"]:                               # the acceptance rule, step by step, from the logits
+            a = 0
+            while a < x["n_draft"] and x["selected"][a] == x["rows"][a + 1]:
+                a += 1
+            assert x["emitted"] == min(a + 1, max_new - x["count"]), what + (x, a)
+        for fill in (("elem", t[0]), ("elem", -200)):        # around the two stop ids: an emitted token, then a sentinel
+            g = _verify_run(eng, sdec, R, max_new, P, e0, history_of, sample, True, stop_fill=fill)
+            g["ws"].check(f"{what}: workspace ({g['need']} bytes declared)")
+            g["stop_arena"].check(str(what + ("stop ids",)))
+            for k, a in g["hold"].items():
+                a.check(str(what + (k, fill)))
+                assert torch.equal(_bits(g["ten"][k]), _bits(tp[k])), what + (k, fill, g["ten"][k].flatten()[:8], tp[k].flatten()[:8])
+            assert [x["pos"] for x in g["log"]] == [x["pos"] for x in plain["log"]]
+            for a, nm in zip(g["chold"], ("K", "V", "V^T")):
+                a.check(str(what + (nm, "cache arena", fill)))
+            _cache_rows(eng, g["caches"], 0, g["hi"], plain["caches"], g["before"], what + (fill,))
+            _cache_rows(eng, g["caches"], P, g["hi"], plain["caches"], g["before"], what + (fill, "verify rows"))
+            # less than declared is refused before any launch
+            assert lib.teo_llama_verify_begin(C.byref(g["d"]), C.byref(g["s"]), G.p(g["ws"].view), g["need"] - 1, G.stream()) == -4
+            assert lib.teo_llama_verify_step(C.byref(g["d"]), C.byref(g["s"]), G.p(g["ws"].view), g["need"] - 1, G.stream()) == -4
+            torch.cuda.synchronize()
+            g["ws"].check(str(what + ("refused calls",)))
+            for k, a in g["hold"].items():
+                a.check(str(what + (k, "refused calls")))
+                assert torch.equal(_bits(g["ten"][k]), _bits(tp[k])), what + (k, "refused calls")
+            for a in g["chold"]:
+                a.check(str(what + ("caches", "refused calls")))
+        if sample:
+            assert tp["rng"].tolist() == [_VERIFY_SAMPLER["seed"], 1 + max_new]
+    finally:
+        if variant == "mxfp4":
+            eng.set_options(batch_mxfp4=False)
+
+
+def _residual_views(ws, B, D, dt):
+    """h, hg, ssq as decode_batch_carve lays them out at the front of the step's workspace (teochat_amd/stream.py::residual_rows)"""
+    e = torch.empty(0, dtype=dt).element_size()
+    row = (B * D * e + 255) // 256 * 256
+    nparts = (D + 15) // 16
+    return (ws[:B * D * e].view(B, D * e), ws[row:row + B * D * e].view(B, D * e), ws[2 * row:2 * row + B * nparts * 4].view(B, nparts * 4))
+
+
+def _stream_run(eng, variant, guarded):
+    from teochat_amd.batch import BatchDecoder
+    from teochat_amd.stream import StreamDecoder
+    lib, dt, c = G.lib(), eng.dtype, eng.cfg
+    Lr, Hk, hd, D, V = c.num_hidden_layers, c.num_key_value_heads, c.head_dim, c.hidden_size, c.vocab_size
+    B, max_new = 4, 8
+    bd = BatchDecoder(eng, B, max_new=max_new)
+    sdec = StreamDecoder(eng, B, max_new=max_new, batch_decoder=bd)
+    assert bd.w4 == (variant == "mxfp4") and bd.tiled == (variant != "fp32")
+    keep, what = [], ("teo_llama_decode_stream_step", variant)
+    pd, d = L.LlamaDesc.from_buffer_copy(bd.slot_desc[0]), L.LlamaDesc.from_buffer_copy(bd.desc)
+    chold, caches = _cache_arenas((Lr, B, Hk, MAX_SEQ, hd), (Lr, B, Hk, hd, MAX_SEQ), dt, guarded)
+    _repoint((pd, d), caches, lambda t, l: t[l, 0], keep)
+    stride = caches[0].stride(1)
+    assert stride == bd.state.cache_stride
+    before = [t.clone() for t in caches]
+    spec = (("token", (B,), I64), ("pos", (B,), I32), ("out", (B, max_new), I64), ("count", (B,), I32), ("stop", (B,), I32), ("logits", (B, V), F32),
+            ("rng", (B, 2), I64), ("limit", (B,), I32))
+    hold, ten = _arrays(spec, guarded)
+    for k in ("token", "out", "count", "rng"):               # StreamDecoder.reset: every slot parked and free
+        ten[k].zero_()
+    ten["pos"].fill_(-1)
+    ten["stop"].fill_(1)
+    ten["limit"].fill_(1)
+    ten["logits"].fill_(float("nan"))
+    s = L.DecodeStreamState.from_buffer_copy(sdec.state)
+    s.d_token, s.d_pos, s.d_out_tokens = ten["token"].data_ptr(), ten["pos"].data_ptr(), ten["out"].data_ptr()
+    s.d_out_count, s.d_stop, s.d_stop_ids, s.n_stop_ids = ten["count"].data_ptr(), ten["stop"].data_ptr(), None, 0
+    s.d_logits, s.d_rng, s.d_limit = ten["logits"].data_ptr(), ten["rng"].data_ptr(), ten["limit"].data_ptr()
+    assert s.batch == B and s.out_stride == max_new
+    need = lib.teo_llama_decode_stream_workspace_bytes(C.byref(d), B)
+    ws = _ws_exact(need) if guarded else None
+    wsp, nbytes = (ws.view, need) if guarded else (_ws_generous(need), need + (1 << 20))
+    checks = []                                              # (arena, what) to check at the end: the prefill workspaces and their operands
+
+    def refill(slots, lens, key):
+        total, n = sum(lens), len(lens)
+        e0 = (torch.randn(total, D, generator=_gen(total, key)) * 0.5).to(dt).to(DEV)
+        need_p = lib.teo_llama_prefill_workspace_bytes(C.byref(pd), total)
+        if guarded:
+            emb, lg, ws_p = _in(e0), _out((n, V), F32), _ws_exact(need_p)
+            checks.extend([(lg, "prefill_slots logits"), (ws_p, f"teo_llama_prefill_slots workspace ({need_p} bytes declared)")])
+            e, lgt, wsv, nb = emb.view, lg.view, ws_p.view, need_p
+        else:
+            e, lgt = e0, _nan((n, V), F32)
+            wsv = _ws_generous(need_p)
+            nb = wsv.numel()
+        args = (C.byref(pd), G.p(e), (C.c_int * n)(*lens), (C.c_int * n)(*slots), n, stride, 1, G.p(lgt))
+        L.check(lib.teo_llama_prefill_slots(*args, G.p(wsv), nb, G.stream(), None), "teo_llama_prefill_slots")
+        flag = C.c_int(-1)
+        L.check(lib.teo_llama_prefill_workspace_status(C.byref(pd), total, G.p(wsv), nb, C.byref(flag), G.stream()), "status")
+        assert flag.value == 0
+        if guarded:                                          # less than declared is refused, not overrun
+            assert lib.teo_llama_prefill_slots(*args, G.p(wsv), need_p - 1, G.stream(), None) == -4
+        assert not bool(torch.isnan(lgt).any())
+        return lgt.clone()
+
+    def arm(slot, token, pos, limit, fresh=True):
+        if pos >= 0:
+            ten["token"][slot], ten["pos"][slot], ten["count"][slot], ten["stop"][slot], ten["limit"][slot] = int(token), pos, 0, 0, limit
+            ten["rng"][slot] = torch.tensor([1000 + slot, 1], dtype=I64)
+        torch.cuda.synchronize()
+        b4 = [v.clone() for v in _residual_views(wsp, B, D, dt)]
+        L.check(lib.teo_llama_decode_stream_arm(C.byref(d), C.byref(s), slot, G.p(wsp), nbytes, G.stream()), "teo_llama_decode_stream_arm")
+        torch.cuda.synchronize()
+        now = _residual_views(wsp, B, D, dt)
+        others = [b for b in range(B) if b != slot]
+        for v0, v1, nm in zip(b4, now, ("h", "hg", "ssq")):
+            assert torch.equal(v0[others], v1[others]), what + ("arm", slot, nm, "touched another slot's row")
+        assert torch.equal(now[0][slot], _bits(eng.embed[int(ten["token"][slot])])), what + ("arm", slot, "h is not the token's embedding row")
+        if bd.tiled and fresh:                               # (the rows were NaN bytes; a re-armed row may legitimately get the bits it had)
+            assert not torch.equal(b4[1][slot], now[1][slot]) and not torch.equal(b4[2][slot], now[2][slot]), what + ("arm", slot, "hg / ssq not written")
+
+    lens1 = [33, 70, 5]
+    lg = refill([3, 0, 2], lens1, 48)
+    firsts = {sl: _first_max(lg[i].cpu()) for i, sl in enumerate([3, 0, 2])}
+    limits = {0: 6, 2: 2, 3: 6}
+    lens = {3: 33, 0: 70, 2: 5}
+    for slot in range(B):                                    # slot 1 is never filled: parked at -1 with token 0
+        if slot == 1:
+            arm(1, 0, -1, 1)
+        else:
+            arm(slot, firsts[slot], lens[slot], limits[slot])
+    for _ in range(2):
+        L.check(lib.teo_llama_decode_stream_step(C.byref(d), C.byref(s), G.p(wsp), nbytes, G.stream()), "teo_llama_decode_stream_step")
+    torch.cuda.synchronize()
+    mid = {k: t.clone() for k, t in ten.items()}
+    lg2 = refill([2], [MAX_SEQ - 3], 49)
+    arm(2, _first_max(lg2[0].cpu()), MAX_SEQ - 3, 3, fresh=False)         # position + limit == max_seq: the slot's last step writes the cache's last row
+    create = lambda st, out: lib.teo_llama_decode_stream_graph_create(C.byref(d), C.byref(s), G.p(wsp), nbytes, st, out)   # noqa: E731
+    _side_replays(create, 4)
+    after4 = {k: t.clone() for k, t in ten.items()}
+    _side_replays(create, 1)                                 # one more: every slot is parked
+    return dict(ten=ten, hold=hold, ws=ws, need=need, before=before, caches=[t.clone() for t in caches], chold=chold, mid=mid, after4=after4,
+                checks=checks, d=d, s=s, keep=keep, bd=bd, sdec=sdec, create=create)
+
+
+@pytest.mark.parametrize("variant", ["bf16", "fp16", "fp32", "fp8", "mxfp4"])
+def test_stage_llama_decode_stream_arm_and_steps_on_their_declared_workspace(variant):
+    """teo_llama_prefill_slots + teo_llama_decode_stream_arm / _step / _graph_create over four slots on tinyB515, everything in arenas
+    (d_limit included; the caches too), the step's workspace exactly teo_llama_decode_stream_workspace_bytes() and NaN before the first
+    arm only.  Script: slots [3, 0, 2] are filled in that order with 33, 70 and 5 rows in one pass, slot 1 never is (d_pos = -1, token
+    0); all four are armed (limits 6, -, 2, 6); two plain steps, slot 2 parks itself; slot 2 is refilled with MAX_SEQ - 3 rows and armed
+    with limit 3 (position + limit == max_seq); four graph replays -- slot 2 writes row MAX_SEQ - 1 and parks at -1 - MAX_SEQ, slots 0
+    and 3 reach their limits -- and a fifth with every slot parked."""
+    eng = _engine(variant, "tinyB515")
+    if variant == "mxfp4":
+        eng.set_options(batch_mxfp4=True)
+    try:
+        lib = G.lib()
+        p, g = _stream_run(eng, variant, False), _stream_run(eng, variant, True)
+        what = ("teo_llama_decode_stream_step", variant)
+        tp = p["ten"]
+        # the plain run did what the script says
+        assert p["mid"]["pos"].tolist() == [72, -1, -1 - 7, 35] and p["mid"]["count"].tolist() == [2, 0, 2, 2] and p["mid"]["stop"].tolist() == [0, 1, 1, 0]
+        assert p["after4"]["pos"].tolist() == [-1 - 76, -1, -1 - MAX_SEQ, -1 - 39] and p["after4"]["count"].tolist() == [6, 0, 3, 6]
+        assert p["after4"]["stop"].tolist() == [1, 1, 1, 1]
+        for k in ("token", "pos", "out", "count", "stop", "rng", "limit"):
+            assert torch.equal(tp[k], p["after4"][k]), what + (k, "a replay with every slot parked changed the state")
+        assert not bool(torch.isnan(tp["logits"]).any()), what + ("a parked slot's residual row is not finite",)
+        assert tp["out"][1].tolist() == [0] * 8 and tp["out"][2, 3:].tolist() == [0] * 5
+        g["ws"].check(f"{what}: workspace ({g['need']} bytes declared)")
+        for a, nm in g["checks"]:
+            a.check(str(what + (nm,)))
+        for k, a in g["hold"].items():
+            a.check(str(what + (k,)))
+            assert torch.equal(_bits(g["ten"][k]), _bits(tp[k])), what + (k, g["ten"][k].flatten()[:8], tp[k].flatten()[:8])
+            assert torch.equal(_bits(g["mid"][k]), _bits(p["mid"][k])), what + (k, "after the two plain steps")
+        for a, nm in zip(g["chold"], ("K", "V", "V^T")):
+            a.check(str(what + (nm, "cache arena")))
+        for b, n in ((0, 76), (1, 0), (2, MAX_SEQ), (3, 39)):
+            _cache_rows(eng, [t[:, b] for t in g["caches"]], 0, n, [t[:, b] for t in p["caches"]], [t[:, b] for t in g["before"]], what + (b,))
+        # less than declared is refused before any launch
+        d, s, ws, need = g["d"], g["s"], g["ws"], g["need"]
+        assert lib.teo_llama_decode_stream_step(C.byref(d), C.byref(s), G.p(ws.view), need - 1, G.stream()) == -4
+        assert lib.teo_llama_decode_stream_arm(C.byref(d), C.byref(s), 0, G.p(ws.view), need - 1, G.stream()) == -4
+        torch.cuda.synchronize()
+        side = torch.cuda.Stream()
+        out = C.c_void_p()
+        assert lib.teo_llama_decode_stream_graph_create(C.byref(d), C.byref(s), G.p(ws.view), need - 1, C.c_void_p(side.cuda_stream), C.byref(out)) == -4
+        assert not out.value
+        torch.cuda.synchronize()
+        ws.check(str(what + ("refused calls",)))
+        for k, a in g["hold"].items():
+            a.check(str(what + (k, "refused calls")))
+            assert torch.equal(_bits(g["ten"][k]), _bits(tp[k])), what + (k, "refused calls")
+        for a in g["chold"]:
+            a.check(str(what + ("caches", "refused calls")))
+    finally:
+        if variant == "mxfp4":
+            eng.set_options(batch_mxfp4=False)
+
+
+def test_spec_propose_on_exact_arrays():
+    """teo_spec_propose against teochat_amd.speculative.propose_ngram with d_hist EXACTLY *d_hist_len ids long: history lengths at the
+    strides of the 256-thread scan and around the n-gram (1, 2, n, n + 1, 255, 256, 257, 513), rows 1, 2 and 16, n-grams up to 1 .. 8
+    (the ABI's range), alphabets of 2 and 3 ids so that matches are dense.  The ids around the history are the history's own last id
+    (a scan that runs one position too far matches the suffix against itself and then finds a following id in the guard), then the
+    image sentinel; d_rows is exactly `rows` long and d_n_draft one int."""
+    from teochat_amd.speculative import propose_ngram
+    lib = G.lib()
+    rows_a = {R: _out((R,), I64) for R in (1, 2, 16)}
+    nd_a = _out((1,), I32)
+    cases = with_drafts = 0
+    for n in range(1, 9):
+        for hl in sorted({1, 2, n, n + 1, 255, 256, 257, 513}):
+            g = _gen(n, hl, 51)
+            alpha = 2 + (n + hl) % 2
+            h = (10 + torch.randint(0, alpha, (hl,), generator=g)).tolist()
+            hist = _in(torch.tensor(h, dtype=I64), fill=("elem", h[-1]))
+            hlen = _in(torch.tensor([hl], dtype=I32), fill=("elem", hl + 1))
+            for R in (1, 2, 16):
+                want = propose_ngram(h, R, n)
+                cases += 1
+                with_drafts += bool(want)
+                for fill in (("elem", h[-1]), ("elem", -200)):
+                    hist.repoison(fill)
+                    rows_a[R].view.fill_(-1)
+                    rows_a[R].view[0] = h[-1]
+                    nd_a.view.fill_(-1)
+                    L.check(lib.teo_spec_propose(G.p(hist.view), G.p(hlen.view), G.p(rows_a[R].view), G.p(nd_a.view), R, n, G.stream()), "teo_spec_propose")
+                    what = ("teo_spec_propose", "hl", hl, "rows", R, "ngram_max", n, fill)
+                    got_n, got = int(nd_a.view.item()), rows_a[R].view.tolist()
+                    assert got_n == len(want) and got[1:1 + got_n] == want, what + (h[-10:], want, got_n, got)
+                    assert got[0] == h[-1] and got[1 + got_n:] == [h[-1]] * (R - 1 - got_n), what + ("unused rows hold the pending token",)
+                    rows_a[R].check(str(what + ("d_rows",)))
+                    nd_a.check(str(what + ("d_n_draft",)))
+    assert 2 * with_drafts > cases, (with_drafts, cases)
 
 
 # ======================================================================================================== coverage
