@@ -45,6 +45,7 @@ typedef enum {
 #define TEO_GEMM_FORCE_SIMPLE 2u /* use the shape-agnostic VALU kernel even when the MFMA kernel applies */
 #define TEO_GEMM_SWIGLU8 8u /* teo_gemm_skinny: like SWIGLU16 with gate/up rows interleaved in blocks of 8 */
 #define TEO_GEMM_F16 16u /* teo_gemm_skinny: x / W / residual are IEEE half (implied by a TEO_F16 output; needed with a TEO_F32 one) */
+#define TEO_GEMV_W13 32u /* teo_gemv: d_W is a w13 image of the bf16 matrix (see teo_gemv) */
 #define TEO_GEMM_WTILED 4u /* teo_gemm_skinny / teo_gemm_skinny_w4: W is stored as 1 KB operand tiles (16 rows x 32 k bf16 / 64 k fp8 / 128 k MXFP4), see below */
 
 int teo_version(void);
@@ -340,6 +341,19 @@ int teo_sample_topk(const float* d_logits, long long* d_token, int vocab, float 
  *   norm_w != NULL : f(x) = rmsnorm(x) * norm_w (rounded to dtype), else f(x) = x
  *   flags & TEO_GEMM_SWIGLU16 : W is gate/up interleaved-16; y[N/2] = silu(g)*u
  *   out_dtype TEO_F32 allowed (logits).
+ *   flags & TEO_GEMV_W13 : d_W is not the matrix but its "w13 image", a lossless 13-bit-per-weight picture of the bf16 matrix W[N, K]
+ *     built once at load (0.8125 x the bytes; the kernels rebuild the 16-bit patterns in registers, so y is bit for bit what the raw
+ *     matrix gives, whatever the other flags and the tune block say).  dtype other than TEO_BF16: TEO_ERR_ARG; K % 8 != 0:
+ *     TEO_ERR_UNSUPPORTED; the image 16-byte aligned.  For a bf16 pattern b: lo = b & 0xFF, P = (b >> 8) & 0x7F, s = b >> 15.  Per row
+ *     rp = max(1, Pmax - 14); the row is packable when every element has P == 0 or rp <= P <= rp + 14, with the 4-bit code n = 0 for
+ *     P == 0 and n = P - rp + 1 otherwise.  One allocation, five sections, each starting on a 256-byte boundary, in this order:
+ *       RT [N]         uint32: packed row: rp in the low byte; escaped (not packable) row: 0xFF in the low byte, its ESC slot in bits 8..31
+ *       LO [N][K]      bytes : lo of every element in element order
+ *       NIB[N][K/2]    bytes : one little-endian dword per 8-element chunk c: byte i = n(8c + i) | n(8c + 4 + i) << 4, i = 0 .. 3
+ *       SGN[N][K/8]    bytes : one byte per chunk: bit i = s(8c + i), i = 0 .. 7
+ *       ESC[n_esc][K]  bf16  : the raw rows that are not packable, in row order (slot = the number of escaped rows above)
+ *     LO / NIB / SGN hold valid bytes for every row (an escaped row's are read and ignored).  Size = the first four sections rounded up
+ *     to 256 bytes each + 2 * n_esc * K.  teochat_amd.engine.pack_w13 / unpack_w13 build and invert it.
  * Same Linear layers as teo_gemm, for the q_len == 1 decode step (HBM-bound, no MFMA). */
 int teo_gemv(const void* d_x, const void* d_W, const void* d_norm_w, const void* d_residual, void* d_y, int N, int K,
              float eps, unsigned flags, int dtype, int out_dtype, teo_stream_t stream);
@@ -512,6 +526,17 @@ typedef struct {
     const void* const* o_w4;      const uint8_t* const* o_e4;
     const void* const* gateup_w4; const uint8_t* const* gateup_e4;
     const void* const* down_w4;   const uint8_t* const* down_e4;
+    /* Optional w13 images (teo_gemv, TEO_GEMV_W13) of the bf16 matrices.  Read by teo_llama_decode_step and its graph / profile forms
+     * ONLY: per layer and per matrix a non-NULL entry is streamed instead of the 16-bit matrix (same bits out); a NULL entry, or a NULL
+     * array, means the 16-bit matrix.  Any of them together with *_w8 or *_w4 copies, or with a dtype other than TEO_BF16: TEO_ERR_ARG
+     * before the first launch.  Every other entry point (prefill, the batched, stream and verify steps) ignores these fields and reads
+     * the 16-bit matrices, which therefore stay.  (They sit here, in front of the options, and not behind `tune`: `tune` stays the last
+     * field.  sizeof(teo_llama_desc) grew by 40 and the options and `tune` moved by as much: a binding checks teo_sizeof at load.) */
+    const void* const* qkv_p13;
+    const void* const* o_p13;
+    const void* const* gateup_p13;
+    const void* const* down_p13;
+    const void* lm_head_p13;
     /* Per-engine options (they select a path or change results, so they live here and not in teo_tune_set): */
     int prefill_fp8;   /* 1: prefill Linear layers as w8a8 on the fp8 MFMA (activations quantised per token; needs the *_w8 copies,
                         *    bf16).  Lossy beyond the weight quantisation: selectable, never a default.  0: bf16 / f32 GEMMs */

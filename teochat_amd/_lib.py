@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(HERE, "libteo_hip.so")
 TEO_F32, TEO_BF16, TEO_F16 = 0, 1, 2
 ACT_NONE, ACT_GELU_ERF, ACT_QUICK_GELU = 0, 1, 2
 GEMM_SWIGLU16, GEMM_FORCE_SIMPLE, GEMM_WTILED, GEMM_SWIGLU8, GEMM_F16 = 1, 2, 4, 8, 16
+GEMV_W13 = 32                   # teo_gemv: d_W is a w13 image (engine.pack_w13)
 ATTN_FORCE_SIMPLE = 1
 INT32_MIN = -(2 ** 31)
 
@@ -68,6 +69,7 @@ class LlamaDesc(C.Structure):
                 ("down_w8", PP), ("down_s", PP), ("lm_head8", C.c_void_p), ("lm_head_s", C.c_void_p),
                 ("qkv_w4", PP), ("qkv_e4", PP), ("o_w4", PP), ("o_e4", PP), ("gateup_w4", PP), ("gateup_e4", PP),
                 ("down_w4", PP), ("down_e4", PP),
+                ("qkv_p13", PP), ("o_p13", PP), ("gateup_p13", PP), ("down_p13", PP), ("lm_head_p13", C.c_void_p),
                 ("prefill_fp8", C.c_int), ("prefill_w4", C.c_int), ("rope_in_attn", C.c_int), ("prefill_w4a8", C.c_int), ("tune", C.c_void_p)]
 
 

@@ -381,6 +381,8 @@ int teo_gemv(const void* x, const void* W, const void* norm_w, const void* res, 
     ENTER();
     NEED_DT(dtype); NEED_DT(out_dtype); TEO_CHECK_ARG(N >= 0 && K > 0, "teo_gemv: N %d K %d", N, K);
     if (N) { NEED(x, "x"); NEED(W, "W"); NEED(y, "y"); }
+    if (flags & TEO_GEMV_W13)             // W is a w13 image (dtype / K checks: gemv_w)
+        return gemv_w(x, W, nullptr, GV_W_P13, norm_w, res, y, N, K, eps, flags & ~TEO_GEMV_W13, dtype, out_dtype, ST(s));
     return gemv(x, W, norm_w, res, y, N, K, eps, flags, dtype, out_dtype, ST(s));
 }
 

@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "ops.h"
+#include "p13.h"
 
 namespace teo {
 
@@ -150,6 +151,57 @@ template <typename T, typename WT> struct BfImage { static constexpr bool v = Is
 // needs 16 (shift / mask unpack) -- and measured 1.2-2.6 % behind bf16 whatever the data (tools/fp16_probe.py).  The 16-bit image +
 // v_dot2_f32_f16 is 4 instructions and one ds_read_b128 per 8 weights.  (The QKV + RoPE kernel keeps the fp32 image: it ties there.)
 template <typename T, typename WT> struct RowsImage16 { static constexpr bool v = BfImage<T, WT>::v || (IsF16<T>::v && IsF16<WT>::v); };
+
+// w13 image (p13.h): W points at the image; chunks are the bf16 instantiation's (8 weights), only the loads differ -- 8 B of LO, 4 B
+// of NIB and 1 B of SGN per chunk, kept raw in the uint4 the bf16 kernels hold a chunk in ({lo0, lo1, nib, sgn}) and rebuilt into the 16
+// bytes of the raw row right before the dot (rebuild_block).  Two bytes wide so that none of the fp8 (sizeof == 1) choices apply: the x
+// image, its staging, the geometry and the fp32 order of the sums are those of bf16 weights, and every output bit with them.
+struct p13_t { unsigned short v; };
+template <typename WT> struct IsP13 { static constexpr bool v = false; };
+template <> struct IsP13<p13_t> { static constexpr bool v = true; };
+// (what the row-group kernels hand to cvt is rebuild_block's {lo0, lo1, h0, h1}: one v_perm_b32 per weight widens it to fp32, where
+// the bf16 unpack takes two instructions per weight on top of the rebuild's interleave)
+template <> struct Vec16<p13_t> {
+    static constexpr int N = 8;
+    __device__ static __forceinline__ void cvt(const uint4& r, float* f) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { f[i] = __uint_as_float(p13_f32(r.z, r.x, i)); f[4 + i] = __uint_as_float(p13_f32(r.w, r.y, i)); }
+    }
+};
+struct P13Img {                                       // section pointers of one image
+    const unsigned* rt; const unsigned char *lo, *nib, *sgn; const bf16_t* esc;
+};
+__device__ __forceinline__ P13Img p13_img(const void* W, int N, int K) {
+    const P13Layout l = p13_layout(N, K);
+    const unsigned char* b = reinterpret_cast<const unsigned char*>(W);
+    return {reinterpret_cast<const unsigned*>(b + l.rt), b + l.lo, b + l.nib, b + l.sgn, reinterpret_cast<const bf16_t*>(b + l.esc)};
+}
+template <bool NT, typename V>
+__device__ __forceinline__ V ldv(const void* p) {
+    return NT ? __builtin_nontemporal_load(reinterpret_cast<const V*>(p)) : *reinterpret_cast<const V*>(p);
+}
+// the raw bytes of chunk c of a row: lo / nib / sgn are the ROW's section pointers
+template <bool NT>
+__device__ __forceinline__ uint4 p13_load(const unsigned char* lo, const unsigned char* nib, const unsigned char* sgn, long long c) {
+    typedef unsigned v2u __attribute__((ext_vector_type(2)));
+    const v2u l = ldv<NT, v2u>(lo + c * 8);
+    return make_uint4(l.x, l.y, ldv<NT, unsigned>(nib + c * 4), (unsigned)ldv<NT, unsigned char>(sgn + c));
+}
+// raw {lo0, lo1, nib, sgn} -> PAIRS: the chunk's four bf16 pairs (v_dot2 operands); else {lo0, lo1, h0, h1} for Vec16<p13_t>::cvt
+template <bool PAIRS>
+__device__ __forceinline__ uint4 p13_chunk(const uint4& raw, unsigned rpm) {
+    if constexpr (PAIRS) {
+        unsigned o[4];
+        p13_rebuild(raw.x, raw.y, raw.z, raw.w, rpm, o);
+        return make_uint4(o[0], o[1], o[2], o[3]);
+    } else {
+        unsigned h0, h1;
+        p13_high(raw.z, raw.w, rpm, h0, h1);
+        return make_uint4(raw.x, raw.y, h0, h1);
+    }
+}
+__device__ __forceinline__ unsigned p13_rpm(unsigned rt) { return ((rt & 0xffu) - 1u) * 0x00010001u; }     // (an escaped row's is never used)
+__device__ __forceinline__ bool p13_escaped(unsigned rt) { return (rt & 0xffu) == 0xffu; }
 
 template <bool NT>
 __device__ __forceinline__ uint4 ld16(const void* p) {
@@ -296,10 +348,24 @@ __device__ __forceinline__ void stage_x(const T* __restrict__ x, const T* __rest
 
 // one block of R rows x U chunks: loads and the dot-product update
 // (MXFP4: sx receives the chunks' e8m0 bytes from the scale rows srow -- one byte per lane, a wave's 64 in one request; unused otherwise)
+// (w13 image: rowp / srow / grow are the rows' LO / NIB / SGN pointers and w receives the raw bytes; grow is unused otherwise)
 template <typename WT, int R, int U, bool NT, bool FULL>
 __device__ __forceinline__ void issue_block(uint4 (&w)[U][R], unsigned (&sx)[U][R], const WT* const (&rowp)[R],
-                                            const unsigned char* const (&srow)[R], int c0, int lane, int nchunk) {
+                                            const unsigned char* const (&srow)[R], const unsigned char* const (&grow)[R], int c0, int lane,
+                                            int nchunk) {
     constexpr int CH = CU<WT>::v;
+    if constexpr (IsP13<WT>::v) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int c = c0 + u * 64 + lane;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (FULL) w[u][r] = p13_load<NT>(reinterpret_cast<const unsigned char*>(rowp[r]), srow[r], grow[r], c);
+                else w[u][r] = (c < nchunk) ? p13_load<NT>(reinterpret_cast<const unsigned char*>(rowp[r]), srow[r], grow[r], c) : make_uint4(0, 0, 0, 0);
+            }
+        }
+        return;
+    }
     if constexpr (IsMx<WT>::v) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -316,6 +382,16 @@ __device__ __forceinline__ void issue_block(uint4 (&w)[U][R], unsigned (&sx)[U][
             if (FULL) w[u][r] = ld16<NT>(rowp[r] + (long long)c * CH);
             else w[u][r] = (c < nchunk) ? ld16<NT>(rowp[r] + (long long)c * CH) : make_uint4(0, 0, 0, 0);
         }
+    }
+}
+// w13 image: the raw bytes of a block -> the 16-byte chunks of the raw rows (rpm: p13_rpm of each row); nothing for the other formats
+template <typename WT, int R, int U, bool PAIRS = false>
+__device__ __forceinline__ void rebuild_block(uint4 (&w)[U][R], const unsigned (&rpm)[R]) {
+    if constexpr (IsP13<WT>::v) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int r = 0; r < R; ++r) w[u][r] = p13_chunk<PAIRS>(w[u][r], rpm[r]);
     }
 }
 template <typename T, typename WT, int R, int U, bool FULL, bool XB16 = BfImage<T, WT>::v>
@@ -372,6 +448,28 @@ __device__ __forceinline__ void consume_block(const uint4 (&w)[U][R], const unsi
     }
 }
 
+// w13 image, an escaped row: the lane's partial sum of ONE raw bf16 row, in the steps and the order of the bf16 row-group kernel
+template <typename T, int U, bool NT, bool XB16>
+__device__ __forceinline__ float rows_escaped_row(const bf16_t* row, const float* xs, int lane, int nchunk) {
+    constexpr int STEP = 64 * U;
+    const bf16_t* rowp[1] = {row};
+    const unsigned char* none[1] = {nullptr};
+    uint4 w[U][1];
+    unsigned sx[U][1];
+    float acc[1] = {0.f};
+    const int cfull = (nchunk / STEP) * STEP;
+    int c0 = 0;
+    for (; c0 < cfull; c0 += STEP) {
+        issue_block<bf16_t, 1, U, NT, true>(w, sx, rowp, none, none, c0, lane, nchunk);
+        consume_block<T, bf16_t, 1, U, true, XB16>(w, sx, xs, c0, lane, nchunk, acc);
+    }
+    if (c0 < nchunk) {
+        issue_block<bf16_t, 1, U, NT, false>(w, sx, rowp, none, none, c0, lane, nchunk);
+        consume_block<T, bf16_t, 1, U, false, XB16>(w, sx, xs, c0, lane, nchunk, acc);
+    }
+    return acc[0];
+}
+
 // ------------------------------------------------------------------------------------------------
 // Row-group kernel: a wave owns R rows (SWIGLU: R/2 (gate, up) pairs 16 apart inside 32-row blocks).
 // ------------------------------------------------------------------------------------------------
@@ -400,6 +498,19 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const T* __restrict__ 
     uint4 wa[U][R];
     unsigned sa[U][R];                            // MXFP4 block scales of wa
     const long long rowlen = K / WPer<WT>::v;     // WT units per row
+    P13Img img = {};
+    if constexpr (IsP13<WT>::v) img = p13_img(W, N, K);
+    // the pointers a block's loads start from: the weight row (w13 image: the row's LO bytes), the MXFP4 scale row (w13: the NIB row),
+    // and the w13 SGN row
+    auto row_ptrs = [&](long long row, const WT*& wp, const unsigned char*& sp, const unsigned char*& gp) {
+        if constexpr (IsP13<WT>::v) {
+            wp = reinterpret_cast<const WT*>(img.lo + row * K); sp = img.nib + row * (K / 2); gp = img.sgn + row * (K / 8);
+        } else {
+            wp = W + row * rowlen;
+            sp = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) + row * nchunk : nullptr;
+            gp = nullptr;
+        }
+    };
     int grp = blockIdx.x * GV_WAVES + wid;
     // PF (host guarantees nchunk >= STEP): NO branch around the prefetch -- at a control-flow merge hipcc waits vmcnt(0),
     // which would drain the weights before the prologue.  Waves past the last group prefetch a clamped (valid) row.
@@ -407,42 +518,55 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const T* __restrict__ 
         if (PF) {
             const int gp = min(grp, ngroups - 1);
             const WT* rowp[R];
-            const unsigned char* srow[R];
+            const unsigned char *srow[R], *grow[R];
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                rowp[r] = W + row_of(gp, r) * rowlen;
-                srow[r] = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) + row_of(gp, r) * nchunk : nullptr;
-            }
-            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, 0, lane, nchunk);
+            for (int r = 0; r < R; ++r) row_ptrs(row_of(gp, r), rowp[r], srow[r], grow[r]);
+            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, grow, 0, lane, nchunk);
         }
     });
 
     bool have = PF;
     for (; grp < ngroups; grp += nwaves) {
         const WT* rowp[R];
-        const unsigned char* srow[R];
+        const unsigned char *srow[R], *grow[R];
         long long rows[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            rows[r] = row_of(grp, r); rowp[r] = W + rows[r] * rowlen;
-            srow[r] = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) + rows[r] * nchunk : nullptr;
+            rows[r] = row_of(grp, r);
+            row_ptrs(rows[r], rowp[r], srow[r], grow[r]);
         }
         float sc[R];                                 // row scales: loaded ahead of the weight stream, never waited on later
 #pragma unroll
-        for (int r = 0; r < R; ++r) sc[r] = (!IsMx<WT>::v && wscale) ? (float)wscale[rows[r]] : 1.f;
+        for (int r = 0; r < R; ++r) sc[r] = (!IsMx<WT>::v && !IsP13<WT>::v && wscale) ? (float)wscale[rows[r]] : 1.f;
+        unsigned rt[R], rpm[R];                      // w13 row table entries, loaded here for the same reason
+#pragma unroll
+        for (int r = 0; r < R; ++r) { rt[r] = IsP13<WT>::v ? img.rt[rows[r]] : 0u; rpm[r] = p13_rpm(rt[r]); }
         float acc[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = 0.f;
         int c0 = 0;
-        if (have) { consume_block<T, WT, R, U, true, RowsImage16<T, WT>::v>(wa, sa, xs, 0, lane, nchunk, acc); c0 = STEP; have = false; }
+        if (have) {
+            rebuild_block<WT, R, U>(wa, rpm);
+            consume_block<T, WT, R, U, true, RowsImage16<T, WT>::v>(wa, sa, xs, 0, lane, nchunk, acc); c0 = STEP; have = false;
+        }
         const int cfull = (nchunk / STEP) * STEP;          // steady state: no bounds checks, no exec masking
         for (; c0 < cfull; c0 += STEP) {
-            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, c0, lane, nchunk);
+            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, grow, c0, lane, nchunk);
+            rebuild_block<WT, R, U>(wa, rpm);
             consume_block<T, WT, R, U, true, RowsImage16<T, WT>::v>(wa, sa, xs, c0, lane, nchunk, acc);
         }
         if (c0 < nchunk) {
-            issue_block<WT, R, U, NT, false>(wa, sa, rowp, srow, c0, lane, nchunk);
+            issue_block<WT, R, U, NT, false>(wa, sa, rowp, srow, grow, c0, lane, nchunk);
+            rebuild_block<WT, R, U>(wa, rpm);
             consume_block<T, WT, R, U, false, RowsImage16<T, WT>::v>(wa, sa, xs, c0, lane, nchunk, acc);
+        }
+        if constexpr (IsP13<WT>::v) {
+            // an escaped row (rare; rt is the same in every lane, so the branch is uniform): the packed pass above streamed its clamped
+            // codes for nothing; its sum is taken again from the raw row in ESC
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (p13_escaped(rt[r]))
+                    acc[r] = rows_escaped_row<T, U, NT, RowsImage16<T, WT>::v>(img.esc + (long long)(rt[r] >> 8) * K, xs, lane, nchunk);
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = wave_sum(acc[r]);
@@ -485,7 +609,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int nchunk = K / VE;
     const int row0 = blockIdx.x * R;
-    const float my_scale = (!IsMx<WT>::v && wscale && tid < R && row0 + tid < N) ? (float)wscale[row0 + tid] : 1.f;   // ahead of the stream
+    const float my_scale = (!IsMx<WT>::v && !IsP13<WT>::v && wscale && tid < R && row0 + tid < N) ? (float)wscale[row0 + tid] : 1.f;   // ahead of the stream
     // the residual too: read after the reduction barrier it is a dependent global round trip at the tail of EVERY workgroup
     // (all of them are resident at once, so the whole launch ends one memory latency later); only this thread writes y[n]
     const float my_res = (res && tid < R && row0 + tid < N) ? Elem<T>::ld(res + row0 + tid) : 0.f;
@@ -494,10 +618,22 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
     for (int r = 0; r < R; ++r) acc[r] = 0.f;
     const WT* wrow[R];
     const unsigned char* srow[R];                         // MXFP4: the rows' e8m0 bytes, one per chunk
+    const unsigned char* grow[R];                         // w13 image: wrow / srow / grow are the rows' LO / NIB / SGN bytes
+    unsigned rt[R], rpm[R];                               // and its row table entries, ahead of the stream like the scales
+    P13Img img = {};
+    if constexpr (IsP13<WT>::v) img = p13_img(W, N, K);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        wrow[r] = W + (long long)min(row0 + r, N - 1) * (K / WPer<WT>::v);
-        srow[r] = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) + (long long)min(row0 + r, N - 1) * nchunk : nullptr;
+        const long long row = min(row0 + r, N - 1);
+        if constexpr (IsP13<WT>::v) {
+            wrow[r] = reinterpret_cast<const WT*>(img.lo + row * K); srow[r] = img.nib + row * (K / 2); grow[r] = img.sgn + row * (K / 8);
+            rt[r] = img.rt[row];
+        } else {
+            wrow[r] = W + row * (K / WPer<WT>::v);
+            srow[r] = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) + row * nchunk : nullptr;
+            grow[r] = nullptr; rt[r] = 0u;
+        }
+        rpm[r] = p13_rpm(rt[r]);
     }
     // chunk index for (iteration, unroll u): c = cb + u*256 + wid*64 + lane
     auto step = [&](int cb, auto full_tag) {
@@ -524,9 +660,14 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
         for (int u = 0; u < U; ++u) {
             const int c = cb + u * 256 + wid * 64 + lane;
 #pragma unroll
-            for (int r = 0; r < R; ++r)
-                w[u][r] = (FULL || c < nchunk) ? ld16<NT>(wrow[r] + (long long)c * CU<WT>::v) : make_uint4(0, 0, 0, 0);
+            for (int r = 0; r < R; ++r) {
+                if constexpr (IsP13<WT>::v)
+                    w[u][r] = (FULL || c < nchunk) ? p13_load<NT>(reinterpret_cast<const unsigned char*>(wrow[r]), srow[r], grow[r], c) : make_uint4(0, 0, 0, 0);
+                else
+                    w[u][r] = (FULL || c < nchunk) ? ld16<NT>(wrow[r] + (long long)c * CU<WT>::v) : make_uint4(0, 0, 0, 0);
+            }
         }
+        rebuild_block<WT, R, U, true>(w, rpm);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if constexpr (IsMx<WT>::v) {
@@ -548,6 +689,37 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
     int cb = 0;
     for (; cb < cfull; cb += 256 * U) step(cb, std::true_type{});
     for (; cb < nchunk; cb += 256 * U) step(cb, std::false_type{});
+    if constexpr (IsP13<WT>::v) {
+        // an escaped row (rare; the four waves share their rows, so the whole workgroup takes the branch): its sum is taken again from
+        // the raw row in ESC, with the chunk -> (wave, lane) map and the order of the bf16 kernel
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (p13_escaped(rt[r])) {
+                const bf16_t* raw = img.esc + (long long)(rt[r] >> 8) * K;
+                float a = 0.f;
+                auto estep = [&](int cb2, auto full_tag) {
+                    constexpr bool FULL = decltype(full_tag)::value;
+                    uint4 xr[U], w[U];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const int c = cb2 + u * 256 + wid * 64 + lane;
+                        xr[u] = (FULL || c < nchunk) ? *reinterpret_cast<const uint4*>(x + (long long)c * VE) : make_uint4(0, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const int c = cb2 + u * 256 + wid * 64 + lane;
+                        w[u] = (FULL || c < nchunk) ? ld16<NT>(raw + (long long)c * VE) : make_uint4(0, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) a = dotb<bf16_t>(w[u], &xr[u], a);
+                };
+                int c2 = 0;
+                for (; c2 < cfull; c2 += 256 * U) estep(c2, std::true_type{});
+                for (; c2 < nchunk; c2 += 256 * U) estep(c2, std::false_type{});
+                acc[r] = a;
+            }
+        }
+    }
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[r] = wave_sum(acc[r]);
     if (lane == 0) {
@@ -611,15 +783,27 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_qkv_rope_kernel(const WT* __r
     unsigned sa[U][R];                                   // MXFP4 block scales of wa
     const long long rowlen = K / WPer<WT>::v;
     const unsigned char* sbase = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) : nullptr;
+    P13Img img = {};
+    if constexpr (IsP13<WT>::v) img = p13_img(W, (H + 2 * Hk) * hd, K);
+    // a row's load pointers (see gemv_kernel): weights / MXFP4 scales, or the w13 image's LO / NIB / SGN rows
+    auto row_ptrs = [&](long long row, const WT*& wp, const unsigned char*& sp, const unsigned char*& gp) {
+        if constexpr (IsP13<WT>::v) {
+            wp = reinterpret_cast<const WT*>(img.lo + row * K); sp = img.nib + row * (K / 2); gp = img.sgn + row * (K / 8);
+        } else {
+            wp = W + row * rowlen; sp = sbase ? sbase + row * nchunk : nullptr; gp = nullptr;
+        }
+    };
     const int grp0 = blockIdx.x * GV_WAVES + wid;
     stage_x<T, VE, BfImage<T, WT>::v, XPT>(x, norm_w, xs, red, K, eps, [&]() {
         if (PF) {                                         // branch-free (see gemv_kernel)
             long long rows[R];
             int head, i0;
             rows_of(min(grp0, ngroups - 1), rows, head, i0);
-            const WT* rowp[R] = {W + rows[0] * rowlen, W + rows[1] * rowlen};
-            const unsigned char* srow[R] = {sbase ? sbase + rows[0] * nchunk : nullptr, sbase ? sbase + rows[1] * nchunk : nullptr};
-            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, 0, lane, nchunk);
+            const WT* rowp[R];
+            const unsigned char *srow[R], *grow[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) row_ptrs(rows[r], rowp[r], srow[r], grow[r]);
+            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, grow, 0, lane, nchunk);
         }
     });
 
@@ -628,23 +812,40 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_qkv_rope_kernel(const WT* __r
         long long rows[R];
         int head = 0, i0 = 0;
         const bool is_qk = rows_of(grp, rows, head, i0);
-        const WT* rowp[R] = {W + rows[0] * rowlen, W + rows[1] * rowlen};
-        const unsigned char* srow[R] = {sbase ? sbase + rows[0] * nchunk : nullptr, sbase ? sbase + rows[1] * nchunk : nullptr};
+        const WT* rowp[R];
+        const unsigned char *srow[R], *grow[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) row_ptrs(rows[r], rowp[r], srow[r], grow[r]);
         // rotation coefficients of this pair: loaded before the weight stream so the epilogue never waits on memory
         float rc = 1.f, rs = 0.f;
         if (is_qk) { rc = cs[(long long)pos * half + i0]; rs = sn[(long long)pos * half + i0]; }
-        const float sc0 = (!IsMx<WT>::v && wscale) ? (float)wscale[rows[0]] : 1.f, sc1 = (!IsMx<WT>::v && wscale) ? (float)wscale[rows[1]] : 1.f;
+        constexpr bool SCALED = !IsMx<WT>::v && !IsP13<WT>::v;
+        const float sc0 = (SCALED && wscale) ? (float)wscale[rows[0]] : 1.f, sc1 = (SCALED && wscale) ? (float)wscale[rows[1]] : 1.f;
+        unsigned rt[R], rpm[R];                          // w13 row table entries: ahead of the stream too
+#pragma unroll
+        for (int r = 0; r < R; ++r) { rt[r] = IsP13<WT>::v ? img.rt[rows[r]] : 0u; rpm[r] = p13_rpm(rt[r]); }
         float acc[R] = {0.f, 0.f};
         int c0 = 0;
-        if (have) { consume_block<T, WT, R, U, true>(wa, sa, xs, 0, lane, nchunk, acc); c0 = STEP; have = false; }
+        if (have) {
+            rebuild_block<WT, R, U>(wa, rpm);
+            consume_block<T, WT, R, U, true>(wa, sa, xs, 0, lane, nchunk, acc); c0 = STEP; have = false;
+        }
         const int cfull = (nchunk / STEP) * STEP;
         for (; c0 < cfull; c0 += STEP) {
-            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, c0, lane, nchunk);
+            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, grow, c0, lane, nchunk);
+            rebuild_block<WT, R, U>(wa, rpm);
             consume_block<T, WT, R, U, true>(wa, sa, xs, c0, lane, nchunk, acc);
         }
         if (c0 < nchunk) {
-            issue_block<WT, R, U, NT, false>(wa, sa, rowp, srow, c0, lane, nchunk);
+            issue_block<WT, R, U, NT, false>(wa, sa, rowp, srow, grow, c0, lane, nchunk);
+            rebuild_block<WT, R, U>(wa, rpm);
             consume_block<T, WT, R, U, false>(wa, sa, xs, c0, lane, nchunk, acc);
+        }
+        if constexpr (IsP13<WT>::v) {                     // escaped rows: as in gemv_kernel
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (p13_escaped(rt[r]))
+                    acc[r] = rows_escaped_row<T, U, NT, BfImage<T, WT>::v>(img.esc + (long long)(rt[r] >> 8) * K, xs, lane, nchunk);
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = wave_sum(acc[r]);
@@ -723,7 +924,9 @@ static int gemv_launch(const void* x, const void* W, const void* ws, const void*
         // projection) takes U = 1 -- with U = 2 half of the step's instructions are masked (5.39 -> 4.95 us alone, 5.24 -> 4.72 in
         // the step); 4 rows per workgroup are within noise alone and lose in the step (fp8 down 9.94 -> 10.53 us).  The chunk ->
         // (wave, lane) map and every lane's order of accumulation do not depend on R or U: all forms give the same bits (tested)
-        const int u = tune().gemv_splitk_u > 0 ? tune().gemv_splitk_u : (nchunk <= 256 ? 1 : (nchunk <= 512 ? 2 : (nchunk <= 1024 ? 4 : (nchunk <= 1536 ? 6 : 2))));
+        // (w13 image: the rebuild holds more registers per chunk in flight -- down projection, U = 6: 151 VGPRs, 16.9 us; U = 2: 15.0 us)
+        const int u = tune().gemv_splitk_u > 0 ? tune().gemv_splitk_u
+                      : (nchunk <= 256 ? 1 : ((nchunk <= 512 || IsP13<WT>::v) ? 2 : (nchunk <= 1024 ? 4 : (nchunk <= 1536 ? 6 : 2))));
         const int r = tune().gemv_splitk_r > 0 ? tune().gemv_splitk_r : 2;
 #define TEO_SPK(RR, UU) if (r == RR && u == UU) return launch_splitk<T, TO, WT, RR, UU>(x, W, ws, res, y, N, K, st)
         TEO_SPK(2, 1); TEO_SPK(2, 3); TEO_SPK(2, 4); TEO_SPK(2, 6);
@@ -786,6 +989,12 @@ static int gemv_launch(const void* x, const void* W, const void* ws, const void*
         if (fits) return launch_rows<T, TO, WT, 2, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
         return launch_rows<T, TO, WT, 2, 2, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
     }
+    if constexpr (IsP13<WT>::v) {
+        // w13 image: the same 2 x 4 geometry (and bits) without the prefetch under the prologue -- the raw block it would hold across
+        // the prologue costs registers the rebuild needs (gate/up 26.1 -> 25.0 us, lm_head 37.9 -> 35.6 with gemv_variant = 1's form)
+        if (small_k) return launch_rows<T, TO, WT, 2, 4, false, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
+        return launch_rows<T, TO, WT, 2, 4, false>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
+    }
     if constexpr (Is16<T>::v) { if (small_k) return launch_rows<T, TO, WT, 2, 4, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st); }
     return launch_rows<T, TO, WT, 2, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
 }
@@ -796,7 +1005,14 @@ int gemv_w(const void* x, const void* W, const void* wscale, int wfmt, const voi
            int K, float eps, unsigned flags, int dtype, int out_dtype, hipStream_t st) {
     if (N == 0) return TEO_OK;
     const bool swiglu = flags & TEO_GEMM_SWIGLU16;
-    const bool w_fp8 = wfmt == GV_W_FP8, w_mx = wfmt == GV_W_MXFP4;
+    const bool w_fp8 = wfmt == GV_W_FP8, w_mx = wfmt == GV_W_MXFP4, w_p13 = wfmt == GV_W_P13;
+    if (w_p13) {
+        TEO_CHECK_ARG(dtype == TEO_BF16, "teo_gemv: a w13 image holds bf16 weights and needs bf16 activations (dtype %d)", dtype);
+        if (K % 8 != 0) {
+            set_error("teo_gemv: K=%d is not a multiple of the w13 image's 8-element chunk", K);
+            return TEO_ERR_UNSUPPORTED;
+        }
+    }
     const int ve = w_mx ? 32 : (w_fp8 ? 16 : (dtype == TEO_F32 ? 4 : 8));
     TEO_CHECK_ARG(K % ve == 0, "teo_gemv: K=%d must be a multiple of %d", K, ve);
     TEO_CHECK_ARG((reinterpret_cast<uintptr_t>(W) & 15) == 0, "teo_gemv: W must be 16-byte aligned");
@@ -808,6 +1024,10 @@ int gemv_w(const void* x, const void* W, const void* wscale, int wfmt, const voi
         TEO_CHECK_ARG(dtype == TEO_BF16 && wscale != nullptr, "teo_gemv: MXFP4 weights need bf16 activations and block scales");
         if (out_dtype == TEO_F32) return gemv_launch<bf16_t, float, fp4x2_t>(x, W, wscale, norm_w, res, y, N, K, eps, swiglu, st);
         return gemv_launch<bf16_t, bf16_t, fp4x2_t>(x, W, wscale, norm_w, res, y, N, K, eps, swiglu, st);
+    }
+    if (w_p13) {           // the image's sections start on 256-byte boundaries of the allocation: the 16-byte alignment above is all they need
+        if (out_dtype == TEO_F32) return gemv_launch<bf16_t, float, p13_t>(x, W, nullptr, norm_w, res, y, N, K, eps, swiglu, st);
+        return gemv_launch<bf16_t, bf16_t, p13_t>(x, W, nullptr, norm_w, res, y, N, K, eps, swiglu, st);
     }
     if (w_fp8) {
         TEO_CHECK_ARG(dtype == TEO_BF16 && wscale != nullptr, "teo_gemv: fp8 weights need bf16 activations and per-row scales");
@@ -838,7 +1058,8 @@ int gemv(const void* x, const void* W, const void* norm_w, const void* res, void
 int gemv_qkv_rope(const void* x, const void* W, const void* wscale, int wfmt, const void* norm_w, void* qout,
                   const float* cs, const float* sn, const int* d_pos, void* kc, void* vc, void* vtc, int S_max, int H, int Hk,
                   int hd, int K, float eps, int dtype, hipStream_t st) {
-    const bool w_fp8 = wfmt == GV_W_FP8, w_mx = wfmt == GV_W_MXFP4;
+    const bool w_fp8 = wfmt == GV_W_FP8, w_mx = wfmt == GV_W_MXFP4, w_p13 = wfmt == GV_W_P13;
+    TEO_CHECK_ARG(!w_p13 || dtype == TEO_BF16, "gemv_qkv_rope: a w13 image needs bf16 activations");
     const int ve = w_mx ? 32 : (w_fp8 ? 16 : (dtype == TEO_F32 ? 4 : 8));
     TEO_CHECK_ARG(K % ve == 0 && hd >= 2 && (hd & (hd - 1)) == 0, "gemv_qkv_rope: K=%d hd=%d (head_dim must be a power of two)", K, hd);
     TEO_CHECK_ARG((size_t)(K + 1040) * 4 <= 64 * 1024, "gemv_qkv_rope: K=%d too large for LDS staging", K);
@@ -870,6 +1091,7 @@ int gemv_qkv_rope(const void* x, const void* W, const void* wscale, int wfmt, co
 #define TEO_QR4(TT, WW, NTV) if (small_k) { TEO_QR2(TT, WW, NTV, 2, 2); } else { TEO_QR2(TT, WW, NTV, 6, 2); }
     if (w_mx)                  { if (tune().gemv_nt) { TEO_QR4(bf16_t, fp4x2_t, true); } else { TEO_QR4(bf16_t, fp4x2_t, false); } }
     else if (w_fp8)                 { if (tune().gemv_nt) { TEO_QR8(bf16_t, fp8_t, true); } else { TEO_QR8(bf16_t, fp8_t, false); } }
+    else if (w_p13)            { if (tune().gemv_nt) { TEO_QR(bf16_t, p13_t, true); } else { TEO_QR(bf16_t, p13_t, false); } }
     else if (dtype == TEO_F32) { if (tune().gemv_nt) { TEO_QR6(float, float, true); } else { TEO_QR6(float, float, false); } }
     else if (dtype == TEO_F16) { if (tune().gemv_nt) { TEO_QR(f16_t, f16_t, true); } else { TEO_QR(f16_t, f16_t, false); } }
     else                       { if (tune().gemv_nt) { TEO_QR(bf16_t, bf16_t, true); } else { TEO_QR(bf16_t, bf16_t, false); } }

@@ -132,8 +132,9 @@ int gemm_w4a8(const void* A8, const float* a_scale, const void* W4, const void* 
 int quant_rows_fp8(const void* x, const void* norm_w, void* q, float* s, int M, int K, int ldx, float eps, hipStream_t st);
 int gemm_sk_workspace_init(void* ws, hipStream_t st);
 // decode GEMV weight formats: the activations' own type, fp8 e4m3 + one fp32 scale per row, MXFP4 (e2m1 codes + one e8m0 byte per
-// 32-element block along K, [N][K/32]); the last two take bf16 activations
-enum GemvWFmt { GV_W_NATIVE = 0, GV_W_FP8 = 1, GV_W_MXFP4 = 2 };
+// 32-element block along K, [N][K/32]); a w13 image of a bf16 matrix (p13.h: W is the image, no scales).  All but the first take bf16
+// activations
+enum GemvWFmt { GV_W_NATIVE = 0, GV_W_FP8 = 1, GV_W_MXFP4 = 2, GV_W_P13 = 3 };
 int gemv_qkv_rope(const void* x, const void* W, const void* wscale, int wfmt, const void* norm_w, void* qout,
                   const float* cs, const float* sn, const int* d_pos, void* kc, void* vc, void* vtc, int S_max, int H, int Hk,
                   int hd, int K, float eps, int dtype, hipStream_t st);

@@ -442,6 +442,14 @@ int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* 
                       "teo_llama_decode_step: a descriptor carries fp8 (w8) or MXFP4 (w4) decode weights, not both");
         TEO_CHECK_ARG(d->dtype == TEO_BF16, "teo_llama_decode_step: MXFP4 weights need bf16 activations");
     }
+    // w13 images of the bf16 matrices: never beside the fp8 / MXFP4 copies, bf16 only (checked before any launch)
+    if (d->qkv_p13 || d->o_p13 || d->gateup_p13 || d->down_p13 || d->lm_head_p13) {
+        TEO_CHECK_ARG(!w4 && !d->qkv_w8 && !d->o_w8 && !d->gateup_w8 && !d->down_w8 && !d->lm_head8,
+                      "teo_llama_decode_step: a descriptor carries w13 images or fp8 (w8) / MXFP4 (w4) decode weights, not both");
+        TEO_CHECK_ARG(d->dtype == TEO_BF16, "teo_llama_decode_step: w13 images need bf16 activations");
+        TEO_CHECK_ARG(d->hidden % 8 == 0 && (d->heads * d->head_dim) % 8 == 0 && d->inter % 8 == 0,
+                      "teo_llama_decode_step: w13 images need hidden, heads * head_dim and inter to be multiples of 8");
+    }
     const DecodeWs w = decode_carve(d, ws, ws_bytes);
     if (w.total > ws_bytes) {
         set_error("teo_llama_decode_step: workspace %zu < %zu", ws_bytes, w.total);
@@ -453,22 +461,27 @@ int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* 
     // w.h holds the embedding of *s->d_token: written by the previous step's tail (or by teo_llama_decode_begin)
     const bool w8 = d->qkv_w8 != nullptr;              // decode streams the fp8 or MXFP4 copies when they are present
     const int wf = w4 ? GV_W_MXFP4 : (w8 ? GV_W_FP8 : GV_W_NATIVE);
-    auto lin = [&](const void* const* w16, const void* const* q8, const void* const* q4, int l) { return w4 ? q4[l] : (w8 ? q8[l] : w16[l]); };
+    // (a w13 image, where the layer has one, goes in place of the 16-bit matrix: fmt() tells the GEMV which of the two lin() returned)
+    auto p13 = [&](const void* const* im, int l) -> const void* { return (!w4 && !w8 && im) ? im[l] : nullptr; };
+    auto lin = [&](const void* const* w16, const void* const* q8, const void* const* q4, const void* const* im, int l) {
+        return w4 ? q4[l] : (w8 ? q8[l] : (p13(im, l) ? p13(im, l) : w16[l]));
+    };
+    auto fmt = [&](const void* const* im, int l) { return p13(im, l) ? (int)GV_W_P13 : wf; };
     auto scl = [&](const float* const* s8, const uint8_t* const* e4, int l) -> const void* { return w4 ? (const void*)e4[l] : (w8 ? (const void*)s8[l] : nullptr); };
     for (int l = 0; l < d->layers; ++l) {
         if (d->rope_in_attn) {
             // rmsnorm + QKV projection (plain weight stream); RoPE + KV append ride inside the attention kernel
             // (position read from s->d_pos on the device)
             prof_class(TEO_PROF_QKV);
-            TEO_TRY(gemv_w(w.h, lin(d->qkv_w, d->qkv_w8, d->qkv_w4, l), scl(d->qkv_s, d->qkv_e4, l), wf, d->in_norm_w[l], nullptr,
-                           w.qkv, QKV, D, d->eps, 0, dt, dt, st));
+            TEO_TRY(gemv_w(w.h, lin(d->qkv_w, d->qkv_w8, d->qkv_w4, d->qkv_p13, l), scl(d->qkv_s, d->qkv_e4, l), fmt(d->qkv_p13, l), d->in_norm_w[l],
+                           nullptr, w.qkv, QKV, D, d->eps, 0, dt, dt, st));
             prof_class(TEO_PROF_ATTN);
             TEO_TRY(attn_decode(w.qkv, d->k_cache[l], d->v_cache[l], d->vt_cache[l], d->rope_cos, d->rope_sin, w.attn, w.part,
                                 s->d_pos, d->max_seq, H, Hk, hd, 1.0f / sqrtf((float)hd), dt, st));
         } else {
             // rmsnorm -> QKV projection -> RoPE -> KV append in the GEMV epilogue
             prof_class(TEO_PROF_QKV);
-            TEO_TRY(gemv_qkv_rope(w.h, lin(d->qkv_w, d->qkv_w8, d->qkv_w4, l), scl(d->qkv_s, d->qkv_e4, l), wf, d->in_norm_w[l], w.qkv,
+            TEO_TRY(gemv_qkv_rope(w.h, lin(d->qkv_w, d->qkv_w8, d->qkv_w4, d->qkv_p13, l), scl(d->qkv_s, d->qkv_e4, l), fmt(d->qkv_p13, l), d->in_norm_w[l], w.qkv,
                                   d->rope_cos, d->rope_sin, s->d_pos, d->k_cache[l], d->v_cache[l], d->vt_cache[l], d->max_seq,
                                   H, Hk, hd, D, d->eps, dt, st));
             prof_class(TEO_PROF_ATTN);
@@ -476,19 +489,20 @@ int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* 
                                 d->max_seq, H, Hk, hd, 1.0f / sqrtf((float)hd), dt, st));
         }
         prof_class(TEO_PROF_O);
-        TEO_TRY(gemv_w(w.attn, lin(d->o_w, d->o_w8, d->o_w4, l), scl(d->o_s, d->o_e4, l), wf, nullptr, w.h, w.h, D, H * hd, d->eps,
+        TEO_TRY(gemv_w(w.attn, lin(d->o_w, d->o_w8, d->o_w4, d->o_p13, l), scl(d->o_s, d->o_e4, l), fmt(d->o_p13, l), nullptr, w.h, w.h, D, H * hd, d->eps,
                        0, dt, dt, st));
         prof_class(TEO_PROF_GATEUP);
-        TEO_TRY(gemv_w(w.h, lin(d->gateup_w, d->gateup_w8, d->gateup_w4, l), scl(d->gateup_s, d->gateup_e4, l), wf, d->post_norm_w[l], nullptr,
+        TEO_TRY(gemv_w(w.h, lin(d->gateup_w, d->gateup_w8, d->gateup_w4, d->gateup_p13, l), scl(d->gateup_s, d->gateup_e4, l), fmt(d->gateup_p13, l), d->post_norm_w[l], nullptr,
                        w.act, 2 * F, D, d->eps, TEO_GEMM_SWIGLU16, dt, dt, st));
         prof_class(TEO_PROF_DOWN);
-        TEO_TRY(gemv_w(w.act, lin(d->down_w, d->down_w8, d->down_w4, l), scl(d->down_s, d->down_e4, l), wf, nullptr, w.h, w.h, D, F, d->eps,
+        TEO_TRY(gemv_w(w.act, lin(d->down_w, d->down_w8, d->down_w4, d->down_p13, l), scl(d->down_s, d->down_e4, l), fmt(d->down_p13, l), nullptr, w.h, w.h, D, F, d->eps,
                        0, dt, dt, st));
     }
     {
         const bool h8 = d->lm_head8 != nullptr;          // (the MXFP4 mode keeps a 16-bit lm_head)
         prof_class(TEO_PROF_LM_HEAD);
-        TEO_TRY(gemv_w(w.h, h8 ? d->lm_head8 : d->lm_head, h8 ? d->lm_head_s : nullptr, h8, d->final_norm_w, nullptr,
+        const bool hp = !h8 && d->lm_head_p13 != nullptr;
+        TEO_TRY(gemv_w(w.h, h8 ? d->lm_head8 : (hp ? d->lm_head_p13 : d->lm_head), h8 ? d->lm_head_s : nullptr, hp ? (int)GV_W_P13 : (int)h8, d->final_norm_w, nullptr,
                        s->d_logits, d->vocab, D, d->eps, 0, dt, TEO_F32, st));
     }
     // argmax -> append/advance/stop test -> embedding row of the next token into w.h, one launch

@@ -13,6 +13,7 @@ Weights arrive keyed by the reference's state-dict names (SURVEY.md section 8a r
     (prefill MFMA attention wants key-contiguous values) -- 288 GB of HBM3E pays for the second V layout.
 """
 import ctypes as C
+import logging
 import math
 import warnings
 
@@ -202,6 +203,75 @@ def quantize_mxfp4_rows(w, max_elems=1 << 21):
     return q, e
 
 
+# ---- w13 image: a lossless 13-bit-per-weight picture of a bf16 matrix for the decode GEMVs (format: include/teo_hip.h at teo_gemv,
+# teochat_amd/csrc/p13.h).  For a pattern b: lo = b & 0xFF, P = (b >> 8) & 0x7F, s = b >> 15; per row rp = max(1, Pmax - 14) and a 4-bit
+# code n = 0 (P == 0) or P - rp + 1 (rp <= P <= rp + 14); a row holding any other P is "escaped" and kept raw.
+def w13_sections(N, K, n_escaped=0):
+    """Byte offsets (rt, lo, nib, sgn, esc) of the five sections and the image's total size."""
+    def up(v):
+        return (v + 255) // 256 * 256
+    lo = up(4 * N)
+    nib = lo + up(N * K)
+    sgn = nib + up(N * K // 2)
+    esc = sgn + up(N * K // 8)
+    return (0, lo, nib, sgn, esc), esc + 2 * n_escaped * K
+
+
+def pack_w13(W):
+    """bf16 W [N, K] (K % 8 == 0) -> (image: uint8 tensor on W's device, number of escaped rows).  Integer ops on W's own device."""
+    if W.dtype != torch.bfloat16 or W.dim() != 2 or W.shape[1] % 8:
+        raise ValueError(f"pack_w13 takes a bfloat16 [N, K] matrix with K % 8 == 0, got {W.dtype} {tuple(W.shape)}")
+    N, K = W.shape
+    b = W.contiguous().view(torch.uint8).view(N, K, 2)            # little-endian: [..., 0] = lo, [..., 1] = sign + the upper 7 exponent bits
+    hi = b[:, :, 1]
+    P = hi & 0x7F
+    rp = (P.amax(dim=1).to(torch.int32) - 14).clamp_(min=1)       # 1 .. 113
+    m = P - rp.to(torch.uint8)[:, None]                           # uint8, wraps: 0 .. 14 exactly for rp <= P <= rp + 14
+    zero = P == 0
+    escaped = ((m > 14) & ~zero).any(dim=1)
+    n = torch.where(zero, torch.zeros_like(m), m.clamp_(max=14) + 1)      # 0 .. 15 (an escaped row's codes are clamped: valid bytes, never used)
+    del m, zero, P
+    n = n.view(N, K // 8, 2, 4)
+    nib = n[:, :, 0, :] | (n[:, :, 1, :] << 4)                    # byte i of chunk c = n(8c + i) | n(8c + 4 + i) << 4
+    del n
+    s = (hi >> 7).view(N, K // 8, 8)
+    sgn = s[:, :, 0].clone()
+    for i in range(1, 8):
+        sgn |= s[:, :, i] << i                                     # bit i of chunk c = s(8c + i)
+    del s
+    n_esc = int(escaped.sum())
+    slot = torch.cumsum(escaped.to(torch.int32), 0) - 1
+    rt = torch.where(escaped, (slot << 8) | 0xFF, rp).to(torch.int32)
+    (o_rt, o_lo, o_nib, o_sgn, o_esc), total = w13_sections(N, K, n_esc)
+    img = torch.zeros(total, dtype=torch.uint8, device=W.device)
+    img[o_rt:o_rt + 4 * N] = rt.view(torch.uint8)
+    img[o_lo:o_lo + N * K].view(N, K).copy_(b[:, :, 0])
+    img[o_nib:o_nib + N * K // 2].view(N, K // 8, 4).copy_(nib)
+    img[o_sgn:o_sgn + N * K // 8].view(N, K // 8).copy_(sgn)
+    if n_esc:
+        img[o_esc:].view(n_esc, 2 * K).copy_(b.view(N, 2 * K)[escaped])
+    return img, n_esc
+
+
+def unpack_w13(image, N, K):
+    """The bf16 matrix [N, K] a w13 image holds (bit-exact inverse of pack_w13)."""
+    (o_rt, o_lo, o_nib, o_sgn, o_esc), _ = w13_sections(N, K)
+    rt = image[o_rt:o_rt + 4 * N].view(torch.int32)
+    escaped = (rt & 0xFF) == 0xFF
+    rp = (rt & 0xFF).to(torch.uint8)
+    nib = image[o_nib:o_nib + N * K // 2].view(N, K // 8, 1, 4)
+    n = torch.cat([nib & 0x0F, nib >> 4], dim=2).reshape(N, K)
+    P = torch.where(n == 0, torch.zeros_like(n), n + (rp[:, None] - 1))
+    sgn = image[o_sgn:o_sgn + N * K // 8].view(N, K // 8, 1)
+    s = torch.cat([(sgn >> i) & 1 for i in range(8)], dim=2).reshape(N, K)
+    out = torch.stack([image[o_lo:o_lo + N * K].view(N, K), P | (s << 7)], dim=2).contiguous()          # [N, K, 2] bytes
+    if bool(escaped.any()):
+        slots = (rt[escaped] >> 8).long()
+        n_esc = int(escaped.sum())
+        out.view(N, 2 * K)[escaped] = image[o_esc:o_esc + 2 * n_esc * K].view(n_esc, 2 * K)[slots]
+    return out.view(N, 2 * K).view(torch.bfloat16)
+
+
 def rope_tables(head_dim, theta, max_pos):
     """cos/sin [max_pos, hd/2] fp32; inv_freq and pos*inv_freq in fp32 on the host (tf LlamaRotaryEmbedding)."""
     inv = 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.float32) / head_dim))
@@ -210,7 +280,8 @@ def rope_tables(head_dim, theta, max_pos):
 
 
 class TeoEngine:
-    def __init__(self, state_dict, config, dtype=torch.bfloat16, device="cuda:0", max_seq=None, weight_format=None, mxfp4_only=False):
+    def __init__(self, state_dict, config, dtype=torch.bfloat16, device="cuda:0", max_seq=None, weight_format=None, mxfp4_only=False,
+                 decode_pack=True):
         self.lib = L.load()                       # raises TeoLibraryError when the HIP library is missing
         if not torch.cuda.is_available():
             raise RuntimeError("TeoEngine needs an MI355X (no CPU fallback exists for the product path)")
@@ -236,6 +307,12 @@ class TeoEngine:
             if self.weight_format != "mxfp4":
                 raise ValueError("mxfp4_only needs weight_format='mxfp4'")
             self._check_mxfp4_sizes("mxfp4_only")
+        # decode_pack: the single-conversation decode step streams w13 images (pack_w13: 13 bits per weight, bit-identical results) of
+        # qkv / o / gateup / down / lm_head beside the 16-bit matrices, which prefill and the batched paths keep using.  bf16 engines
+        # with native weights only; skipped when the device is short of memory (see _build_decode_pack)
+        self.decode_pack = False
+        self._p13 = None
+        self.decode_pack_stats = None
         self._keep = []                           # host pointer arrays referenced by the descriptors
         self._ws = {}
         self._phase_depth = 0
@@ -250,6 +327,8 @@ class TeoEngine:
         self._load_llama(state_dict)
         self._alloc_cache()
         self._alloc_decode_state(max_new=max(4096, self.max_seq))
+        if decode_pack and self._decode_pack_applies():
+            self._set_decode_pack(True)
 
     def _check_mxfp4_sizes(self, what):
         c = self.cfg
@@ -424,6 +503,64 @@ class TeoEngine:
                     w4[k].append(q)
                     e4[k].append(e)
             self.llama_w4 = (w4, e4)
+
+    # ------------------------------------------------------------------ w13 images of the decode weights
+    _P13_KINDS = ("qkv", "o", "gateup", "down")
+
+    def _decode_pack_applies(self):
+        c = self.cfg
+        return (self.dtype == torch.bfloat16 and self.weight_format == "native" and not self.mxfp4_only
+                and c.hidden_size % 8 == 0 and c.intermediate_size % 8 == 0 and (c.num_attention_heads * c.head_dim) % 8 == 0)
+
+    def _build_decode_pack(self):
+        """Pack every decode matrix, one at a time (the packer's temporaries are freed between matrices).  Returns False, with one log
+        line, when free device memory is below twice the images' total."""
+        mats = {k: self.llama_w[k] for k in self._P13_KINDS}
+        mats["lm_head"] = [self.lm_head]
+        total = sum(w13_sections(*w.shape)[1] for ws in mats.values() for w in ws)
+        free = torch.cuda.mem_get_info(self.device)[0]
+        if free < 2 * total:
+            logging.getLogger(__name__).warning("decode_pack skipped: %.2f GB free on %s, the w13 images need %.2f GB (and twice that to build)",
+                                                free / 1e9, self.device, total / 1e9)
+            return False
+        imgs, stats, nbytes = {}, {}, 0
+        try:
+            with torch.cuda.device(self.device):
+                for k, ws in mats.items():
+                    imgs[k], esc = [], 0
+                    for w in ws:
+                        img, n = pack_w13(w)
+                        imgs[k].append(img)
+                        esc += n
+                        nbytes += img.numel()
+                    stats[k] = {"rows": sum(int(w.shape[0]) for w in ws), "escaped": esc}
+        except torch.cuda.OutOfMemoryError:
+            # several engines filling one device at once (the free-memory figure above is each one's own snapshot): give the images back
+            # and stream the 16-bit matrices, the same kernels' bf16 instantiation
+            imgs.clear()
+            img = None
+            torch.cuda.empty_cache()
+            logging.getLogger(__name__).warning("decode_pack skipped: %s ran out of memory while the w13 images (%.2f GB) were built",
+                                                self.device, total / 1e9)
+            return False
+        stats["image_bytes"] = nbytes
+        self._p13 = {"imgs": imgs, "arrs": {k: self._arr(imgs[k]) for k in self._P13_KINDS}}
+        self.decode_pack_stats = stats
+        return True
+
+    def _set_decode_pack(self, on):
+        d = self.llama_desc
+        if on and self._p13 is None and not self._build_decode_pack():
+            on = False
+        if on:
+            a = self._p13["arrs"]
+            d.qkv_p13, d.o_p13, d.gateup_p13, d.down_p13 = a["qkv"], a["o"], a["gateup"], a["down"]
+            d.lm_head_p13 = self._p13["imgs"]["lm_head"][0].data_ptr()
+        else:
+            d.qkv_p13 = d.o_p13 = d.gateup_p13 = d.down_p13 = None
+            d.lm_head_p13 = None
+        self.decode_pack = bool(on)
+        self._drop_graph()                        # the pointers are baked into a captured decode step
 
     def _alloc_cache(self):
         c = self.cfg
@@ -734,7 +871,7 @@ class TeoEngine:
             L.check(self.lib.teo_llama_decode_begin(C.byref(self.llama_desc), C.byref(self.decode_state), _p(ws), ws.numel(),
                                                     st), "teo_llama_decode_begin")
 
-    def set_options(self, prefill_fp8=None, rope_in_attn=None, batch_mxfp4=None, prefill_mxfp4=None, prefill_mxfp4_a8=None):
+    def set_options(self, prefill_fp8=None, rope_in_attn=None, batch_mxfp4=None, prefill_mxfp4=None, prefill_mxfp4_a8=None, decode_pack=None):
         """Per-engine options of the LLaMA descriptor (include/teo_hip.h teo_llama_desc): `prefill_fp8` = w8a8 prefill on the fp8
         MFMA (lossy, needs weight_format='fp8'), `rope_in_attn` = RoPE + KV append inside the decode attention kernel instead of
         the QKV GEMV epilogue (same values).  Not process-global: two engines in one process can differ.
@@ -748,8 +885,16 @@ class TeoEngine:
         `prefill_mxfp4_a8` (default False; needs weight_format='mxfp4', those sizes, and prefill_mxfp4 on -- already, or in the same call):
         those Linear layers run teo_quant_rows_fp8 + teo_gemm_w4a8 (teo_llama_desc.prefill_w4a8): per-token e4m3 activations against the
         same MXFP4 arrays on the block-scaled MFMA.  Lossy, never a default; free to switch on and off, also on an `mxfp4_only` engine.
-        Switching prefill_mxfp4 off while it is on: ValueError."""
+        Switching prefill_mxfp4 off while it is on: ValueError.
+        `decode_pack` (default on for a bf16 engine with native weights): the single-conversation decode step streams the w13 images
+        (pack_w13) instead of the 16-bit matrices -- the same bits out, 0.8125 x the weight bytes per token, the images' memory beside the
+        matrices.  Switching it flips the descriptor's pointers and drops a captured decode graph; True on an engine it does not apply to
+        (not bf16, fp8 / MXFP4 weights, a K that is no multiple of 8): ValueError.  The images are built on first use."""
         d = self.llama_desc
+        if decode_pack is not None and bool(decode_pack) != self.decode_pack:
+            if decode_pack and not self._decode_pack_applies():
+                raise ValueError("decode_pack needs a bf16 engine with native weights and hidden / heads * head_dim / intermediate sizes that are multiples of 8")
+            self._set_decode_pack(bool(decode_pack))
         a8 = self.prefill_mxfp4_a8 if prefill_mxfp4_a8 is None else bool(prefill_mxfp4_a8)
         w4 = self.prefill_mxfp4 if prefill_mxfp4 is None else bool(prefill_mxfp4)
         if prefill_mxfp4_a8:
