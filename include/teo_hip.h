@@ -67,6 +67,19 @@ const char* teo_gemm_w4_plan(int M, int N, int K, unsigned flags, int out_dtype,
 /* The same for teo_gemm_w4a8 ("gemm_w4a8_64", "gemm_w4a8_128", "gemm_w4a8_wide", "gemm_w4a8_big"; "" for a shape it does not take, a
  * TEO_F16 output included).  From M, N, the flags and the CU count alone: no teo_tune key, no workspace. */
 const char* teo_gemm_w4a8_plan(int M, int N, int K, unsigned flags, int out_dtype, int cu_count);
+/* The decode GEMV dispatch as one line, under the calling thread's tune block; nothing is launched.  teo_gemv_plan: what teo_gemv
+ * (wfmt 0; 3 with TEO_GEMV_W13), teo_gemv_w8 (wfmt 1) or teo_gemv_w4 (wfmt 2) would run for W[N, K] with these flags, with (has_norm = 1) or
+ * without a fused RMSNorm (a residual does not enter the choice); teo_gemv_qkv_plan: the fused QKV + RoPE GEMV of teo_llama_decode_step for
+ * H query heads, Hk key / value heads of hd elements and hidden size K.  The line reads
+ *   "<kernel> <x>/<y>/<W> R<rows> U<chunks> pf<0|1> x<2|6> nt<0|1> sw<0|1> wg<workgroups> lds<bytes> img<0|16|32>"
+ * with kernel one of "gemv_rows", "gemv_splitk", "gemv_qkv_rope"; x / y / W the element types ("f32", "bf16", "f16", "fp8", "mxfp4", "w13");
+ * R x U the rows per wave (split-K: per workgroup) and the 16-byte weight chunks per lane and step; pf the first block's prefetch under
+ * the x prologue, x that prologue's register chunks (0 for split-K, which has none); nt non-temporal loads; sw the SwiGLU epilogue; lds the
+ * launch's dynamic LDS; img the element width of the x image in LDS (16: a step's U chunks are summed before they join the row, so U enters
+ * the fp32 order of the sums; 32: it does not; 0: split-K stages no image).  Aligned operands are assumed.  "" where the entry point would refuse the call (its reason is teo_last_error's)
+ * and for N = 0, which launches nothing.  The choice itself is gemv_plan.hip's; its rules are listed there in the order they are tried. */
+const char* teo_gemv_plan(int N, int K, int wfmt, unsigned flags, int has_norm, int dtype, int out_dtype);
+const char* teo_gemv_qkv_plan(int K, int H, int Hk, int hd, int wfmt, int dtype);
 /* Size of a struct of this header as the LIBRARY was built with it (0 for an unknown name): a binding checks its own layout against it
  * at load time -- "teo_vit_desc", "teo_proj_desc", "teo_llama_desc", "teo_decode_state", "teo_decode_batch_state", "teo_attn_args",
  * "teo_verify_state", "teo_decode_stream_state". */
@@ -83,7 +96,10 @@ size_t teo_sizeof(const char* struct_name);
  * A block may be read by any number of threads; changing it while another thread runs a call under it is the caller's race.
  * teo_tune_destroy on a block still bound by ANOTHER thread or named by a live descriptor is a use-after-free of the caller's making.
  * teo_tune_get(NULL, key, &v) reads the shipped default; teo_tune_keys() lists every key, space separated.  Keys (0 / 1 unless said):
- *   decode GEMV   : "gemv_variant" (-1 default; 0..2, 10..13: row-group geometry; fp32 order), "gemv_nt" (non-temporal weight loads),
+ *   decode GEMV   : "gemv_variant" (row-group geometry, R rows x U chunks per step; fp32 order.  -1 default: split-K where it applies, else
+ *                   the format's own geometry; 0: 4 x 2, 1: 2 x 4, both without the prefetch, 2: 2 x 8 with it -- every weight format; 10..13:
+ *                   fp8 2 x 4 / 4 x 2 / 2 x 2 / 4 x 4, MXFP4 the same but 11 unmapped (its default 4 x 2), nothing for the other formats; any
+ *                   value >= 0 turns split-K off), "gemv_nt" (non-temporal weight loads),
  *                   "gemv_max_blocks" (workgroup cap), "gemv_small_k" (x prologue sized to K <= 4096; bit-identical), "gemv_splitk_u" (chunks per thread and step of the split-K GEMV: 0 auto, 1/2/3/4/6), "gemv_splitk_r" (its rows per workgroup: 0 auto, 2/4)
  *   prefill GEMM  : "gemm_bm" (tile rows of the plain kernel: 0 auto, 64, 128), "gemm_depth", "gemm_sk" (stream-K: 0 off, 1 auto, 2 force),
  *                   "gemm_wide" (0 off, 1 auto, 2 force), "gemm_wide_sched", "gemm_wide_group", "gemm_big" (0 off, 1 auto, 2 force),

@@ -119,6 +119,8 @@ _SIGS = {
     "teo_gemm_fp8_plan": (C.c_char_p, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int]),
     "teo_gemm_w4_plan": (C.c_char_p, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]),
     "teo_gemm_w4a8_plan": (C.c_char_p, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]),
+    "teo_gemv_plan": (C.c_char_p, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int]),
+    "teo_gemv_qkv_plan": (C.c_char_p, [C.c_int] * 6),
     "teo_sizeof": (C.c_size_t, [C.c_char_p]),
     "teo_tune_create": (C.c_void_p, []),
     "teo_tune_destroy": (C.c_int, [C.c_void_p]),

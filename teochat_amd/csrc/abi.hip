@@ -131,6 +131,32 @@ const char* teo_gemm_w4a8_plan(int M, int N, int K, unsigned flags, int out_dtyp
     const bool ok = (out_dtype == TEO_BF16 || out_dtype == TEO_F32) && teo::gemm_w4a8_ok(M, N, K, K, ldc, flags, nullptr, nullptr, nullptr, nullptr, nullptr);
     return teo::plan_gemm_w4a8({M, N, K, K, ldc, TEO_ACT_NONE, flags, TEO_BF16, out_dtype, ok}, teo::tune(), cu_count).name;
 }
+// the decode GEMV plans: the entry points' own checks (placeholder operands: any aligned non-null address) and planner, nothing launched
+static thread_local char g_gemv_plan[160] = "";
+const char* teo_gemv_plan(int N, int K, int wfmt, unsigned flags, int has_norm, int dtype, int out_dtype) {
+    alignas(16) static const char operand[16] = {};
+    const void* any = operand;
+    if (!dtype_ok(dtype) || !dtype_ok(out_dtype) || N <= 0 || K <= 0 || wfmt < GV_W_NATIVE || wfmt > GV_W_P13) return "";
+    teo::GemvPlan g;
+    const bool scaled = wfmt == GV_W_FP8 || wfmt == GV_W_MXFP4;
+    if (teo::gemv_w(any, any, scaled ? any : nullptr, wfmt, has_norm ? any : nullptr, nullptr, nullptr, N, K, 0.f, flags & ~TEO_GEMV_W13, dtype,
+                    out_dtype, nullptr, &g) != TEO_OK)
+        return "";
+    teo::gemv_plan_line({N, K, wfmt, dtype, out_dtype, (flags & TEO_GEMM_SWIGLU16) != 0, has_norm != 0, 0, 0, 0}, g, g_gemv_plan, sizeof g_gemv_plan);
+    return g_gemv_plan;
+}
+const char* teo_gemv_qkv_plan(int K, int H, int Hk, int hd, int wfmt, int dtype) {
+    alignas(16) static const char operand[16] = {};
+    const void* any = operand;
+    if (!dtype_ok(dtype) || K <= 0 || H <= 0 || Hk <= 0 || wfmt < GV_W_NATIVE || wfmt > GV_W_P13) return "";
+    teo::GemvPlan g;
+    const bool scaled = wfmt == GV_W_FP8 || wfmt == GV_W_MXFP4;
+    if (teo::gemv_qkv_rope(any, any, scaled ? any : nullptr, wfmt, any, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, H, Hk, hd, K,
+                           0.f, dtype, nullptr, &g) != TEO_OK)
+        return "";
+    teo::gemv_plan_line({(H + 2 * Hk) * hd, K, wfmt, dtype, dtype, false, true, H, Hk, hd}, g, g_gemv_plan, sizeof g_gemv_plan);
+    return g_gemv_plan;
+}
 
 teo_tune* teo_tune_create(void) { return new (std::nothrow) teo_tune(); }
 int teo_tune_destroy(teo_tune* t) {

@@ -1,8 +1,7 @@
 // The GEMM dispatch as data: plan_gemm / plan_gemm_fp8 (gemm_plan.hip) choose the tile family and its geometry from the problem, the
 // tune block and the CU count, without any HIP call; the launch helpers of gemm*.hip take that plan and only launch.
 #pragma once
-#include <type_traits>
-
+#include "dispatch.h"      // with_flags / int_c: how the launch helpers turn a plan into template arguments
 #include "tune.h"
 
 namespace teo {
@@ -56,17 +55,5 @@ GemmPlan plan_gemm(const GemmProblem& p, const teo_tune& t, int cu_count, bool h
 GemmPlan plan_gemm_fp8(const GemmProblem& p, const teo_tune& t, int cu_count, bool have_workspace);
 GemmPlan plan_gemm_w4(const GemmProblem& p, const teo_tune& t, int cu_count);      // aligned = gemm_w4_ok of the call
 GemmPlan plan_gemm_w4a8(const GemmProblem& p, const teo_tune& t, int cu_count);    // aligned = gemm_w4a8_ok of the call and a bf16 / f32 output
-
-// f(std::integral_constant<bool, b>...) with every runtime flag turned into a compile-time one: the launch helpers' way of picking a
-// template instantiation (each call instantiates f for all 2^n combinations of its flags, no more)
-template <int V>
-using int_c = std::integral_constant<int, V>;
-template <typename F>
-decltype(auto) with_flags(F&& f) { return f(); }
-template <typename F, typename... B>
-decltype(auto) with_flags(F&& f, bool b, B... rest) {
-    if (b) return with_flags([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
-    return with_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
-}
 
 }  // namespace teo

@@ -19,8 +19,6 @@
 
 namespace teo {
 
-constexpr int GV_WAVES = 4;           // waves per workgroup
-constexpr int GV_THREADS = GV_WAVES * 64;
 typedef unsigned char fp8_t;          // OCP e4m3fn bits
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -221,19 +219,13 @@ __device__ __forceinline__ int xs_off(int k) {
     const int c = k / VE, g = (k % VE) >> 2;
     return (((c >> 6) * (VE / 4) + g) << 8) + ((c & 63) << 2);
 }
-template <int VE>
-static size_t xs_lds_bytes(int K) { return ((size_t)((K / VE + 63) / 64) * 64 * VE + 8) * sizeof(float); }
 // bf16 image: 16-byte pieces, lane-linear per piece index g = (k % VE) / 8 (VE = 8: the plain row)
 template <int VE>
 __device__ __forceinline__ int xb_off(int k) {
     const int c = k / VE, g = (k % VE) >> 3;
     return ((((c >> 6) * (VE / 8) + g) << 6) + (c & 63)) * 8 + (k & 7);
 }
-template <int VE>
-static size_t xb_lds_bytes(int K) { return (size_t)((K / VE + 63) / 64) * 64 * VE * 2 + 8 * sizeof(float); }
-template <bool XB, int VE>
-static size_t x_image_bytes(int K) { return XB ? xb_lds_bytes<VE>(K) : xs_lds_bytes<VE>(K); }
-// scratch floats behind the image
+// scratch floats behind the image (its size in bytes: gemv_plan.hip x_image_bytes)
 template <bool XB, int VE>
 __device__ __forceinline__ float* x_image_end(float* xs, int nchunk) {
     const int padded = ((nchunk + 63) / 64) * 64 * VE;
@@ -878,131 +870,87 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_qkv_rope_kernel(const WT* __r
 }
 
 // ------------------------------------------------------------------------------------------------
-// host dispatch  (kernels: `res` and the output may be the same buffer -- in-place residual add -- so neither is __restrict__)
+// host side: the argument checks, then the planner's choice (gemv_plan.hip) handed to one launch helper per kernel template.  A helper
+// maps the plan's geometry to an instantiation through the list of the geometries its weight class can reach and chooses nothing.
+// (kernels: `res` and the output may be the same buffer -- in-place residual add -- so neither is __restrict__)
 // ------------------------------------------------------------------------------------------------
-template <typename T, typename TO, typename WT, int R, int U, bool PF, int XPT = 6>
-static int launch_rows(const void* x, const void* W, const void* ws, const void* norm_w, const void* res, void* y, int N,
-                       int K, float eps, bool swiglu, hipStream_t st) {
-    if (PF && K / Vec16<WT>::N < 64 * U)          // the unconditional prefetch needs one full step per row
-        return launch_rows<T, TO, WT, R, U, false>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);   // (short rows: the default prologue)
-    const int ngroups = swiglu ? cdiv(N / 2, R / 2) : cdiv(N, R);
-    int blocks = cdiv(ngroups, GV_WAVES);
-    if (blocks > tune().gemv_max_blocks) blocks = tune().gemv_max_blocks;
-    const size_t lds = x_image_bytes<RowsImage16<T, WT>::v, Vec16<WT>::N>(K);
-#define TEO_GV(NTV, SW)                                                                                              \
-    TEO_KLAUNCH((gemv_kernel<T, TO, WT, R, U, PF, NTV, SW, XPT>), blocks, GV_THREADS, lds, st, (const T*)x, (const WT*)W, (const WScaleT<WT>*)ws, \
-                (const T*)norm_w, \
-                (const T*)res, (TO*)y, N, K, eps)
-    if (tune().gemv_nt) { if (swiglu) TEO_GV(true, true); else TEO_GV(true, false); }
-    else           { if (swiglu) TEO_GV(false, true); else TEO_GV(false, false); }
-#undef TEO_GV
+struct GemvArgs {
+    const void *x, *W, *ws, *norm_w, *res;
+    void* y;
+    int N, K;
+    float eps;
+};
+
+template <typename T, typename TO, typename WT, int R, int U, bool PF, int XPT>
+static int rows_form(const GemvPlan& g, const GemvArgs& a, hipStream_t st) {
+    with_flags([&](auto nt, auto sw) {
+        TEO_KLAUNCH((gemv_kernel<T, TO, WT, R, U, PF, decltype(nt)::value, decltype(sw)::value, XPT>), g.blocks, GV_THREADS, g.lds_bytes, st,
+                    (const T*)a.x, (const WT*)a.W, (const WScaleT<WT>*)a.ws, (const T*)a.norm_w, (const T*)a.res, (TO*)a.y, a.N, a.K, a.eps);
+    }, g.nt, g.swiglu);
     TEO_LAUNCH_CHECK("gemv");
     return TEO_OK;
 }
+template <typename T, typename TO, typename WT>
+static int launch_rows(const GemvPlan& g, const GemvArgs& a, hipStream_t st) {
+#define TEO_GV_FORM(R_, U_, PF_, XPT_) \
+    if (g.R == R_ && g.U == U_ && g.prefetch == PF_ && g.xpt == XPT_) return rows_form<T, TO, WT, R_, U_, PF_, XPT_>(g, a, st)
+    // gemv_variant 0 / 1 / 2 (and 2's short rows): every weight class
+    TEO_GV_FORM(4, 2, false, 6); TEO_GV_FORM(2, 4, false, 6); TEO_GV_FORM(2, 8, true, 6); TEO_GV_FORM(2, 8, false, 6);
+    if constexpr (sizeof(WT) == 1) {              // fp8 / MXFP4: four geometries under either prologue, and their short rows
+        TEO_GV_FORM(2, 4, true, 2); TEO_GV_FORM(4, 2, true, 2); TEO_GV_FORM(2, 2, true, 2); TEO_GV_FORM(4, 4, true, 2);
+        TEO_GV_FORM(2, 4, true, 6); TEO_GV_FORM(4, 2, true, 6); TEO_GV_FORM(2, 2, true, 6); TEO_GV_FORM(4, 4, true, 6);
+        TEO_GV_FORM(2, 2, false, 6); TEO_GV_FORM(4, 4, false, 6);
+    } else if constexpr (IsP13<WT>::v) {          // w13 image: 2 x 4 without the prefetch
+        TEO_GV_FORM(2, 4, false, 2);
+        // no plan reaches these two: they have been part of the library's device code since the image was added, and the set of
+        // instantiations is not this dispatch's to change (they go with the kernel clean-up)
+        TEO_GV_FORM(2, 4, true, 2); TEO_GV_FORM(2, 4, true, 6);
+    } else {                                      // bf16 / f16 / f32: 2 x 4; the small prologue for 16-bit activations
+        TEO_GV_FORM(2, 4, true, 6);
+        if constexpr (Is16<T>::v) TEO_GV_FORM(2, 4, true, 2);
+    }
+#undef TEO_GV_FORM
+    set_error("gemv: no row kernel of %d x %d, prefetch %d, %d x chunks for this weight format", g.R, g.U, (int)g.prefetch, g.xpt);
+    return TEO_ERR_UNSUPPORTED;
+}
 
 template <typename T, typename TO, typename WT, int R, int U>
-static int launch_splitk(const void* x, const void* W, const void* ws, const void* res, void* y, int N, int K, hipStream_t st) {
-    const int blocks = cdiv(N, R);
-    const WScaleT<WT>* s = (const WScaleT<WT>*)ws;
-    if (tune().gemv_nt)
-        TEO_KLAUNCH((gemv_splitk_kernel<T, TO, WT, R, U, true>), blocks, GV_THREADS, 0, st, (const T*)x, (const WT*)W, s, (const T*)res, (TO*)y, N, K);
-    else
-        TEO_KLAUNCH((gemv_splitk_kernel<T, TO, WT, R, U, false>), blocks, GV_THREADS, 0, st, (const T*)x, (const WT*)W, s, (const T*)res, (TO*)y, N, K);
+static int splitk_form(const GemvPlan& g, const GemvArgs& a, hipStream_t st) {
+    with_flags([&](auto nt) {
+        TEO_KLAUNCH((gemv_splitk_kernel<T, TO, WT, R, U, decltype(nt)::value>), g.blocks, GV_THREADS, 0, st, (const T*)a.x, (const WT*)a.W,
+                    (const WScaleT<WT>*)a.ws, (const T*)a.res, (TO*)a.y, a.N, a.K);
+    }, g.nt);
     TEO_LAUNCH_CHECK("gemv_splitk");
     return TEO_OK;
 }
-
 template <typename T, typename TO, typename WT>
-static int gemv_launch(const void* x, const void* W, const void* ws, const void* norm_w, const void* res, void* y, int N, int K,
-                       float eps, bool swiglu, hipStream_t st) {
-    // few long rows without a fused norm (o / down projections): split-K workgroups, 2 rows each (measured best).
-    // U is chosen so that ONE step covers the whole row (256*U chunks): every load of the workgroup is in flight at once
-    // instead of 2-3 dependent steps (down projection, K = 11008: 3 steps of U = 2 -> 1 step of U = 6).
-    if (!swiglu && norm_w == nullptr && N <= 8192 && tune().gemv_variant < 0) {
-        const int nchunk = K / Vec16<WT>::N;
-        // round 4 sweep (tools/bench_kernels.py gemv_splitk_sweep -> profiles/r04_gemv_splitk_sweep.txt): a row of <= 256 chunks (fp8 o
-        // projection) takes U = 1 -- with U = 2 half of the step's instructions are masked (5.39 -> 4.95 us alone, 5.24 -> 4.72 in
-        // the step); 4 rows per workgroup are within noise alone and lose in the step (fp8 down 9.94 -> 10.53 us).  The chunk ->
-        // (wave, lane) map and every lane's order of accumulation do not depend on R or U: all forms give the same bits (tested)
-        // (w13 image: the rebuild holds more registers per chunk in flight -- down projection, U = 6: 151 VGPRs, 16.9 us; U = 2: 15.0 us)
-        const int u = tune().gemv_splitk_u > 0 ? tune().gemv_splitk_u
-                      : (nchunk <= 256 ? 1 : ((nchunk <= 512 || IsP13<WT>::v) ? 2 : (nchunk <= 1024 ? 4 : (nchunk <= 1536 ? 6 : 2))));
-        const int r = tune().gemv_splitk_r > 0 ? tune().gemv_splitk_r : 2;
-#define TEO_SPK(RR, UU) if (r == RR && u == UU) return launch_splitk<T, TO, WT, RR, UU>(x, W, ws, res, y, N, K, st)
-        TEO_SPK(2, 1); TEO_SPK(2, 3); TEO_SPK(2, 4); TEO_SPK(2, 6);
-        TEO_SPK(4, 1); TEO_SPK(4, 2); TEO_SPK(4, 3); TEO_SPK(4, 4); TEO_SPK(4, 6);
-#undef TEO_SPK
-        return launch_splitk<T, TO, WT, 2, 2>(x, W, ws, res, y, N, K, st);
-    }
-    switch (tune().gemv_variant) {          // tuning sweep (tools/bench_kernels.py): R rows x U chunks, prefetch on/off
-        case 0: return launch_rows<T, TO, WT, 4, 2, false>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-        case 1: return launch_rows<T, TO, WT, 2, 4, false>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-        case 2: return launch_rows<T, TO, WT, 2, 8, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
+static int launch_splitk(const GemvPlan& g, const GemvArgs& a, hipStream_t st) {
+    switch (g.R * 10 + g.U) {                     // R = 2 / 4 rows x U = 1 / 2 / 3 / 4 / 6 chunks: every weight class
+        case 21: return splitk_form<T, TO, WT, 2, 1>(g, a, st);
+        case 22: return splitk_form<T, TO, WT, 2, 2>(g, a, st);
+        case 23: return splitk_form<T, TO, WT, 2, 3>(g, a, st);
+        case 24: return splitk_form<T, TO, WT, 2, 4>(g, a, st);
+        case 26: return splitk_form<T, TO, WT, 2, 6>(g, a, st);
+        case 41: return splitk_form<T, TO, WT, 4, 1>(g, a, st);
+        case 42: return splitk_form<T, TO, WT, 4, 2>(g, a, st);
+        case 43: return splitk_form<T, TO, WT, 4, 3>(g, a, st);
+        case 44: return splitk_form<T, TO, WT, 4, 4>(g, a, st);
+        case 46: return splitk_form<T, TO, WT, 4, 6>(g, a, st);
         default: break;
     }
-    const bool fits = K / Vec16<T>::N <= 2 * GV_THREADS;              // the x prologue fits 2 chunks per thread (stage_x)
-    const bool small_k = fits && (tune().gemv_small_k != 0);
-    if constexpr (IsMx<WT>::v) {
-        // MXFP4 rows are a quarter of bf16's (K = 4096: 128 chunks, 2 KB).  4 rows x 2 chunks = 8 KB per wave per step, the whole row in
-        // one step, as fp8's 2 x 4.  U sets the fp32 order of the image's sums (see below): it stays 2 whatever gemv_small_k says, and
-        // gemv_small_k picks only the prologue.  gemv_variant 10..13 take fp8's geometries (fp32 order).
-        if (small_k) {
-            switch (tune().gemv_variant) {
-                case 10: return launch_rows<T, TO, WT, 2, 4, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-                case 12: return launch_rows<T, TO, WT, 2, 2, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-                case 13: return launch_rows<T, TO, WT, 4, 4, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-                default: return launch_rows<T, TO, WT, 4, 2, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-            }
-        }
-        switch (tune().gemv_variant) {
-            case 10: return launch_rows<T, TO, WT, 2, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-            case 12: return launch_rows<T, TO, WT, 2, 2, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-            case 13: return launch_rows<T, TO, WT, 4, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-            default: return launch_rows<T, TO, WT, 4, 2, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-        }
-    }
-    // >= 4 KiB contiguous per row per step streams ~7 % faster than 2 KiB; first block prefetched under the prologue.
-    // fp8 rows are half as long: 4 rows per wave keep the same bytes in flight per lane
-    if constexpr (sizeof(WT) == 1) {
-        // fp8 rows are half as long.  With the small prologue (61-95 VGPRs) 2 rows x 4 chunks = 8 KB per wave per step wins
-        // (gate/up 16.7 -> 15.3 us, qkv 11.3 -> 10.0, lm_head 23 -> 21.7: at the streaming floor); with the K <= 12288
-        // prologue the registers are the prologue's and 2 x 2 keeps the occupancy
-        if constexpr (IsBf<T>::v) {
-            if (small_k) {
-                switch (tune().gemv_variant) {
-                    case 11: return launch_rows<T, TO, WT, 4, 2, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-                    case 12: return launch_rows<T, TO, WT, 2, 2, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-                    case 13: return launch_rows<T, TO, WT, 4, 4, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-                    default: return launch_rows<T, TO, WT, 2, 4, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-                }
-            }
-        }
-        switch (tune().gemv_variant) {
-            case 10: return launch_rows<T, TO, WT, 2, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-            case 11: return launch_rows<T, TO, WT, 4, 2, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-            case 12: return launch_rows<T, TO, WT, 2, 2, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-            case 13: return launch_rows<T, TO, WT, 4, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-            default: break;
-        }
-        // the bf16 image sums a step's U chunks before adding them to the row (consume_block), so U sets the fp32 order: where the small
-        // prologue would apply but gemv_small_k = 0, keep its 2 x 4 form (the knob picks the prologue, not the order of the sums)
-        if (fits) return launch_rows<T, TO, WT, 2, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-        return launch_rows<T, TO, WT, 2, 2, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-    }
-    if constexpr (IsP13<WT>::v) {
-        // w13 image: the same 2 x 4 geometry (and bits) without the prefetch under the prologue -- the raw block it would hold across
-        // the prologue costs registers the rebuild needs (gate/up 26.1 -> 25.0 us, lm_head 37.9 -> 35.6 with gemv_variant = 1's form)
-        if (small_k) return launch_rows<T, TO, WT, 2, 4, false, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-        return launch_rows<T, TO, WT, 2, 4, false>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
-    }
-    if constexpr (Is16<T>::v) { if (small_k) return launch_rows<T, TO, WT, 2, 4, true, 2>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st); }
-    return launch_rows<T, TO, WT, 2, 4, true>(x, W, ws, norm_w, res, y, N, K, eps, swiglu, st);
+    set_error("gemv: no split-K kernel of %d rows x %d chunks", g.R, g.U);
+    return TEO_ERR_UNSUPPORTED;
 }
 
-// wfmt (ops.h GemvWFmt): the activations' type, fp8 e4m3 with per-row fp32 scales, or MXFP4 with [N][K/32] e8m0 bytes (both: bf16
-// activations only)
+template <typename T, typename TO, typename WT>
+static int gemv_launch(const GemvPlan& g, const GemvArgs& a, hipStream_t st) {
+    return g.kind == GemvKind::SplitK ? launch_splitk<T, TO, WT>(g, a, st) : launch_rows<T, TO, WT>(g, a, st);
+}
+
+// wfmt (gemv_plan.h GemvWFmt): the activations' type, fp8 e4m3 with per-row fp32 scales, or MXFP4 with [N][K/32] e8m0 bytes (both: bf16
+// activations only).  plan_only: check and plan as the launch would, launch nothing (teo_gemv_plan, with placeholder operands)
 int gemv_w(const void* x, const void* W, const void* wscale, int wfmt, const void* norm_w, const void* res, void* y, int N,
-           int K, float eps, unsigned flags, int dtype, int out_dtype, hipStream_t st) {
+           int K, float eps, unsigned flags, int dtype, int out_dtype, hipStream_t st, GemvPlan* plan_only) {
     if (N == 0) return TEO_OK;
     const bool swiglu = flags & TEO_GEMM_SWIGLU16;
     const bool w_fp8 = wfmt == GV_W_FP8, w_mx = wfmt == GV_W_MXFP4, w_p13 = wfmt == GV_W_P13;
@@ -1020,34 +968,24 @@ int gemv_w(const void* x, const void* W, const void* wscale, int wfmt, const voi
     TEO_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (norm_w == nullptr || (reinterpret_cast<uintptr_t>(norm_w) & 15) == 0),
                   "teo_gemv: x / norm_w must be 16-byte aligned");
     if (swiglu) TEO_CHECK_ARG(N % 32 == 0 && !res, "teo_gemv: SWIGLU16 needs N %% 32 == 0 and no residual");
-    if (w_mx) {
-        TEO_CHECK_ARG(dtype == TEO_BF16 && wscale != nullptr, "teo_gemv: MXFP4 weights need bf16 activations and block scales");
-        if (out_dtype == TEO_F32) return gemv_launch<bf16_t, float, fp4x2_t>(x, W, wscale, norm_w, res, y, N, K, eps, swiglu, st);
-        return gemv_launch<bf16_t, bf16_t, fp4x2_t>(x, W, wscale, norm_w, res, y, N, K, eps, swiglu, st);
+    if (w_mx) TEO_CHECK_ARG(dtype == TEO_BF16 && wscale != nullptr, "teo_gemv: MXFP4 weights need bf16 activations and block scales");
+    else if (w_fp8) TEO_CHECK_ARG(dtype == TEO_BF16 && wscale != nullptr, "teo_gemv: fp8 weights need bf16 activations and per-row scales");
+    else if (!w_p13 && dtype == TEO_F32) TEO_CHECK_ARG(out_dtype == TEO_F32, "teo_gemv: f32 inputs need f32 output");
+    else if (!w_p13 && dtype != TEO_BF16 && dtype != TEO_F16) {
+        set_error("teo_gemv: unknown dtype %d", dtype);
+        return TEO_ERR_UNSUPPORTED;
     }
-    if (w_p13) {           // the image's sections start on 256-byte boundaries of the allocation: the 16-byte alignment above is all they need
-        if (out_dtype == TEO_F32) return gemv_launch<bf16_t, float, p13_t>(x, W, nullptr, norm_w, res, y, N, K, eps, swiglu, st);
-        return gemv_launch<bf16_t, bf16_t, p13_t>(x, W, nullptr, norm_w, res, y, N, K, eps, swiglu, st);
-    }
-    if (w_fp8) {
-        TEO_CHECK_ARG(dtype == TEO_BF16 && wscale != nullptr, "teo_gemv: fp8 weights need bf16 activations and per-row scales");
-        if (out_dtype == TEO_F32) return gemv_launch<bf16_t, float, fp8_t>(x, W, wscale, norm_w, res, y, N, K, eps, swiglu, st);
-        return gemv_launch<bf16_t, bf16_t, fp8_t>(x, W, wscale, norm_w, res, y, N, K, eps, swiglu, st);
-    }
-    if (dtype == TEO_F32) {
-        TEO_CHECK_ARG(out_dtype == TEO_F32, "teo_gemv: f32 inputs need f32 output");
-        return gemv_launch<float, float, float>(x, W, nullptr, norm_w, res, y, N, K, eps, swiglu, st);
-    }
-    if (dtype == TEO_BF16) {
-        if (out_dtype == TEO_F32) return gemv_launch<bf16_t, float, bf16_t>(x, W, nullptr, norm_w, res, y, N, K, eps, swiglu, st);
-        return gemv_launch<bf16_t, bf16_t, bf16_t>(x, W, nullptr, norm_w, res, y, N, K, eps, swiglu, st);
-    }
-    if (dtype == TEO_F16) {
-        if (out_dtype == TEO_F32) return gemv_launch<f16_t, float, f16_t>(x, W, nullptr, norm_w, res, y, N, K, eps, swiglu, st);
-        return gemv_launch<f16_t, f16_t, f16_t>(x, W, nullptr, norm_w, res, y, N, K, eps, swiglu, st);
-    }
-    set_error("teo_gemv: unknown dtype %d", dtype);
-    return TEO_ERR_UNSUPPORTED;
+    const GemvPlan g = plan_gemv({N, K, wfmt, dtype, out_dtype, swiglu, norm_w != nullptr, 0, 0, 0}, tune());
+    if (plan_only) { *plan_only = g; return TEO_OK; }
+    // (a w13 image's sections start on 256-byte boundaries of the allocation: the 16-byte alignment above is all they need)
+    const GemvArgs a = {x, W, (w_fp8 || w_mx) ? wscale : nullptr, norm_w, res, y, N, K, eps};
+    const bool of32 = out_dtype == TEO_F32;
+    if (w_mx) return of32 ? gemv_launch<bf16_t, float, fp4x2_t>(g, a, st) : gemv_launch<bf16_t, bf16_t, fp4x2_t>(g, a, st);
+    if (w_p13) return of32 ? gemv_launch<bf16_t, float, p13_t>(g, a, st) : gemv_launch<bf16_t, bf16_t, p13_t>(g, a, st);
+    if (w_fp8) return of32 ? gemv_launch<bf16_t, float, fp8_t>(g, a, st) : gemv_launch<bf16_t, bf16_t, fp8_t>(g, a, st);
+    if (dtype == TEO_F32) return gemv_launch<float, float, float>(g, a, st);
+    if (dtype == TEO_BF16) return of32 ? gemv_launch<bf16_t, float, bf16_t>(g, a, st) : gemv_launch<bf16_t, bf16_t, bf16_t>(g, a, st);
+    return of32 ? gemv_launch<f16_t, float, f16_t>(g, a, st) : gemv_launch<f16_t, f16_t, f16_t>(g, a, st);
 }
 
 int gemv(const void* x, const void* W, const void* norm_w, const void* res, void* y, int N, int K, float eps,
@@ -1055,53 +993,59 @@ int gemv(const void* x, const void* W, const void* norm_w, const void* res, void
     return gemv_w(x, W, nullptr, GV_W_NATIVE, norm_w, res, y, N, K, eps, flags, dtype, out_dtype, st);
 }
 
+struct QkvArgs {
+    const void *x, *W, *ws, *norm_w;
+    void* qout;
+    const float *cs, *sn;
+    const int* d_pos;
+    void *kc, *vc, *vtc;
+    int S_max, H, Hk, hd, K;
+    float eps;
+};
+template <typename T, typename WT, int U, int XPT>
+static int qkv_form(const GemvPlan& g, const QkvArgs& a, hipStream_t st) {
+    with_flags([&](auto nt, auto pf) {
+        TEO_KLAUNCH((gemv_qkv_rope_kernel<T, WT, decltype(nt)::value, decltype(pf)::value, U, XPT>), g.blocks, GV_THREADS, g.lds_bytes, st,
+                    (const WT*)a.W, (const T*)a.x, (const T*)a.norm_w, (const WScaleT<WT>*)a.ws, a.d_pos, a.K, a.H, a.Hk, a.hd, (T*)a.qout, a.cs,
+                    a.sn, (T*)a.kc, (T*)a.vc, (T*)a.vtc, a.S_max, a.eps);
+    }, g.nt, g.prefetch);
+    TEO_LAUNCH_CHECK("gemv_qkv_rope");
+    return TEO_OK;
+}
+template <typename T, typename WT>
+static int launch_qkv(const GemvPlan& g, const QkvArgs& a, hipStream_t st) {
+    // (U chunks, x chunks) per weight class: MXFP4 U = 2; fp8 U = 4, and 2 under the large prologue; the rest U = 4; f32 the large prologue only
+    if constexpr (IsMx<WT>::v) {
+        if (g.U == 2 && g.xpt == 2) return qkv_form<T, WT, 2, 2>(g, a, st);
+        if (g.U == 2 && g.xpt == 6) return qkv_form<T, WT, 2, 6>(g, a, st);
+    } else {
+        if constexpr (Is16<T>::v) { if (g.U == 4 && g.xpt == 2) return qkv_form<T, WT, 4, 2>(g, a, st); }
+        if (g.U == 4 && g.xpt == 6) return qkv_form<T, WT, 4, 6>(g, a, st);
+        if constexpr (sizeof(WT) == 1) { if (g.U == 2 && g.xpt == 6) return qkv_form<T, WT, 2, 6>(g, a, st); }
+    }
+    set_error("gemv_qkv_rope: no kernel of %d chunks per step, %d x chunks for this weight format", g.U, g.xpt);
+    return TEO_ERR_UNSUPPORTED;
+}
+
+// plan_only: as gemv_w's (teo_gemv_qkv_plan)
 int gemv_qkv_rope(const void* x, const void* W, const void* wscale, int wfmt, const void* norm_w, void* qout,
                   const float* cs, const float* sn, const int* d_pos, void* kc, void* vc, void* vtc, int S_max, int H, int Hk,
-                  int hd, int K, float eps, int dtype, hipStream_t st) {
+                  int hd, int K, float eps, int dtype, hipStream_t st, GemvPlan* plan_only) {
     const bool w_fp8 = wfmt == GV_W_FP8, w_mx = wfmt == GV_W_MXFP4, w_p13 = wfmt == GV_W_P13;
     TEO_CHECK_ARG(!w_p13 || dtype == TEO_BF16, "gemv_qkv_rope: a w13 image needs bf16 activations");
     const int ve = w_mx ? 32 : (w_fp8 ? 16 : (dtype == TEO_F32 ? 4 : 8));
     TEO_CHECK_ARG(K % ve == 0 && hd >= 2 && (hd & (hd - 1)) == 0, "gemv_qkv_rope: K=%d hd=%d (head_dim must be a power of two)", K, hd);
     TEO_CHECK_ARG((size_t)(K + 1040) * 4 <= 64 * 1024, "gemv_qkv_rope: K=%d too large for LDS staging", K);
     TEO_CHECK_ARG(!(w_fp8 || w_mx) || (dtype == TEO_BF16 && wscale), "gemv_qkv_rope: fp8 / MXFP4 weights need bf16 activations and scales");
-    const int ngroups = (H + Hk) * (hd / 2) + Hk * hd / 2;
-    int blocks = cdiv(ngroups, GV_WAVES);
-    if (blocks > tune().gemv_max_blocks) blocks = tune().gemv_max_blocks;
-    const size_t lds = w_mx ? xb_lds_bytes<32>(K) : (w_fp8 ? xb_lds_bytes<16>(K) : (dtype == TEO_F32 ? xs_lds_bytes<4>(K) : xs_lds_bytes<8>(K)));
-    // small x prologue (2 register chunks per thread) whenever K allows: fewer VGPRs, more waves per SIMD (see stage_x); fp8 rows then
-    // take 4 chunks per step like the row-group kernel (8 KB per wave in flight)
-    const bool fits = K / (dtype == TEO_F32 ? 4 : 8) <= 2 * GV_THREADS;
-    const bool small_k = (tune().gemv_small_k != 0) && fits;
-    // (fp8: U sets the fp32 order of the bf16 image's sums, see gemv_launch -- it follows what K allows, not gemv_small_k)
-    // (MXFP4: a K = 4096 row is 128 chunks -- 2 chunks per step take it whole; U = 2 at every K keeps one order of the sums)
-    const int uu = w_mx ? 2 : ((w_fp8 && !fits) ? 2 : 4);
-    const bool pf = K / ve >= 64 * uu;
-#define TEO_QR2(TT, WW, NTV, XP, UU)                                                                                      \
-    if (pf) TEO_KLAUNCH((gemv_qkv_rope_kernel<TT, WW, NTV, true, UU, XP>), blocks, GV_THREADS, lds, st, (const WW*)W, (const TT*)x, (const TT*)norm_w, \
-                                                                       (const WScaleT<WW>*)wscale, \
-                                                                       d_pos, K, H, Hk, hd, (TT*)qout, cs, sn, (TT*)kc, (TT*)vc, (TT*)vtc, \
-                                                                       S_max, eps);                                          \
-    else TEO_KLAUNCH((gemv_qkv_rope_kernel<TT, WW, NTV, false, UU, XP>), blocks, GV_THREADS, lds, st, (const WW*)W, (const TT*)x, (const TT*)norm_w, \
-                                                                       (const WScaleT<WW>*)wscale, \
-                                                                       d_pos, K, H, Hk, hd, (TT*)qout, cs, sn, (TT*)kc, (TT*)vc, (TT*)vtc, \
-                                                                       S_max, eps)
-#define TEO_QR(TT, WW, NTV) if (small_k) { TEO_QR2(TT, WW, NTV, 2, 4); } else { TEO_QR2(TT, WW, NTV, 6, 4); }
-#define TEO_QR6(TT, WW, NTV) TEO_QR2(TT, WW, NTV, 6, 4)
-#define TEO_QR8(TT, WW, NTV) if (small_k) { TEO_QR2(TT, WW, NTV, 2, 4); } else if (fits) { TEO_QR2(TT, WW, NTV, 6, 4); } else { TEO_QR2(TT, WW, NTV, 6, 2); }
-#define TEO_QR4(TT, WW, NTV) if (small_k) { TEO_QR2(TT, WW, NTV, 2, 2); } else { TEO_QR2(TT, WW, NTV, 6, 2); }
-    if (w_mx)                  { if (tune().gemv_nt) { TEO_QR4(bf16_t, fp4x2_t, true); } else { TEO_QR4(bf16_t, fp4x2_t, false); } }
-    else if (w_fp8)                 { if (tune().gemv_nt) { TEO_QR8(bf16_t, fp8_t, true); } else { TEO_QR8(bf16_t, fp8_t, false); } }
-    else if (w_p13)            { if (tune().gemv_nt) { TEO_QR(bf16_t, p13_t, true); } else { TEO_QR(bf16_t, p13_t, false); } }
-    else if (dtype == TEO_F32) { if (tune().gemv_nt) { TEO_QR6(float, float, true); } else { TEO_QR6(float, float, false); } }
-    else if (dtype == TEO_F16) { if (tune().gemv_nt) { TEO_QR(f16_t, f16_t, true); } else { TEO_QR(f16_t, f16_t, false); } }
-    else                       { if (tune().gemv_nt) { TEO_QR(bf16_t, bf16_t, true); } else { TEO_QR(bf16_t, bf16_t, false); } }
-#undef TEO_QR
-#undef TEO_QR6
-#undef TEO_QR8
-#undef TEO_QR4
-#undef TEO_QR2
-    TEO_LAUNCH_CHECK("gemv_qkv_rope");
-    return TEO_OK;
+    const GemvPlan g = plan_gemv_qkv({(H + 2 * Hk) * hd, K, wfmt, dtype, dtype, false, norm_w != nullptr, H, Hk, hd}, tune());
+    if (plan_only) { *plan_only = g; return TEO_OK; }
+    const QkvArgs a = {x, W, wscale, norm_w, qout, cs, sn, d_pos, kc, vc, vtc, S_max, H, Hk, hd, K, eps};
+    if (w_mx) return launch_qkv<bf16_t, fp4x2_t>(g, a, st);
+    if (w_fp8) return launch_qkv<bf16_t, fp8_t>(g, a, st);
+    if (w_p13) return launch_qkv<bf16_t, p13_t>(g, a, st);
+    if (dtype == TEO_F32) return launch_qkv<float, float>(g, a, st);
+    if (dtype == TEO_F16) return launch_qkv<f16_t, f16_t>(g, a, st);
+    return launch_qkv<bf16_t, bf16_t>(g, a, st);
 }
 
 }  // namespace teo

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "gemm_plan.h"
+#include "gemv_plan.h"
 
 struct teo_graph {
     hipGraph_t graph;
@@ -131,15 +132,13 @@ int gemm_w4a8(const void* A8, const float* a_scale, const void* W4, const void* 
               int ldc, unsigned flags, int out_dtype, hipStream_t st);
 int quant_rows_fp8(const void* x, const void* norm_w, void* q, float* s, int M, int K, int ldx, float eps, hipStream_t st);
 int gemm_sk_workspace_init(void* ws, hipStream_t st);
-// decode GEMV weight formats: the activations' own type, fp8 e4m3 + one fp32 scale per row, MXFP4 (e2m1 codes + one e8m0 byte per
-// 32-element block along K, [N][K/32]); a w13 image of a bf16 matrix (p13.h: W is the image, no scales).  All but the first take bf16
-// activations
-enum GemvWFmt { GV_W_NATIVE = 0, GV_W_FP8 = 1, GV_W_MXFP4 = 2, GV_W_P13 = 3 };
+// decode GEMVs (wfmt: gemv_plan.h GemvWFmt).  plan_only: run the argument checks and the planner as the launch would, store the plan
+// and launch nothing -- teo_gemv_plan / teo_gemv_qkv_plan call with placeholder operands (any aligned non-null address)
 int gemv_qkv_rope(const void* x, const void* W, const void* wscale, int wfmt, const void* norm_w, void* qout,
                   const float* cs, const float* sn, const int* d_pos, void* kc, void* vc, void* vtc, int S_max, int H, int Hk,
-                  int hd, int K, float eps, int dtype, hipStream_t st);
+                  int hd, int K, float eps, int dtype, hipStream_t st, GemvPlan* plan_only = nullptr);
 int gemv_w(const void* x, const void* W, const void* wscale, int wfmt, const void* norm_w, const void* res, void* y, int N,
-           int K, float eps, unsigned flags, int dtype, int out_dtype, hipStream_t st);
+           int K, float eps, unsigned flags, int dtype, int out_dtype, hipStream_t st, GemvPlan* plan_only = nullptr);
 
 inline size_t esize(int dtype) { return dtype == TEO_F32 ? 4 : 2; }
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }

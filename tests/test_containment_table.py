@@ -35,6 +35,8 @@ TABLE = {
     "teo_gemm_fp8_plan": reason("host only: the planner's choice as a string, launches nothing"),
     "teo_gemm_w4_plan": reason("host only: the planner's choice as a string, launches nothing"),
     "teo_gemm_w4a8_plan": reason("host only: the planner's choice as a string, launches nothing"),
+    "teo_gemv_plan": reason("host only: the planner's choice as a string, launches nothing"),
+    "teo_gemv_qkv_plan": reason("host only: the planner's choice as a string, launches nothing"),
     "teo_sizeof": HOST_ONLY,
     "teo_tune_create": reason("host only: a knob block in host memory"),
     "teo_tune_destroy": reason("host only: a knob block in host memory"),

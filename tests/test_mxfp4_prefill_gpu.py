@@ -4,6 +4,7 @@ Every MXFP4 weight is exactly a bfloat16 number, the kernel converts each code e
 k-ascending MFMA chain and the epilogue of the bf16 tile families.  So everything here is BITWISE: teo_gemm_w4 against teo_gemm_ws on the
 dequantised matrix, an `mxfp4_only` engine against an mxfp4 engine with the options off (the parent's prefill).  No tolerance anywhere."""
 import ctypes as C
+import gc
 import random
 import time
 
@@ -194,7 +195,11 @@ def _build_pair(sd, cfg, max_seq):
     # The figures are the allocator's REQUESTED bytes (torch.cuda.memory_stats "requested_bytes.all.*": what the tensors asked for).
     # "allocated_bytes" counts whole blocks, and a tensor cut from a cached block carries up to 1 MiB of that block's slack, which depends
     # on what earlier tests left in the cache: as much as the bound's whole allowance.  Requested bytes do not depend on that history.
+    # Nor may they depend on WHEN Python's cycle collector next runs: engines of earlier modules are cyclic garbage (engine <-> its option
+    # hooks) that still holds device tensors, and a collection in the middle of a construction below would be booked as memory that engine
+    # gave back.  So collect before every reading.
     def requested(key="current"):
+        gc.collect()
         torch.cuda.synchronize()
         return torch.cuda.memory_stats()["requested_bytes.all." + key]
     base = requested()

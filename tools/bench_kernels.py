@@ -32,6 +32,11 @@ def timeit(fn, iters=20, warm=3):
     return e0.elapsed_time(e1) / iters * 1e3   # us
 
 
+def gemv_plan(N, K, norm, flags, wfmt=0):
+    """the dispatch of the call being timed (teo_gemv_plan under this thread's knobs; bf16 activations and output as the sweeps use)"""
+    return L.load().teo_gemv_plan(N, K, wfmt, flags, int(bool(norm)), L.TEO_BF16, L.TEO_BF16).decode()
+
+
 def bench_gemv():
     shapes = [("qkv", 12288, 4096, True, 0), ("o", 4096, 4096, False, 0), ("gateup", 22016, 4096, True, L.GEMM_SWIGLU16),
               ("down", 4096, 11008, False, 0), ("lm_head", 32000, 4096, True, 0)]
@@ -48,7 +53,7 @@ def bench_gemv():
         L.check(SHIM.teo_bench_gemv_chain(x.data_ptr(), pp, None, n, nw.data_ptr() if norm else None, y.data_ptr(), N, K, 1e-5,
                                         flags, L.TEO_BF16, 10, C.byref(avg), G.stream()), "chain")
         us = avg.value * 1e3
-        print(f"gemv {name:8s} N={N:6d} K={K:6d}: {us:7.2f} us  {N * K * 2 / us / 1e3:7.1f} GB/s", flush=True)
+        print(f"gemv {name:8s} N={N:6d} K={K:6d}: {us:7.2f} us  {N * K * 2 / us / 1e3:7.1f} GB/s  [{gemv_plan(N, K, norm, flags)}]", flush=True)
         del Ws
 
 
@@ -167,7 +172,7 @@ def bench_gemv_fp8():
         L.check(SHIM.teo_bench_gemv_chain(x.data_ptr(), pp, pp2, n, nw.data_ptr() if norm else None, y.data_ptr(), N, K, 1e-5,
                                         flags, L.TEO_BF16, 10, C.byref(avg), G.stream()), "chain")
         us = avg.value * 1e3
-        print(f"gemv fp8 {name:8s} N={N:6d} K={K:6d}: {us:7.2f} us  {N * K / us / 1e3:7.1f} GB/s", flush=True)
+        print(f"gemv fp8 {name:8s} N={N:6d} K={K:6d}: {us:7.2f} us  {N * K / us / 1e3:7.1f} GB/s  [{gemv_plan(N, K, norm, flags, wfmt=1)}]", flush=True)
         del Ws
 
 
@@ -199,6 +204,8 @@ def bench_gemv_sweep():
                     tot += us
                     line += f"  {name} {us:6.1f}us {N * K * 2 / us / 1e3:6.0f}GB/s"
                 print(line + f"  | layer {tot:6.1f}us", flush=True)
+                for name, N, K, norm, flags in shapes:
+                    print(f"    {name}: [{gemv_plan(N, K, norm, flags)}]", flush=True)
     L.tune_set(b"gemv_variant", -1)
 
 
