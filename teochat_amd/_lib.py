@@ -232,6 +232,14 @@ ABI_VERSION = 4            # TEO_ABI_VERSION of include/teo_hip.h this binding w
 
 
 EXPORTS = tuple(_SIGS.keys())
+
+# include/teo_hip_prefix.h: prefix reuse for the stream decoder, a second header of the same library (bound beside the first table)
+_SIGS_PREFIX = {
+    "teo_llama_prefill_slots_past": (C.c_int, [C.POINTER(LlamaDesc), C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                               C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "teo_kv_fork": (C.c_int, [C.POINTER(LlamaDesc), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_longlong, C.c_void_p]),
+}
+EXPORTS_PREFIX = tuple(_SIGS_PREFIX.keys())
 _lib = None
 
 
@@ -252,7 +260,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:
         raise TeoLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_PREFIX.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

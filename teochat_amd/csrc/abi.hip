@@ -62,7 +62,8 @@ int llama_prefill(const teo_llama_desc* d, const void* embeds, const int* positi
                   float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, void* attentions);
 int llama_prefill_batch(const teo_llama_desc* d, const void* embeds, const int* seq_lens, int nseq, long long cache_stride,
                         int last_only, float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states,
-                        const int* slots = nullptr);
+                        const int* slots = nullptr, const int* pasts = nullptr);
+int llama_prefill_check_weights(const teo_llama_desc* d);
 size_t llama_decode_workspace_bytes(const teo_llama_desc* d);
 int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st);
 int llama_decode_step_profile(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, float* ms_out, int* count_out,
@@ -890,3 +891,6 @@ int teo_gemm_skinny_w4(const void* x, const void* W4, const void* e8m0, const vo
 }
 
 }  // extern "C"
+
+// the prefill entry points of the second header (include/teo_hip_prefix.h, prefix.hip) run the same weight checks
+int teo::llama_prefill_check_weights(const teo_llama_desc* d) { return check_prefill_weights(d); }

@@ -321,8 +321,11 @@ int llama_prefill(const teo_llama_desc* d, const void* embeds, const int* positi
 // elements, fresh caches: past = 0).  logits [nseq, vocab]: last position of every sequence.
 // slots != NULL (teo_llama_prefill_slots): sequence i goes into cache slot slots[i] instead of slot i -- the refill pass of the stream
 // decoder, every slot freed in a round in one pass over the weights.
+// pasts != NULL (teo_llama_prefill_slots_past, include/teo_hip_prefix.h): sequence i's rows are appended at positions pasts[i] .. behind
+// what its slot already holds (RoPE, KV rows and kv_len as llama_prefill's `past`); the entry point has checked the bounds.
 int llama_prefill_batch(const teo_llama_desc* d, const void* embeds, const int* seq_lens, int nseq, long long cache_stride,
-                        int last_only, float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, const int* slots) {
+                        int last_only, float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, const int* slots,
+                        const int* pasts) {
     int total = 0;
     for (int b = 0; b < nseq; ++b) {
         TEO_CHECK_ARG(seq_lens[b] >= 1 && seq_lens[b] <= d->max_seq, "teo_llama_prefill_batch: seq_lens[%d] = %d", b, seq_lens[b]);
@@ -351,10 +354,11 @@ int llama_prefill_batch(const teo_llama_desc* d, const void* embeds, const int* 
             const int Sb = seq_lens[b];
             unsigned char* qkv_b = (unsigned char*)w.qkv + (size_t)row0 * QKV * e;
             const size_t slot = slots ? (size_t)slots[b] : (size_t)b;
+            const int past = pasts ? pasts[b] : 0;
             unsigned char* kc = (unsigned char*)d->k_cache[l] + slot * cache_stride * e;
             unsigned char* vc = (unsigned char*)d->v_cache[l] + slot * cache_stride * e;
             unsigned char* vtc = (unsigned char*)d->vt_cache[l] + slot * cache_stride * e;
-            TEO_TRY(rope_kv_append(qkv_b, QKV, nullptr, d->rope_cos, d->rope_sin, kc, vc, vtc, Sb, 0, nullptr, d->max_seq, H, Hk,
+            TEO_TRY(rope_kv_append(qkv_b, QKV, nullptr, d->rope_cos, d->rope_sin, kc, vc, vtc, Sb, past, nullptr, d->max_seq, H, Hk,
                                    hd, dt, st));
             teo_attn_args a;
             memset(&a, 0, sizeof(a));
@@ -364,7 +368,7 @@ int llama_prefill_batch(const teo_llama_desc* d, const void* embeds, const int* 
             a.v_bs = 0; a.v_hs = (long long)d->max_seq * hd; a.v_rs = hd;
             a.vt_bs = 0; a.vt_hs = (long long)hd * d->max_seq; a.vt_rs = d->max_seq;
             a.o_bs = 0; a.o_rs = (long long)H * hd;
-            a.batch = 1; a.heads = H; a.kv_heads = Hk; a.head_dim = hd; a.q_len = Sb; a.kv_len = Sb;
+            a.batch = 1; a.heads = H; a.kv_heads = Hk; a.head_dim = hd; a.q_len = Sb; a.kv_len = past + Sb;
             a.causal = 1;
             a.scale = 1.0f / sqrtf((float)hd);
             TEO_TRY(attention(&a, dt, st));

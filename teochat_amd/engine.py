@@ -742,6 +742,7 @@ class TeoEngine:
     # ------------------------------------------------------------------ LLaMA
     def reset_cache(self):
         self.cache_len = 0
+        self.cache_epoch = getattr(self, "cache_epoch", 0) + 1     # what generate(prefix_key=) remembers about the cache no longer holds
 
     def prefill(self, embeds, positions=None, last_only=False, hidden_states=False, attentions=False):
         """embeds [S, D] appended to the cache; returns fp32 logits [S, V] (or [1, V]).  With hidden_states: (logits, hs) where hs is
@@ -778,6 +779,7 @@ class TeoEngine:
             self._check_handoffs("prefill", lambda f: self.lib.teo_llama_prefill_workspace_status(C.byref(self.llama_desc), S, _p(ws), ws.numel(),
                                                                                                   C.byref(f), sid), "teo_llama_prefill")
         self.cache_len = past + S
+        self.cache_epoch = getattr(self, "cache_epoch", 0) + 1
         if attentions:
             return (logits, hs, att) if hidden_states else (logits, att)
         return (logits, hs) if hidden_states else logits

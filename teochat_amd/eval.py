@@ -53,12 +53,13 @@ def output_path(dataset_name, model_path, out_name=None, out_dir=None, prompt_st
 def eval(dataset_name, model_path, model_base, load_8bit=False, load_4bit=False, cache_dir=None, data_cache_dir=None,
          out_name=None, out_dir=None, prompt_strategy=None, chronological_prefix=True, conv_mode="v1", device="cuda",
          force_rerun=False, temperature=0.2, max_new_tokens=256, dataset=None, model_bundle=None, batch_size=1,
-         continuous=False):
+         continuous=False, prefix_cache=False):
     """Run (or re-use) the model's answers on one TEOChatlas evaluation split and print / return its task metrics.
     Extra keywords (not in the reference): `dataset` = examples to use instead of the hub download, `model_bundle` =
     (tokenizer, model, processor) already loaded, `batch_size` = examples answered per generation (1 = the reference's loop;
     up to 16 share every weight read of a decode step, inference.run_inference_batch), `continuous` = the whole split through one
-    generate_stream over batch_size conversation slots that are refilled as answers finish (off: groups of batch_size examples)."""
+    generate_stream over batch_size conversation slots that are refilled as answers finish (off: groups of batch_size examples),
+    `prefix_cache` (with continuous) = examples about the same image sequence share its prefill (inference.run_inference_batch)."""
     print("Arguments passed to eval:")
     for k, v in (("dataset_name", dataset_name), ("model_path", model_path), ("model_base", model_base), ("out_name", out_name),
                  ("out_dir", out_dir), ("prompt_strategy", prompt_strategy), ("chronological_prefix", chronological_prefix),
@@ -85,7 +86,7 @@ def eval(dataset_name, model_path, model_base, load_8bit=False, load_4bit=False,
                                    trust_remote_code=True)
         outputs = run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronological_prefix, conv_mode,
                                 temperature, max_new_tokens, **({"batch_size": batch_size} if batch_size != 1 else {}),
-                                **({"continuous": True} if continuous else {}))
+                                **({"continuous": True} if continuous else {}), **({"prefix_cache": True} if prefix_cache else {}))
         print(f"Saving outputs to {out_path}")
         with open(out_path, "w") as f:
             json.dump(outputs, f, indent=4)
@@ -125,6 +126,8 @@ _CLI = (
     # not in the reference: continuous batching over batch_size slots (teochat_amd/stream.py).  Absent from the parsed arguments unless
     # given (eval()'s default, off, holds): the parsed defaults stay the reference's flags + batch_size
     ("continuous", dict(action="store_true", default=argparse.SUPPRESS)),
+    # not in the reference: with --continuous, examples with the same image paths share the prefill up to their last <image>
+    ("prefix_cache", dict(action="store_true", default=argparse.SUPPRESS)),
 )
 
 

@@ -60,7 +60,7 @@ def run_inference_single(model, processor, tokenizer, inp, image_paths, conv_mod
 
 def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, conv_mode="v1", timestamps_list=None,
                         prompt_strategy="interleave", chronological_prefix=True, temperature=0.2, max_new_tokens=256,
-                        do_sample=True, continuous=False, slots=None):
+                        do_sample=True, continuous=False, slots=None, prefix_cache=False):
     """run_inference_single for up to 16 examples at once (not in the reference, whose loop is one example at a time,
     inference.py:100-113): the same prompt construction, frame order, tokenisation and stop keyword per example, then ONE
     batched generation -- every frame of every example through the tower together, one prefill per example, and a decode loop
@@ -72,11 +72,17 @@ def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, con
     `slots` (default min(number of examples, 16)) conversation slots -- a slot whose answer has finished is refilled with the next
     example instead of idling until the longest answer of its group ends.  The same prompts, frames and stop keywords, each
     prepared when its example is admitted to a slot (inps, image_paths_list and timestamps_list may be lazy sequences); greedy
-    answers equal the static path's, sampled ones draw from per-EXAMPLE Philox streams."""
+    answers equal the static path's, sampled ones draw from per-EXAMPLE Philox streams.
+
+    prefix_cache=True (with continuous=True only): examples about the same image sequence share its prefill -- generate_stream's
+    prefix_keys, the key being the tuple of the example's image paths after the timestamp sort (paths that are not strings: no key).
+    An example that starts from another one's rows neither opens nor preprocesses its images."""
     B = len(inps)
+    if prefix_cache and not continuous:
+        raise ValueError("prefix_cache needs continuous=True (prefix reuse lives in the stream decoder's slots)")
     if continuous:
         return _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, conv_mode, timestamps_list, prompt_strategy,
-                                     chronological_prefix, temperature, max_new_tokens, do_sample, slots)
+                                     chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache)
     if timestamps_list is None:
         timestamps_list = [[] for _ in range(B)]
     if len(image_paths_list) != B or len(timestamps_list) != B:
@@ -101,10 +107,11 @@ def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, con
 
 class _Prepared:
     """Example i's (input ids, frames, criteria), built when first asked for; the last `keep` examples are kept, so that the ids, the
-    frames and the criteria of one example come from one preparation while no more than a lookahead of them is held."""
+    frames and the criteria of one example come from one preparation while no more than a lookahead of them is held.  A column in `lazy`
+    holds a function until it is indexed for the first time (the frames: an example that reuses a prefix never opens its images)."""
 
-    def __init__(self, prepare, n, keep):
-        self.prepare, self.n, self.keep, self.cache = prepare, n, keep, {}
+    def __init__(self, prepare, n, keep, lazy=()):
+        self.prepare, self.n, self.keep, self.cache, self.lazy = prepare, n, keep, {}, tuple(lazy)
 
     def get(self, i):
         if i not in self.cache:
@@ -121,12 +128,15 @@ class _Prepared:
                 return outer.n
 
             def __getitem__(self, i):
-                return outer.get(i)[k]
+                row = outer.get(i)
+                if k in outer.lazy and callable(row[k]):
+                    row[k] = row[k]()
+                return row[k]
         return Column()
 
 
 def _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, conv_mode, timestamps_list, prompt_strategy,
-                          chronological_prefix, temperature, max_new_tokens, do_sample, slots):
+                          chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache=False):
     N = len(inps)
     if N == 0:
         return []
@@ -135,23 +145,39 @@ def _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, c
     slots = min(N, 16) if slots is None else int(slots)
     n_prompt = {}
 
-    def prepare(i):
+    def sorted_paths(i):
         image_paths = image_paths_list[i]
         timestamps = timestamps_list[i] if timestamps_list is not None else []
         if len(timestamps) > 0:
             order = sorted(range(len(image_paths)), key=lambda k: datetime.strptime(timestamps[k], "%Y-%m-%d"))
             image_paths = [image_paths[k] for k in order]
-        frames = [processor.preprocess(p, return_tensors="pt")["pixel_values"][0] for p in image_paths]
-        frames = [f.to(model.device, dtype=model.dtype) for f in frames]
+        return image_paths
+
+    def prepare(i):
+        image_paths = sorted_paths(i)
+
+        def frames():
+            return [processor.preprocess(p, return_tensors="pt")["pixel_values"][0].to(model.device, dtype=model.dtype) for p in image_paths]
         prompt, stop_str = build_prompt(inps[i], image_paths, conv_mode, prompt_strategy, chronological_prefix)
         input_ids = tokenizer_image_token(prompt, tokenizer, IMAGE_TOKEN_INDEX, return_tensors="pt").unsqueeze(0).to(model.device)
         n_prompt[i] = input_ids.shape[1]
-        return input_ids[0], frames, [KeywordsStoppingCriteria([stop_str], tokenizer, input_ids)]
+        return [input_ids[0], frames, [KeywordsStoppingCriteria([stop_str], tokenizer, input_ids)]]
 
-    prepared = _Prepared(prepare, N, 2 * slots)
+    class Keys:
+        """the prefix key of example i: its image paths after the timestamp sort (None when a path is not a string)"""
+
+        def __len__(self):
+            return N
+
+        def __getitem__(self, i):
+            paths = list(sorted_paths(i))
+            return tuple(paths) if paths and all(isinstance(p, str) for p in paths) else None
+
+    prepared = _Prepared(prepare, N, 2 * slots, lazy=(1,))
     with torch.inference_mode():
         outs = model.generate_stream(prepared.column(0), prepared.column(1), slots=slots, do_sample=do_sample, temperature=temperature,
-                                     max_new_tokens=max_new_tokens, stopping_criteria=prepared.column(2))
+                                     max_new_tokens=max_new_tokens, stopping_criteria=prepared.column(2),
+                                     **({"prefix_keys": Keys()} if prefix_cache else {}))
     return [tokenizer.decode(o[n_prompt[i]:]).replace("</s>", "").strip() for i, o in enumerate(outs)]
 
 
@@ -182,15 +208,19 @@ def _record(example, response, dataset):
 
 
 def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronological_prefix, conv_mode, temperature,
-                  max_new_tokens, batch_size=1, continuous=False):
+                  max_new_tokens, batch_size=1, continuous=False, prefix_cache=False):
     """Dataset loop with the bookkeeping the metrics need (inference.py:88-137): response / ground truth / task per example,
     the example's polygon when it has one, and the integer boxes quoted in the question and in the reference answer.
     batch_size (extra trailing keyword, default 1 = the reference's loop): answer that many consecutive examples per
     generation (run_inference_batch, <= 16); the records come out in dataset order either way.
     continuous=True (extra trailing keyword, default off): the whole dataset goes through ONE generate_stream over batch_size
-    conversation slots (run_inference_batch(continuous=True)); examples are read and prepared as slots free up."""
+    conversation slots (run_inference_batch(continuous=True)); examples are read and prepared as slots free up.
+    prefix_cache=True (with continuous=True): examples with the same image paths share the prefill of everything up to their last
+    <image> (run_inference_batch(prefix_cache=True)); the records are the same."""
     if not 1 <= int(batch_size) <= 16:
         raise ValueError(f"batch_size {batch_size}: 1..16 examples per generation")
+    if prefix_cache and not continuous:
+        raise ValueError("prefix_cache needs continuous=True")
     outputs = []
     if continuous:
         n = len(dataset)
@@ -207,7 +237,8 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
         responses = run_inference_batch(model, processor, tokenizer, Field(lambda e: e["conversations"][0]["value"]),
                                         Field(lambda e: e["video"]), conv_mode=conv_mode, timestamps_list=Field(lambda e: e["timestamp"]),
                                         prompt_strategy=prompt_strategy, chronological_prefix=chronological_prefix, temperature=temperature,
-                                        max_new_tokens=max_new_tokens, continuous=True, slots=int(batch_size))
+                                        max_new_tokens=max_new_tokens, continuous=True, slots=int(batch_size),
+                                        **({"prefix_cache": True} if prefix_cache else {}))
         return [_record(dataset[i], r, dataset) for i, r in enumerate(responses)]
     if batch_size == 1:
         for example in dataset:

@@ -506,7 +506,7 @@ class LlavaLlamaForCausalLM:
 
     def _generate(self, input_ids=None, images=None, do_sample=None, temperature=None, top_k=None, top_p=None,
                   max_new_tokens=20, use_cache=True, stopping_criteria=None, eos_token_id="config", attention_mask=None,
-                  generator=None, chunk=16, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, **kwargs):
+                  generator=None, chunk=16, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, prefix_key=None, **kwargs):
         """Greedy or sampled (temperature / top-k, device sampler) decoding of ONE sequence; the loop is device-resident
         and replayed from a hipGraph.
 
@@ -516,6 +516,13 @@ class LlavaLlamaForCausalLM:
         through the batched step's kernels.  `last_generation_stats` holds {steps, proposed, accepted, emitted} afterwards: the DEVICE's
         totals -- when a host-side criterion (several stop candidates, a custom StoppingCriteria) ends the call inside a chunk of replays
         they include the steps and tokens the device ran behind that token.  Any other generate() call sets it to None.  0 or None: off.
+
+        prefix_key=k (a hashable; one conversation, not with prompt_lookup_num_tokens): the multi-turn form of prefix reuse.  The model
+        remembers the key, the ids and the rows per id of what the engine cache holds after this call; the next generate(prefix_key=k)
+        whose ids extend it -- everything up to the last <image>, within the rows the PREFILL wrote (rows appended by decode steps
+        carry other kernels' bits), at least one id left -- prefills only the rest behind those rows and skips the tower (`images` is
+        not read).  Equal keys promise equal frames.  Any other generate() call, and anything that resets or prefills the engine
+        cache, forgets the record.  `last_generation_stats` = {prefix_rows_reused, prefill_rows} afterwards.
 
         Returns int64 [1, n_prompt + n_generated]; the prompt part still contains the -200 sentinels, as with the
         reference (eval/inference.py:75 slices at input_ids.shape[1]).  `eos_token_id=None` disables EOS stopping.
@@ -528,6 +535,9 @@ class LlavaLlamaForCausalLM:
         top_p = getattr(gc, "top_p", 1.0) if top_p is None else top_p
         self.last_generation_stats = None
         K = int(prompt_lookup_num_tokens or 0)
+        if K and prefix_key is not None:
+            raise ValueError("prefix_key is not combined with prompt_lookup_num_tokens")
+        record, self._prefix_record = getattr(self, "_prefix_record", None), None          # any generate() call forgets it
         if K and not 1 <= K <= 15:
             raise ValueError(f"prompt_lookup_num_tokens {K} outside 1..15")
         if K and input_ids.shape[0] != 1:
@@ -559,10 +569,26 @@ class LlavaLlamaForCausalLM:
         if max_new_tokens <= 0:
             return input_ids
         # ---- prefill
-        (_, pos, mask, _, embeds, _) = self.prepare_inputs_labels_for_multimodal(input_ids, None, attention_mask, None,
-                                                                               None, images)
-        if embeds is None:
-            embeds = self.get_model().embed_tokens(input_ids)
+        ids_t, reuse = tuple(input_ids[0].tolist()), (0, 0)
+        plain_mask = attention_mask is None or bool(attention_mask.to(torch.bool).all())
+        if prefix_key is not None and record is not None and plain_mask and record[0] == prefix_key and record[4] == getattr(eng, "cache_epoch", 0):
+            from .stream import reusable_prefix
+            reuse = reusable_prefix(ids_t, record[:4], 1)
+            if reuse[0] != len(record[1]):          # the next turn EXTENDS the remembered prompt; anything else takes the full path
+                reuse = (0, 0)
+        if reuse[1]:
+            embeds = self.get_model().embed_tokens(input_ids[:, reuse[0]:])       # text ids only: no tower, `images` is not read
+            row_map = tuple(record[2][:reuse[0]]) + (1,) * (len(ids_t) - reuse[0])
+        else:
+            (_, pos, mask, _, embeds, _) = self.prepare_inputs_labels_for_multimodal(input_ids, None, attention_mask, None,
+                                                                                   None, images)
+            if embeds is None:
+                embeds = self.get_model().embed_tokens(input_ids)
+            n_img = sum(1 for t in ids_t if t < 0)
+            nv = (int(embeds.shape[1]) - (len(ids_t) - n_img)) // n_img if n_img else 0
+            row_map = tuple(nv if t < 0 else 1 for t in ids_t)
+            if not plain_mask or sum(row_map) != int(embeds.shape[1]):
+                row_map = None                      # rows cut by a mask or by tokenizer_model_max_length: nothing to remember
         spec = None
         if K:
             # one verify step writes K + 1 cache rows from the pending token's position on, whatever it accepts
@@ -574,10 +600,17 @@ class LlavaLlamaForCausalLM:
             spec.reset()
             logits = spec.prefill(embeds[0], last_only=True)
         else:
-            eng.reset_cache()
-            if embeds.shape[1] + max_new_tokens > eng.max_seq:
-                raise ValueError(f"prompt ({embeds.shape[1]}) + max_new_tokens ({max_new_tokens}) exceeds max_seq {eng.max_seq}")
+            if reuse[1] + embeds.shape[1] + max_new_tokens > eng.max_seq:
+                raise ValueError(f"prompt ({reuse[1] + embeds.shape[1]}) + max_new_tokens ({max_new_tokens}) exceeds max_seq {eng.max_seq}")
+            if reuse[1]:
+                eng.cache_len = reuse[1]            # the rows the last generate(prefix_key=) prefilled stay; the rest follows behind them
+            else:
+                eng.reset_cache()
             logits = eng.prefill(embeds[0], last_only=True)
+            if prefix_key is not None:
+                self.last_generation_stats = dict(prefix_rows_reused=reuse[1], prefill_rows=int(embeds.shape[1]))
+                if row_map is not None:             # (key, ids, rows per id, rows written by prefill, the cache's epoch)
+                    self._prefix_record = (prefix_key, ids_t, row_map, eng.cache_len, eng.cache_epoch)
         if do_sample:
             tp = 1.0 if top_p is None else float(top_p)
             k = int(top_k or 0)                    # 0 = top-k filter off (HF: top_k=0 / None disables TopKLogitsWarper)
@@ -781,7 +814,8 @@ class LlavaLlamaForCausalLM:
             return self._generate_stream(*args, **kwargs)
 
     def _generate_stream(self, input_ids_list, images_list=None, slots=8, max_new_tokens=20, do_sample=False, temperature=None,
-                         top_k=None, top_p=None, stopping_criteria=None, eos_token_id="config", generator=None, chunk=16):
+                         top_k=None, top_p=None, stopping_criteria=None, eos_token_id="config", generator=None, chunk=16, prefix_keys=None,
+                         min_prefix_rows=64):
         """Answer N requests (any N >= 1) over `slots` <= 16 conversation slots of the batched decode step: a slot whose request has
         finished parks -- the attention kernels skip it -- and is refilled with the next request, so a step's work follows the requests
         that are still being answered instead of the longest answer of a fixed group (teochat_amd/stream.py).
@@ -794,7 +828,17 @@ class LlavaLlamaForCausalLM:
         slots, chunk or the slot the request landed in.  The device stop is armed while every admitted request's stop candidates
         (keyword id lists and EOS, folded as generate() folds them) are one and the same id sequence; otherwise the host applies the
         criteria once per chunk, at the exact token.  `last_generation_stats` = {requests, steps, live_slot_steps, slot_steps,
-        prefill_passes} afterwards."""
+        prefill_passes} afterwards.
+
+        prefix_keys: one hashable or None per request (any sequence with len() and []) turns prefix reuse on.  Equal keys are the
+        caller's promise that the requests' frames are the same; None never shares.  A request whose ids extend what a slot with its
+        key already holds -- everything up to and including the last <image>, at least min_prefix_rows embedding rows -- is a HIT: the
+        slot's KV rows are copied (teo_kv_fork; not even that when the holder itself is free), only the embeddings of the remaining ids
+        are prefilled behind them (teo_llama_prefill_slots_past), the tower does not run and images_list[i] IS NOT READ for it.  Every
+        slot keeps a private, complete cache, so the decode step is untouched.  The stats gain prefix_hits, prefix_rows_reused, forks,
+        fork_rows, frames_skipped and prefill_rows.  In fp32 the answers are those without keys; in the 16-bit types a prompt prefilled
+        in two pieces is not bit for bit the prompt prefilled in one (the suffix's GEMMs and RoPE take the kernels of a short prefill), so
+        answers may differ from the keyless run's the way two orderings of a sum differ (prefix reuse)."""
         from .stream import request_seed, run_stream
         N = len(input_ids_list)
         slots = int(slots)
@@ -835,16 +879,17 @@ class LlavaLlamaForCausalLM:
                     uniq.append(ids)
             return uniq
 
-        def admit(reqs, slot_list):
-            B = len(reqs)
+        def register(reqs, with_frames):
+            """ids / criteria / the device stop of the requests being admitted; the ids rows and the flat frame list of `with_frames`"""
             rows, flat = [], []
             for r in reqs:
                 ids_of[r] = input_ids_list[r].view(-1)
                 crits_of[r] = list(stopping_criteria[r]) if stopping_criteria is not None else []
-                rows.append(ids_of[r])
-                imgs = images_list[r] if images_list is not None else None
-                if imgs is not None:
-                    flat.extend(list(imgs))
+                if r in with_frames:
+                    rows.append(ids_of[r])
+                    imgs = images_list[r] if images_list is not None else None
+                    if imgs is not None:
+                        flat.extend(list(imgs))
                 uniq = stop_candidates(r)
                 if not dev_stop["off"]:
                     if len(uniq) == 1 and dev_stop["ids"] in (None, uniq[0]):
@@ -852,7 +897,11 @@ class LlavaLlamaForCausalLM:
                     else:
                         dev_stop["off"] = True
             dec.configure(None if dev_stop["off"] else dev_stop["ids"], do_sample=do_sample, temperature=temperature, top_k=k, top_p=tp)
-            # one multimodal preparation for the round, as generate_batch() does it for a group
+            return rows, flat
+
+        def embed_rows(reqs, rows, flat):
+            """one multimodal preparation for the round, as generate_batch() does it for a group: the embedded rows per request"""
+            B = len(reqs)
             dev_ids = rows[0].device
             width = max(int(ids.numel()) for ids in rows)
             ids_p = torch.zeros(B, width, dtype=torch.long, device=dev_ids)
@@ -866,17 +915,51 @@ class LlavaLlamaForCausalLM:
             seqs = []
             for b, r in enumerate(reqs):
                 on = torch.nonzero(new_mask[b].to(torch.bool), as_tuple=False).flatten()
-                lo, hi = int(on[0]), int(on[-1]) + 1
-                if max_new[r] > 0 and hi - lo + max_new[r] > eng.max_seq:
-                    raise ValueError(f"request {r}: prompt ({hi - lo}) + max_new_tokens ({max_new[r]}) exceeds max_seq {eng.max_seq}")
-                seqs.append(embeds[b, lo:hi])
-            logits = dec.refill(slot_list, seqs)
+                seqs.append(embeds[b, int(on[0]):int(on[-1]) + 1])
+            return seqs
+
+        def first_tokens(reqs, logits, lens):
             out = []
             for b, r in enumerate(reqs):
                 seed = request_seed(base_seed, r)
                 first = eng.sample(logits[b], temperature, k, seed, 0, top_p=tp) if do_sample else self._argmax(logits[b])
-                out.append((first, min(max_new[r] - 1, eng.max_seq - int(seqs[b].shape[0])), seed))
+                out.append((first, min(max_new[r] - 1, eng.max_seq - lens[b]), seed))
             return out
+
+        def admit_past(items):
+            """a round's pass with prefix reuse (teochat_amd/stream.py run_stream): items [(request, slot, p ids, P rows)]"""
+            reqs = [it[0] for it in items]
+            misses = [it[0] for it in items if it[3] == 0]
+            rows, flat = register(reqs, set(misses))
+            full = dict(zip(misses, embed_rows(misses, rows, flat))) if misses else {}
+            seqs, lens, maps = [], [], []
+            for r, slot, p, P in items:
+                ids = ids_of[r]
+                if P:
+                    seq = self.get_model().embed_tokens(ids[p:].view(1, -1))[0]          # text ids only (rule c): no tower, no frames
+                    maps.append(None)
+                else:
+                    seq = full[r]
+                    n_img = int((ids < 0).sum())
+                    nv = (int(seq.shape[0]) - (int(ids.numel()) - n_img)) // n_img if n_img else 0
+                    per = [nv if t < 0 else 1 for t in ids.tolist()]
+                    maps.append(per if sum(per) == int(seq.shape[0]) else None)           # None: cut by tokenizer_model_max_length, not shared
+                n = P + int(seq.shape[0])
+                if n + max_new[r] > eng.max_seq:
+                    raise ValueError(f"request {r}: prompt ({n}) + max_new_tokens ({max_new[r]}) exceeds max_seq {eng.max_seq}")
+                seqs.append(seq)
+                lens.append(n)
+            logits = dec.refill_past([it[1] for it in items], seqs, [it[3] for it in items])
+            return [f + (maps[b], int(seqs[b].shape[0])) for b, f in enumerate(first_tokens(reqs, logits, lens))]
+
+        def admit(reqs, slot_list):
+            rows, flat = register(reqs, set(reqs))
+            seqs = embed_rows(reqs, rows, flat)
+            lens = [int(q.shape[0]) for q in seqs]
+            for r, n in zip(reqs, lens):
+                if max_new[r] > 0 and n + max_new[r] > eng.max_seq:
+                    raise ValueError(f"request {r}: prompt ({n}) + max_new_tokens ({max_new[r]}) exceeds max_seq {eng.max_seq}")
+            return first_tokens(reqs, dec.refill(slot_list, seqs), lens)
 
         def host_done(r, toks):
             if eos_token_id is not None and toks[-1] == eos_token_id:
@@ -887,8 +970,18 @@ class LlavaLlamaForCausalLM:
             return False
 
         todo = [r for r in range(N) if max_new[r] > 0]
-        results, stats = run_stream(dec, len(todo), slots, lambda reqs, sl: admit([todo[i] for i in reqs], sl),
-                                    lambda i, toks: host_done(todo[i], toks), chunk=chunk) if todo else ([], None)
+        if prefix_keys is not None and len(prefix_keys) != N:
+            raise ValueError("prefix_keys must hold one key (or None) per request")
+        if not todo:
+            results, stats = [], None
+        elif prefix_keys is None:
+            results, stats = run_stream(dec, len(todo), slots, lambda reqs, sl: admit([todo[i] for i in reqs], sl),
+                                        lambda i, toks: host_done(todo[i], toks), chunk=chunk)
+        else:
+            results, stats = run_stream(dec, len(todo), slots, None, lambda i, toks: host_done(todo[i], toks), chunk=chunk,
+                                        keys=[prefix_keys[r] for r in todo], ids_of=lambda i: input_ids_list[todo[i]].view(-1).tolist(),
+                                        admit_past=lambda items: admit_past([(todo[i], s, p, P) for i, s, p, P in items]),
+                                        min_prefix_rows=min_prefix_rows)
         outs = []
         new_of = {todo[i]: toks for i, toks in enumerate(results)}
         for r in range(N):

@@ -87,6 +87,7 @@ class StreamDecoder:
         self.live = [False] * self.B             # armed and not yet seen parked by poll() / parked by park()
         self.pos = [-1] * self.B                 # host mirror of d_pos / d_out_count as of the last poll
         self.count = [0] * self.B
+        self.held = [None] * self.B              # per slot: None or (key, prompt ids, embedded rows per id, rows written by PREFILL)
         self._stats = dict(steps=0, slot_steps=0, live_slot_steps=0, prefill_passes=0, arms=0)
 
     def configure(self, stop_ids=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0):
@@ -153,9 +154,64 @@ class StreamDecoder:
                                 "teo_llama_prefill_slots")
         for s, n_ in zip(slot_list, lens):
             bd.cache_len[s] = n_
+            self.held[s] = None                  # what the slot held is overwritten; the scheduler records what it holds now
         bd._armed = False
         self._stats["prefill_passes"] += 1
         return logits
+
+    def refill_past(self, slot_list, embeds_list, pasts, last_only=True):
+        """refill() behind a past per slot: embeds_list[i] ([S_i, D]) is appended to cache slot slot_list[i] at positions pasts[i] ..
+        pasts[i] + S_i - 1, rows [0, pasts[i]) being what the slot holds (its own earlier prefill or a fork()): ONE pass over the weights
+        (teo_llama_prefill_slots_past, include/teo_hip_prefix.h).  Returns the fp32 last-position logits [len(slot_list), V]."""
+        eng, bd = self.eng, self.bd
+        slot_list, pasts = [int(s) for s in slot_list], [int(p) for p in pasts]
+        if not (len(slot_list) == len(embeds_list) == len(pasts)) or not slot_list:
+            raise ValueError("refill_past: one sequence and one past per slot, at least one")
+        if len(set(slot_list)) != len(slot_list) or min(slot_list) < 0 or max(slot_list) >= self.B:
+            raise ValueError(f"refill_past: slots {slot_list} are not distinct numbers in 0..{self.B - 1}")
+        if any(self.live[s] for s in slot_list):
+            raise ValueError(f"refill_past: slot(s) {[s for s in slot_list if self.live[s]]} are live")
+        lens = [int(e.shape[0]) for e in embeds_list]
+        if min(lens) < 1 or min(pasts) < 0 or max(p + n_ for p, n_ in zip(pasts, lens)) > eng.max_seq:
+            raise ValueError(f"pasts {pasts} + sequence lengths {lens} outside 1..max_seq {eng.max_seq}")
+        total, n = sum(lens), len(lens)
+        with eng.phase() as st:
+            rows = torch.cat([e.to(device=eng.device, dtype=eng.dtype) for e in embeds_list], dim=0).contiguous()
+            logits = torch.empty(n if last_only else total, eng.cfg.vocab_size, dtype=torch.float32, device=eng.device)
+            eng._flush_handoff_checks("prefill")
+            d0 = bd.slot_desc[0]
+            ws = eng._workspace("prefill", self.lib.teo_llama_prefill_workspace_bytes(C.byref(d0), total))
+            L.check(self.lib.teo_llama_prefill_slots_past(C.byref(d0), _p(rows), (C.c_int * n)(*lens), (C.c_int * n)(*pasts),
+                                                          (C.c_int * n)(*slot_list), n, bd.k_cache.stride(1), 1 if last_only else 0, _p(logits),
+                                                          _p(ws), ws.numel(), st, None), "teo_llama_prefill_slots_past")
+            sid = C.c_void_p(eng.stream.cuda_stream)
+            eng._check_handoffs("prefill", lambda f: self.lib.teo_llama_prefill_workspace_status(C.byref(d0), total, _p(ws), ws.numel(), C.byref(f), sid),
+                                "teo_llama_prefill_slots_past")
+        for s, p, n_ in zip(slot_list, pasts, lens):
+            bd.cache_len[s] = p + n_
+            self.held[s] = None
+        bd._armed = False
+        self._stats["prefill_passes"] += 1
+        return logits
+
+    def fork(self, src, dst_list, rows):
+        """Copy the first `rows` cache positions of slot `src` into every slot of dst_list (teo_kv_fork, on the engine stream).  src may be
+        live or parked -- a live slot only ever appends at or behind its prompt rows -- and must hold a record whose prefill-written rows
+        cover `rows`; no destination may be live.  The destinations' records are dropped: the scheduler writes the new ones."""
+        bd = self.bd
+        src, rows, dst_list = int(src), int(rows), [int(s) for s in dst_list]
+        if not dst_list or len(set(dst_list)) != len(dst_list) or src in dst_list or min(dst_list + [src]) < 0 or max(dst_list + [src]) >= self.B:
+            raise ValueError(f"fork: source {src} and destinations {dst_list} are not distinct slots in 0..{self.B - 1}")
+        if any(self.live[s] for s in dst_list):
+            raise ValueError(f"fork: destination slot(s) {[s for s in dst_list if self.live[s]]} are live")
+        if self.held[src] is None or not 1 <= rows <= self.held[src][3]:
+            raise ValueError(f"fork: slot {src} holds no record that covers {rows} prefill-written rows")
+        n = len(dst_list)
+        with self.eng.phase() as st:
+            L.check(self.lib.teo_kv_fork(C.byref(bd.desc), src, (C.c_int * n)(*dst_list), n, rows, bd.k_cache.stride(1), st), "teo_kv_fork")
+        for s in dst_list:
+            self.held[s] = None
+        self._stats["forks"] = self._stats.get("forks", 0) + n
 
     def arm(self, slot, first_token, seed=0, limit=1, draws_done=1):
         """Make `slot` live: its next step takes first_token at position cache length; it parks itself after `limit` steps (or on the
@@ -254,26 +310,159 @@ class StreamDecoder:
             pass
 
 
-def run_stream(dec, n_requests, slots, admit, host_done, chunk=16):
+def reusable_prefix(ids, record, min_prefix_rows=64):
+    """How much of a holder's cache a request may start from: (ids, embedding rows) of the longest common id prefix of `ids` and the
+    holder's `record` (key, prompt ids, embedded rows per id, rows written by prefill), cut so that
+      (a) at least one id is left to prefill (the last row's logits are needed),
+      (b) it ends no later than the rows the holder's PREFILL wrote (rows appended by decode steps carry other kernels' bits),
+      (c) every image sentinel (negative id) of the request lies inside it,
+    and at least max(min_prefix_rows, 1) rows long; (0, 0) otherwise: a miss."""
+    _, hid, hrows, written = record
+    n = min(len(ids) - 1, len(hid))
+    p = 0
+    while p < n and ids[p] == hid[p]:
+        p += 1
+    P = sum(hrows[:p])
+    while p > 0 and P > written:
+        p -= 1
+        P -= hrows[p]
+    if p < 1 or P < max(int(min_prefix_rows), 1) or any(t < 0 for t in ids[p:]):
+        return 0, 0
+    return p, P
+
+
+def _choose_slot(avail, held, upcoming):
+    """The victim of a refill: the lowest free slot whose held key is not wanted by `upcoming` (keys of the next requests), else the
+    lowest free slot."""
+    wanted = {k for k in upcoming if k is not None}
+    for s in avail:
+        if held[s] is None or held[s][0] not in wanted:
+            return s
+    return avail[0]
+
+
+def _admit_prefix(dec, reqs, free, queue, slots, keys, ids_of, admit_past, min_prefix_rows, stats):
+    """One round of admissions with prefix reuse.  Returns [(request, slot, first token, limit, seed)] in request order.  On the one
+    engine stream: slot choice; every fork from a holder that existed before the round (nothing is overwritten yet); ONE refill_past
+    pass (misses from position 0 after the tower ran over THEIR frames, hits behind their P reused rows); then, when misses of this round
+    are holders for later requests of the round, the forks from them and ONE more pass for those followers."""
+    ids = {r: tuple(int(t) for t in ids_of(r)) for r in reqs}
+    key = {r: keys[r] for r in reqs}
+    before = {s: rec for s, rec in enumerate(dec.held) if rec is not None}
+    plan, leaders = {}, {}                        # request -> [kind, source slot, p ids, P rows]; key -> the round's first miss with it
+    for r in reqs:
+        best = None
+        if key[r] is not None:
+            for s, rec in before.items():
+                if rec[0] == key[r]:
+                    p, P = reusable_prefix(ids[r], rec, min_prefix_rows)
+                    # the longest prefix; among equals a free holder (no copy), then the lowest slot
+                    if P and (best is None or (P, s in free) > (best[2], best[0] in free)):
+                        best = (s, p, P)
+        if best is not None:
+            plan[r] = ["hit", best[0], best[1], best[2]]
+        elif key[r] is not None and key[r] in leaders:
+            plan[r] = ["follow", leaders[key[r]], 0, 0]
+        else:
+            plan[r] = ["miss", None, 0, 0]
+            if key[r] is not None:
+                leaders[key[r]] = r
+    # ---- 1. slots: a hit whose holder is itself free stays in place; the others take victims, in request order
+    avail, slot_of = list(free), {}
+    for r in reqs:
+        if plan[r][0] == "hit" and plan[r][1] in avail:
+            slot_of[r] = plan[r][1]
+            avail.remove(plan[r][1])
+    later = [keys[q] for q in list(queue)[:2 * int(slots)]]
+    for i, r in enumerate(reqs):
+        if r not in slot_of:
+            s = _choose_slot(avail, dec.held, ([key[q] for q in reqs[i + 1:]] + later)[:2 * int(slots)])
+            slot_of[r] = s
+            avail.remove(s)
+
+    def forks(group):
+        by = {}
+        for r in group:
+            if plan[r][1] != slot_of[r]:
+                by.setdefault((plan[r][1], plan[r][3]), []).append(slot_of[r])
+        for (src, rows), dst in sorted(by.items()):
+            dec.fork(src, dst, rows)
+            stats["forks"] += len(dst)
+            stats["fork_rows"] += rows * len(dst)
+
+    def one_pass(group):
+        holder = {r: dec.held[plan[r][1]] for r in group if plan[r][0] == "hit"}     # (read before the pass drops the records)
+        got = admit_past([(r, slot_of[r], plan[r][2], plan[r][3]) for r in group])
+        stats["prefill_passes"] += 1
+        for r, (tok, limit, seed, rows_per_id, n_rows) in zip(group, got):
+            stats["prefill_rows"] += int(n_rows)
+            if plan[r][0] == "hit":
+                p, P = plan[r][2], plan[r][3]
+                stats["prefix_hits"] += 1
+                stats["prefix_rows_reused"] += P
+                stats["frames_skipped"] += sum(1 for t in ids[r] if t < 0)
+                rows_per_id = tuple(holder[r][2][:p]) + (1,) * (len(ids[r]) - p)
+            if key[r] is not None and rows_per_id is not None:
+                dec.held[slot_of[r]] = (key[r], ids[r], tuple(int(x) for x in rows_per_id), int(sum(rows_per_id)))
+            else:
+                dec.held[slot_of[r]] = None
+            first[r] = (tok, limit, seed)
+
+    first = {}
+    # ---- 2. forks from the holders of before the round, 3. one pass: misses and hits
+    now = [r for r in reqs if plan[r][0] != "follow"]
+    forks([r for r in now if plan[r][0] == "hit"])
+    one_pass(now)
+    # ---- 4. followers of this round's misses: forks from them, one more pass
+    rest = [r for r in reqs if plan[r][0] == "follow"]
+    if rest:
+        for r in rest:
+            src = slot_of[plan[r][1]]
+            rec = dec.held[src]
+            p, P = reusable_prefix(ids[r], rec, min_prefix_rows) if rec is not None else (0, 0)
+            plan[r] = ["hit", src, p, P] if P else ["miss", None, 0, 0]
+        forks([r for r in rest if plan[r][0] == "hit"])
+        one_pass(rest)
+    return [(r, slot_of[r]) + tuple(first[r]) for r in reqs]
+
+
+def run_stream(dec, n_requests, slots, admit, host_done, chunk=16, *, keys=None, ids_of=None, admit_past=None, min_prefix_rows=64):
     """The scheduler.  dec: refill / arm / steps / poll / tokens / park as StreamDecoder has them.
       admit(reqs, slot_list) -> per request (first_token, limit, seed): runs the tower over the requests' frames in one call, ONE
                                 dec.refill(slot_list, ...) pass and picks the first tokens; limit = steps the slot may run (<= 0: none)
       host_done(req, tokens) -> True when the host criteria stop request `req` at the last of `tokens`
     Requests are taken in order; one that is finished at its first token is completed on the spot and its slot stays free.  Returns
-    (tokens per request, stats)."""
+    (tokens per request, stats).
+
+    Prefix reuse (keys given; `admit` is not called then): keys[r] is a hashable or None -- equal keys promise equal frames, None never
+    shares -- and a request whose ids extend what a slot with its key holds (dec.held, reusable_prefix) starts from that slot's rows:
+      ids_of(req)        -> the request's prompt ids (negative = an image sentinel)
+      admit_past(items)  -> items [(req, slot, p, P)]: P = 0 a miss (the whole prompt, frames through the tower), else a hit whose first p
+                            ids = P rows are in the slot already (embed ids[p:] only, no frames).  ONE dec.refill_past pass; returns per
+                            item (first_token, limit, seed, embedded rows per id or None, rows prefilled)
+    dec additionally has held / refill_past / fork.  A round is at most two passes over the weights (_admit_prefix).  The stats gain
+    prefix_hits, prefix_rows_reused, forks, fork_rows, frames_skipped and prefill_rows."""
     queue = deque(range(int(n_requests)))
     free = list(range(int(slots)))
     live = {}                                     # slot -> [request, tokens, limit]
     results = [None] * int(n_requests)
     stats = dict(requests=int(n_requests), steps=0, live_slot_steps=0, slot_steps=0, prefill_passes=0)
+    if keys is not None:
+        if len(keys) != int(n_requests) or ids_of is None or admit_past is None:
+            raise ValueError("run_stream: keys needs one entry per request, ids_of and admit_past")
+        stats.update(prefix_hits=0, prefix_rows_reused=0, forks=0, fork_rows=0, frames_skipped=0, prefill_rows=0)
     while queue or live:
         while queue and free:
             take = min(len(queue), len(free))
             reqs = [queue.popleft() for _ in range(take)]
-            sl = free[:take]
-            firsts = admit(reqs, sl)
-            stats["prefill_passes"] += 1
-            for r, s, (tok, limit, seed) in zip(reqs, sl, firsts):
+            if keys is None:
+                sl = free[:take]
+                firsts = admit(reqs, sl)
+                stats["prefill_passes"] += 1
+                admitted = [(r, s) + tuple(f) for r, s, f in zip(reqs, sl, firsts)]
+            else:
+                admitted = _admit_prefix(dec, reqs, free, queue, slots, keys, ids_of, admit_past, min_prefix_rows, stats)
+            for r, s, tok, limit, seed in admitted:
                 toks = [int(tok)]
                 if limit <= 0 or host_done(r, toks):
                     results[r] = toks             # finished at its first token: never armed
