@@ -240,6 +240,15 @@ _SIGS_PREFIX = {
     "teo_kv_fork": (C.c_int, [C.POINTER(LlamaDesc), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_longlong, C.c_void_p]),
 }
 EXPORTS_PREFIX = tuple(_SIGS_PREFIX.keys())
+
+# include/teo_hip_score.h: scoring answer options as packed branches of one cached prompt, a third header of the same library
+_SIGS_SCORE = {
+    "teo_attn_branches": (C.c_int, [C.POINTER(AttnArgs), C.c_void_p, C.c_int, C.c_void_p]),
+    "teo_llama_prefill_branches": (C.c_int, [C.POINTER(LlamaDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_void_p]),
+    "teo_token_logprobs": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+}
+EXPORTS_SCORE = tuple(_SIGS_SCORE.keys())
 _lib = None
 
 
@@ -260,7 +269,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:
         raise TeoLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_PREFIX.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_PREFIX.items()) + list(_SIGS_SCORE.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

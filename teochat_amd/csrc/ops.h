@@ -23,6 +23,9 @@ int gemm(const void* A, const void* W, const void* bias, const void* res, void* 
 
 int attention(const teo_attn_args* a, int dtype, hipStream_t st);
 int attention_flash32(const teo_attn_args& a, hipStream_t st, bool f16 = false);
+bool attn_mfma_ok(const teo_attn_args& a, int dtype);                                    // attention()'s rule for the MFMA flash kernel
+// branches.hip (the score header's teo_attn_branches): causal attention of packed branches over one shared cached prefix
+int attn_branches(const teo_attn_args* a, const int* d_branch_start, int dtype, hipStream_t st);
 int attention_probs(const teo_attn_args* a, int dtype, void* probs, hipStream_t st);      // the softmax maps themselves (`output_attentions`)
 size_t attn_decode_ws_bytes(int heads, int hd, int S_max, int batch = 1);
 struct AttnBatch {          // per-conversation strides (elements) of a batched decode step; {1, 0, 0, 0} = one conversation

@@ -247,8 +247,10 @@ static int snapshot_rows(void* hs, int idx, const void* src, int S, int D, size_
 }
 
 // attentions (optional, `output_attentions` of the kept forward signature, llava_llama.py:65,95): [layers][heads][S][past + S] in the model dtype
-int llama_prefill(const teo_llama_desc* d, const void* embeds, const int* positions, int S, int past, int last_only,
-                  float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, void* attentions) {
+// branch_start (optional, include/teo_hip_score.h): the S rows are packed branches of the cached prefix -- the attention is attn_branches
+static int llama_prefill_rows(const teo_llama_desc* d, const void* embeds, const int* positions, int S, int past, int last_only,
+                              float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, void* attentions,
+                              const int* branch_start) {
     if (S == 0) return TEO_OK;
     TEO_CHECK_ARG(past + S <= d->max_seq, "teo_llama_prefill: past %d + S %d exceeds max_seq %d", past, S, d->max_seq);
     const PrefillWs w = prefill_carve(d, S, ws, ws_bytes);
@@ -283,7 +285,7 @@ int llama_prefill(const teo_llama_desc* d, const void* embeds, const int* positi
         a.scale = 1.0f / sqrtf((float)hd);
         if (attentions)      // the maps of this layer, from the operands the attention kernel is about to read (rotated q, cached k)
             TEO_TRY(attention_probs(&a, dt, (unsigned char*)attentions + (size_t)l * H * S * (size_t)(past + S) * e, st));
-        return attention(&a, dt, st);
+        return branch_start ? attn_branches(&a, branch_start, dt, st) : attention(&a, dt, st);
         };
         if (fp8) {
             TEO_TRY(prefill_layer_fp8(d, w, l, S, attend, st));
@@ -313,6 +315,16 @@ int llama_prefill(const teo_llama_desc* d, const void* embeds, const int* positi
     TEO_TRY(rmsnorm(w.h, d->final_norm_w, w.n, S, D, d->eps, dt, st));
     TEO_TRY(snapshot_rows(hidden_states, d->layers, w.n, S, D, e, st));
     return gemm(w.n, d->lm_head, nullptr, nullptr, logits, S, d->vocab, D, D, d->vocab, TEO_ACT_NONE, 0, dt, TEO_F32, st, w.sk);
+}
+
+int llama_prefill(const teo_llama_desc* d, const void* embeds, const int* positions, int S, int past, int last_only,
+                  float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, void* attentions) {
+    return llama_prefill_rows(d, embeds, positions, S, past, last_only, logits, ws, ws_bytes, st, hidden_states, attentions, nullptr);
+}
+
+int llama_prefill_branches(const teo_llama_desc* d, const void* embeds, const int* positions, const int* branch_start, int S, int past,
+                           float* logits, void* ws, size_t ws_bytes, hipStream_t st) {
+    return llama_prefill_rows(d, embeds, positions, S, past, 0, logits, ws, ws_bytes, st, nullptr, nullptr, branch_start);
 }
 
 // Multi-sequence prefill (batched generate): the rows of nseq new conversations are concatenated so the norms and the

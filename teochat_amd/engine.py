@@ -784,6 +784,51 @@ class TeoEngine:
             return (logits, hs, att) if hidden_states else (logits, att)
         return (logits, hs) if hidden_states else logits
 
+    def prefill_branches(self, embeds, positions, branch_start):
+        """embeds [S, D]: the packed rows of many continuations ("branches") of the cached prompt, scored in ONE pass over the weights
+        (teo_llama_prefill_branches, include/teo_hip_score.h).  branch_start[i] = first row of row i's branch, positions[i] =
+        cache_len + i - branch_start[i] (score.plan_branches builds both).  Returns fp32 logits [S, V] of every row.  cache_len stays
+        where it was: cache rows [cache_len, cache_len + S) are scratch afterwards."""
+        S = embeds.shape[0]
+        past = self.cache_len
+        if S < 1 or past + S > self.max_seq:
+            raise ValueError(f"{S} branch rows behind {past} cached rows: need 1 <= rows and at most the engine's max_seq {self.max_seq}")
+        if len(positions) != S or len(branch_start) != S:
+            raise ValueError(f"positions ({len(positions)}) and branch_start ({len(branch_start)}) must name all {S} rows")
+        with self.phase() as st:
+            e = embeds.to(device=self.device, dtype=self.dtype).contiguous()
+            pos = torch.as_tensor(positions).to(device=self.device, dtype=torch.int32).contiguous()
+            bs = torch.as_tensor(branch_start).to(device=self.device, dtype=torch.int32).contiguous()
+            logits = torch.empty(S, self.cfg.vocab_size, dtype=torch.float32, device=self.device)
+            need = self.lib.teo_llama_prefill_workspace_bytes(C.byref(self.llama_desc), S)
+            self._flush_handoff_checks("prefill")
+            ws = self._workspace("prefill", need)
+            L.check(self.lib.teo_llama_prefill_branches(C.byref(self.llama_desc), _p(e), _p(pos), _p(bs), S, past, _p(logits), _p(ws), ws.numel(),
+                                                        st), "teo_llama_prefill_branches")
+            sid = C.c_void_p(self.stream.cuda_stream)
+            self._check_handoffs("prefill", lambda f: self.lib.teo_llama_prefill_workspace_status(C.byref(self.llama_desc), S, _p(ws), ws.numel(),
+                                                                                                  C.byref(f), sid), "teo_llama_prefill_branches")
+        self.cache_epoch = getattr(self, "cache_epoch", 0) + 1
+        return logits
+
+    def token_logprobs(self, logits, rows, labels):
+        """fp32 [n]: log softmax(logits[rows[k]])[labels[k]] (teo_token_logprobs: the row loss of teo_cross_entropy, negated).
+        logits: fp32 [R, V] on the device (rows may be a view with a padded row stride)."""
+        n = len(rows)
+        V = logits.shape[1]
+        if len(labels) != n:
+            raise ValueError(f"{n} rows, {len(labels)} labels")
+        if logits.dtype != torch.float32 or logits.stride(1) != 1:
+            raise ValueError("token_logprobs: fp32 logits with contiguous rows")
+        if n and (min(rows) < 0 or max(rows) >= logits.shape[0] or min(labels) < 0 or max(labels) >= V):
+            raise ValueError(f"token_logprobs: rows outside 0..{logits.shape[0] - 1} or labels outside 0..{V - 1}")
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        with self.phase() as st:
+            r = torch.as_tensor(list(rows), dtype=torch.int32).to(self.device)
+            lab = torch.as_tensor(list(labels), dtype=torch.int64).to(self.device)
+            L.check(self.lib.teo_token_logprobs(_p(logits), logits.stride(0), _p(r), _p(lab), _p(out), n, V, st), "teo_token_logprobs")
+        return out
+
     def prefill_batch(self, embeds_list, hidden_states=False):
         """Training-shape forward of B independent sequences in ONE pass (teo_llama_prefill_batch, last_only = 0): embeds_list[b]
         is [S_b, D]; the rows are concatenated for the norms / GEMMs, RoPE + causal attention run per sequence on scratch KV slots

@@ -58,6 +58,40 @@ def run_inference_single(model, processor, tokenizer, inp, image_paths, conv_mod
     return tokenizer.decode(output_ids[0, input_ids.shape[1]:]).replace("</s>", "").strip()
 
 
+def option_token_ids(tokenizer, option):
+    """The ids an answer option is scored on: the tokenizer's ids without the leading BOS, followed by EOS -- the reference's answer
+    followed by `</s>`, so that "Airport" is not favoured over "Airport Hangar" for being its prefix."""
+    ids = [int(t) for t in tokenizer(option).input_ids]
+    bos = getattr(tokenizer, "bos_token_id", None)
+    if ids and bos is not None and ids[0] == bos:
+        ids = ids[1:]
+    return ids + [int(tokenizer.eos_token_id)]
+
+
+def run_inference_options(model, processor, tokenizer, inp, image_paths, options, conv_mode="v1", timestamps=[],
+                          prompt_strategy="interleave", chronological_prefix=True, normalize=False):
+    """Closed-set answer: scores log p(option + </s> | frames, question) of every option (model.score_options: all options in one
+    pass over the weights) and returns (best option, fp32 scores [N] on the CPU).  The prompt is run_inference_single's.
+    normalize=True divides every score by its option's token count before the argmax (the returned scores are the divided ones)."""
+    options = list(options)
+    if not options:
+        raise ValueError("run_inference_options: no options")
+    if len(timestamps) > 0:
+        order = sorted(range(len(image_paths)), key=lambda i: datetime.strptime(timestamps[i], "%Y-%m-%d"))
+        image_paths = [image_paths[i] for i in order]
+        timestamps = [timestamps[i] for i in order]
+    frames = [processor.preprocess(p, return_tensors="pt")["pixel_values"][0] for p in image_paths]
+    frames = [f.to(model.device, dtype=model.dtype) for f in frames]
+    prompt, _ = build_prompt(inp, image_paths, conv_mode, prompt_strategy, chronological_prefix)
+    input_ids = tokenizer_image_token(prompt, tokenizer, IMAGE_TOKEN_INDEX, return_tensors="pt").unsqueeze(0).to(model.device)
+    option_ids = [option_token_ids(tokenizer, o) for o in options]
+    with torch.inference_mode():
+        scores = model.score_options(input_ids, frames, option_ids).detach().float().cpu()
+    if normalize:
+        scores = scores / torch.tensor([float(len(ids)) for ids in option_ids])
+    return options[int(scores.argmax())], scores
+
+
 def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, conv_mode="v1", timestamps_list=None,
                         prompt_strategy="interleave", chronological_prefix=True, temperature=0.2, max_new_tokens=256,
                         do_sample=True, continuous=False, slots=None, prefix_cache=False):

@@ -678,6 +678,55 @@ class LlavaLlamaForCausalLM:
                 break
         return self._finish(input_ids, new_tokens)
 
+    # --- closed-set answers: log p(option | frames, question) of every option, the options packed into one pass over the weights
+    @torch.no_grad()
+    def score_options(self, input_ids, images, options, attention_mask=None, max_rows=1024):
+        """fp32 [N] on the model device: for each option (a list of token ids) the sum over its tokens of the natural-log probability
+        given the prompt and the option's earlier tokens.  One conversation.  Tower, projector, splice and the prompt's prefill run as in
+        generate(); then the options' rows are scored as packed branches of the cached prompt (score.plan_branches,
+        teo_llama_prefill_branches): one pass over the weights per `max_rows` rows instead of one per option.  The token log-probs come
+        from teo_token_logprobs in fp32; the per-option sum is taken in fp64 on the host.  Forgets the prefix_key record like any
+        generate() call; `last_generation_stats` = {prompt_rows, branch_rows, passes} afterwards."""
+        from .score import PROMPT_ROW, plan_branches
+        if input_ids.dim() != 2 or input_ids.shape[0] != 1:
+            raise ValueError("score_options applies to one conversation (input_ids [1, n])")
+        option_ids = [[int(t) for t in (o.tolist() if hasattr(o, "tolist") else o)] for o in options]
+        V = self.engine.cfg.vocab_size
+        for c, ids in enumerate(option_ids):
+            if not ids or min(ids) < 0 or max(ids) >= V:
+                raise ValueError(f"score_options: option {c} is empty or holds ids outside 0..{V - 1}")
+        self.last_generation_stats = None
+        self._prefix_record = None
+        eng = self.engine
+        with eng.phase():
+            (_, pos, mask, _, embeds, _) = self.prepare_inputs_labels_for_multimodal(input_ids, None, attention_mask, None, None, images)
+            if embeds is None:
+                embeds = self.get_model().embed_tokens(input_ids)
+            P = int(embeds.shape[1])
+            if option_ids and P + 1 > eng.max_seq:
+                raise ValueError(f"prompt ({P}) leaves no room behind it in max_seq {eng.max_seq}")
+            passes = plan_branches(option_ids, P, eng.max_seq, max_rows) if option_ids else []
+            eng.reset_cache()
+            prompt_logits = eng.prefill(embeds[0], last_only=True)
+            totals = [0.0] * len(option_ids)
+            branch_rows = 0
+            for p in passes:
+                S = len(p["rows"])
+                branch_rows += S
+                firsts = [t for t in p["triples"] if t[0] == PROMPT_ROW]
+                rest = [t for t in p["triples"] if t[0] != PROMPT_ROW]
+                lp = eng.token_logprobs(prompt_logits, [0] * len(firsts), [t[1] for t in firsts]).tolist()
+                for t, v in zip(firsts, lp):
+                    totals[t[2]] += v
+                if S:
+                    rows = self.get_model().embed_tokens(torch.tensor(p["rows"], dtype=torch.long, device=input_ids.device).view(1, -1))[0]
+                    logits = eng.prefill_branches(rows, p["positions"], p["branch_start"])
+                    lp = eng.token_logprobs(logits, [t[0] for t in rest], [t[1] for t in rest]).tolist()
+                    for t, v in zip(rest, lp):
+                        totals[t[2]] += v
+        self.last_generation_stats = dict(prompt_rows=P, branch_rows=branch_rows, passes=len(passes))
+        return torch.tensor(totals, dtype=torch.float64).to(torch.float32).to(eng.device)
+
     # --- speculative verify steps (prompt lookup): R rows of one conversation per pass over the weights
     def spec_decoder(self, rows, max_new=1024, ngram_max=2):
         from .speculative import SpecDecoder
