@@ -249,6 +249,26 @@ _SIGS_SCORE = {
     "teo_token_logprobs": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
 }
 EXPORTS_SCORE = tuple(_SIGS_SCORE.keys())
+
+
+# include/teo_hip_guide.h: guided decoding -- a token automaton inside the decode step's tail, a fourth header of the same library
+class Guide(C.Structure):
+    _fields_ = [("d_next", C.c_void_p), ("n_states", C.c_int), ("vocab", C.c_int), ("d_state", C.c_void_p), ("fallback_token", C.c_longlong)]
+
+
+_SIGS_GUIDE = {
+    "teo_guide_sizeof": (C.c_size_t, []),
+    "teo_guide_mask": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.POINTER(Guide), C.c_void_p]),
+    "teo_guide_advance": (C.c_int, [C.POINTER(Guide), C.c_void_p, C.c_int, C.c_void_p]),
+    "teo_llama_decode_step_guided": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeState), C.POINTER(Guide), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "teo_llama_decode_graph_create_guided": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeState), C.POINTER(Guide), C.c_void_p, C.c_size_t,
+                                                       C.c_void_p, C.POINTER(C.c_void_p)]),
+    "teo_llama_decode_stream_step_guided": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeStreamState), C.POINTER(Guide), C.c_void_p, C.c_size_t,
+                                                      C.c_void_p]),
+    "teo_llama_decode_stream_graph_create_guided": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeStreamState), C.POINTER(Guide), C.c_void_p,
+                                                              C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+}
+EXPORTS_GUIDE = tuple(_SIGS_GUIDE.keys())
 _lib = None
 
 
@@ -269,7 +289,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:
         raise TeoLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_PREFIX.items()) + list(_SIGS_SCORE.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_PREFIX.items()) + list(_SIGS_SCORE.items()) + list(_SIGS_GUIDE.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -285,6 +305,8 @@ def load():
         want = lib.teo_sizeof(name.encode())
         if want != C.sizeof(cls):
             raise TeoLibraryError(f"struct layout mismatch: {name} is {want} bytes in {LIB_PATH}, {C.sizeof(cls)} in this binding; rebuild")
+    if lib.teo_guide_sizeof() != C.sizeof(Guide):
+        raise TeoLibraryError(f"struct layout mismatch: teo_guide is {lib.teo_guide_sizeof()} bytes in {LIB_PATH}, {C.sizeof(Guide)} in this binding; rebuild")
     _lib = lib
     return lib
 

@@ -96,6 +96,20 @@ int verify_graph_create(const teo_llama_desc* d, const teo_verify_state* s, void
 
 static bool dtype_ok(int dt) { return dt == TEO_F32 || dt == TEO_BF16 || dt == TEO_F16; }
 
+// the argument checks of the single-conversation decode step: teo_llama_decode_step, its profiled form and the guided forms of
+// include/teo_hip_guide.h (guide.hip) all run this one
+int decode_state_check(const teo_llama_desc* d, const teo_decode_state* st, const char* who) {
+    TEO_CHECK_ARG(d && st, "%s: null desc / state", who);
+    TEO_CHECK_ARG(dtype_ok(d->dtype), "%s: bad dtype %d", who, d->dtype);
+    TEO_CHECK_ARG(st->d_token && st->d_pos && st->d_out_tokens && st->d_out_count && st->d_logits,
+                  "%s: null d_token / d_pos / d_out_tokens / d_out_count / d_logits", who);
+    if (st->do_sample) {
+        TEO_CHECK_ARG(st->d_rng && st->temperature > 0.f, "%s: null d_rng or temperature %g", who, st->temperature);
+        const int rc = sampler_check(d->vocab, st->top_k, st->top_p); if (rc != TEO_OK) return rc;
+    }
+    return TEO_OK;
+}
+
 }  // namespace teo
 
 using namespace teo;
@@ -535,14 +549,9 @@ int teo_llama_prefill_slots(const teo_llama_desc* d, const void* emb, const int*
 size_t teo_llama_decode_workspace_bytes(const teo_llama_desc* d) { return d ? llama_decode_workspace_bytes(d) : 0; }
 int teo_llama_decode_step(const teo_llama_desc* d, const teo_decode_state* st, void* ws, size_t wsb, teo_stream_t s) {
     ENTER();
-    NEED(d, "desc"); NEED(st, "state"); NEED(ws, "workspace"); NEED_DT(d->dtype);
+    { const int rc = decode_state_check(d, st, __func__); if (rc != TEO_OK) return rc; }
+    NEED(ws, "workspace");
     TuneScope tune_scope(d->tune);
-    NEED(st->d_token, "d_token"); NEED(st->d_pos, "d_pos"); NEED(st->d_out_tokens, "d_out_tokens");
-    NEED(st->d_out_count, "d_out_count"); NEED(st->d_logits, "d_logits");
-    if (st->do_sample) {
-        NEED(st->d_rng, "d_rng"); TEO_CHECK_ARG(st->temperature > 0.f, "teo_llama_decode_step: temperature %g", st->temperature);
-        const int rc = sampler_check(d->vocab, st->top_k, st->top_p); if (rc != TEO_OK) return rc;
-    }
     return llama_decode_step(d, st, ws, wsb, ST(s));
 }
 
@@ -560,14 +569,9 @@ int teo_vit_workspace_status(const teo_vit_desc* d, int T, void* ws, size_t wsb,
 int teo_llama_decode_step_profile(const teo_llama_desc* d, const teo_decode_state* st, void* ws, size_t wsb, float* ms_out, int* count_out,
                                   teo_stream_t s) {
     ENTER();
-    NEED(d, "desc"); NEED(st, "state"); NEED(ws, "workspace"); NEED_DT(d->dtype);
+    { const int rc = decode_state_check(d, st, __func__); if (rc != TEO_OK) return rc; }
+    NEED(ws, "workspace");
     TuneScope tune_scope(d->tune);
-    NEED(st->d_token, "d_token"); NEED(st->d_pos, "d_pos"); NEED(st->d_out_tokens, "d_out_tokens");
-    NEED(st->d_out_count, "d_out_count"); NEED(st->d_logits, "d_logits");
-    if (st->do_sample) {
-        NEED(st->d_rng, "d_rng"); TEO_CHECK_ARG(st->temperature > 0.f, "teo_llama_decode_step: temperature %g", st->temperature);
-        const int rc = sampler_check(d->vocab, st->top_k, st->top_p); if (rc != TEO_OK) return rc;
-    }
     NEED(ms_out, "ms_out"); NEED(count_out, "count_out");
     return llama_decode_step_profile(d, st, ws, wsb, ms_out, count_out, ST(s));
 }
@@ -894,3 +898,8 @@ int teo_gemm_skinny_w4(const void* x, const void* W4, const void* e8m0, const vo
 
 // the prefill entry points of the second header (include/teo_hip_prefix.h, prefix.hip) run the same weight checks
 int teo::llama_prefill_check_weights(const teo_llama_desc* d) { return check_prefill_weights(d); }
+
+namespace teo {
+// the stream step's argument checks for the guided entry points (guide.hip)
+int stream_state_check(const teo_llama_desc* d, const teo_decode_stream_state* st) { return check_stream_state(d, st); }
+}  // namespace teo

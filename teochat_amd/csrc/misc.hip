@@ -1,6 +1,7 @@
 // Data-movement and small kernels: RoPE + KV append, V transposes, im2col, embedding splice, CLS drop, argmax,
 // decode bookkeeping.  All HBM/latency-bound; none is shaped into a GEMM.
 #include "common.h"
+#include "guide_dev.h"
 
 namespace teo {
 
@@ -859,6 +860,75 @@ int decode_tail(const float* logits, const teo_decode_state* s, const void* embe
                     (const bf16_t*)g0, (bf16_t*)hg, ssq, nparts);
     TEO_LAUNCH_CHECK("decode_tail");
     return TEO_OK;
+}
+
+// Guided tail (include/teo_hip_guide.h): the row's disallowed logits are overwritten with -inf IN PLACE, then decode_tail_body selects,
+// appends, advances and tests the stop on the masked row, then thread 0 moves the row's automaton state.  `logits` is a plain pointer
+// here: the mask's stores come before decode_tail_body's restrict-qualified reads begin, and a workgroup fence plus a barrier lie
+// between them, so every thread's select reads every other thread's -inf.  A parked stream slot goes straight to the body (which only
+// re-emits its embedding row).  A state outside the table, or a table row that allows nothing, takes the fallback: nothing is read
+// from the table (first case), the token is g.fallback_token, d_stop is set (a stream slot parks), the state and the sampler's draw
+// counter stay.
+template <typename T, bool STREAM>
+__global__ __launch_bounds__(1024) void decode_tail_guided_kernel(float* logits, teo_decode_state st, teo_guide g,
+                                                                  const T* __restrict__ embed, T* __restrict__ h, int vocab, int dim,
+                                                                  int out_stride, const T* __restrict__ g0, T* __restrict__ hg,
+                                                                  float* __restrict__ ssq, int nparts, const int* __restrict__ d_limit) {
+    const long long b = blockIdx.x;
+    const bool parked = STREAM && st.d_pos[b] < 0;          // uniform over the workgroup
+    int state = 0;
+    if (!parked) {
+        state = g.d_state[b];
+        bool ok = state >= 0 && state < g.n_states;
+        if (ok) ok = __syncthreads_or(guide_mask_row(logits + b * vocab, g.d_next + (size_t)state * vocab, vocab) ? 1 : 0) != 0;
+        if (!ok) {
+            __shared__ float red16[16];
+            const long long t = g.fallback_token;
+            if (threadIdx.x == 0) {
+                st.d_token[b] = t;
+                const int n = st.d_out_count[b];
+                st.d_out_tokens[b * out_stride + n] = t;
+                st.d_out_count[b] = n + 1;
+                const int p = st.d_pos[b] + 1;
+                st.d_stop[b] = 1;
+                st.d_pos[b] = STREAM ? -1 - p : p;
+            }
+            embed_row_emit<T>(embed, t, h + b * dim, dim, g0, hg ? hg + b * dim : nullptr, hg ? ssq + b * nparts : nullptr, nparts, red16);
+            return;
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+    decode_tail_body<T, STREAM>(logits, st, embed, h, vocab, dim, out_stride, g0, hg, ssq, nparts, d_limit);
+    if (!parked && threadIdx.x == 0) g.d_state[b] = g.d_next[(size_t)state * vocab + st.d_token[b]];    // thread 0 wrote d_token itself
+}
+
+template <bool STREAM>
+static int launch_tail_guided(float* logits, const teo_decode_state* s, const teo_guide* g, const int* d_limit, const void* embed, void* h,
+                              int vocab, int dim, int dtype, hipStream_t st, int batch, int out_stride, const void* g0, void* hg, float* ssq,
+                              int nparts) {
+    if (dtype == TEO_F32)
+        TEO_KLAUNCH((decode_tail_guided_kernel<float, STREAM>), batch, 1024, 0, st, logits, *s, *g, (const float*)embed, (float*)h, vocab, dim,
+                    out_stride, (const float*)g0, (float*)hg, ssq, nparts, d_limit);
+    else if (dtype == TEO_F16)
+        TEO_KLAUNCH((decode_tail_guided_kernel<f16_t, STREAM>), batch, 1024, 0, st, logits, *s, *g, (const f16_t*)embed, (f16_t*)h, vocab, dim,
+                    out_stride, (const f16_t*)g0, (f16_t*)hg, ssq, nparts, d_limit);
+    else
+        TEO_KLAUNCH((decode_tail_guided_kernel<bf16_t, STREAM>), batch, 1024, 0, st, logits, *s, *g, (const bf16_t*)embed, (bf16_t*)h, vocab,
+                    dim, out_stride, (const bf16_t*)g0, (bf16_t*)hg, ssq, nparts, d_limit);
+    TEO_LAUNCH_CHECK(STREAM ? "decode_stream_tail_guided" : "decode_tail_guided");
+    return TEO_OK;
+}
+
+int decode_tail_guided(float* logits, const teo_decode_state* s, const teo_guide* g, const void* embed, void* h, int vocab, int dim,
+                       int dtype, hipStream_t st, int batch, int out_stride, const void* g0, void* hg, float* ssq, int nparts) {
+    return launch_tail_guided<false>(logits, s, g, nullptr, embed, h, vocab, dim, dtype, st, batch, out_stride, g0, hg, ssq, nparts);
+}
+
+int decode_stream_tail_guided(float* logits, const teo_decode_state* s, const teo_guide* g, const int* d_limit, const void* embed, void* h,
+                              int vocab, int dim, int dtype, hipStream_t st, int batch, int out_stride, const void* g0, void* hg, float* ssq,
+                              int nparts) {
+    return launch_tail_guided<true>(logits, s, g, d_limit, embed, h, vocab, dim, dtype, st, batch, out_stride, g0, hg, ssq, nparts);
 }
 
 int argmax(const float* logits, long long* tok, int rows, int vocab, hipStream_t st) {

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "ops.h"
+#include "guide_dev.h"
 
 namespace teo {
 struct Carver {
@@ -448,7 +449,8 @@ static DecodeWs decode_carve(const teo_llama_desc* d, void* ws, size_t cap) {
 
 size_t llama_decode_workspace_bytes(const teo_llama_desc* d) { return decode_carve(d, nullptr, 0).total; }
 
-int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
+// g (optional, include/teo_hip_guide.h): the guided tail instead of the plain one; every launch in front of it is the same
+int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st, const teo_guide* g) {
     // MXFP4 copies: all eight per-layer arrays or none, never beside the fp8 copies, bf16 activations (checked before any launch)
     const bool w4 = d->qkv_w4 != nullptr;
     if (w4 || d->qkv_e4 || d->o_w4 || d->o_e4 || d->gateup_w4 || d->gateup_e4 || d->down_w4 || d->down_e4) {
@@ -523,7 +525,12 @@ int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* 
     }
     // argmax -> append/advance/stop test -> embedding row of the next token into w.h, one launch
     prof_class(TEO_PROF_TAIL);
+    if (g) return decode_tail_guided(s->d_logits, s, g, d->embed, w.h, d->vocab, D, dt, st);
     return decode_tail(s->d_logits, s, d->embed, w.h, d->vocab, D, dt, st);
+}
+
+int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
+    return llama_decode_step(d, s, ws, ws_bytes, st, nullptr);
 }
 
 
@@ -683,8 +690,9 @@ static int decode_batch_layers(const teo_llama_desc* d, const BatchLoopOpts& o, 
 
 // d_limit == NULL: the batched step.  d_limit != NULL: the stream step (teo_decode_stream_state) -- the same launches with the
 // self-parking tail; the attention kernels skip parked conversations (d_pos < 0) by themselves.
+// g (optional, stream step only): the guided stream tail.
 static int decode_batch_step_impl(const teo_llama_desc* d, const teo_decode_batch_state* s, const int* d_limit, void* ws, size_t ws_bytes,
-                                  const char* who, hipStream_t st) {
+                                  const char* who, hipStream_t st, const teo_guide* g = nullptr) {
     const int B = s->batch;
     const DecodeBatchWs w = decode_batch_carve(d, B, ws, ws_bytes);
     if (w.total > ws_bytes) {
@@ -705,6 +713,13 @@ static int decode_batch_step_impl(const teo_llama_desc* d, const teo_decode_batc
     TEO_TRY(decode_batch_layers(d, o, w, s->d_logits, attend, &skinny, who, st));
     const teo_decode_state t = batch_as_state(s);
     prof_class(TEO_PROF_TAIL);
+    if (d_limit && g) {
+        if (skinny)
+            return decode_stream_tail_guided(s->d_logits, &t, g, d_limit, d->embed, w.h, d->vocab, D, dt, st, B, s->out_stride, d->in_norm_w[0],
+                                             w.hg, w.ssq, w.nparts);
+        return decode_stream_tail_guided(s->d_logits, &t, g, d_limit, d->embed, w.h, d->vocab, D, dt, st, B, s->out_stride, nullptr, nullptr,
+                                         nullptr, 0);
+    }
     if (d_limit) {
         if (skinny)
             return decode_stream_tail(s->d_logits, &t, d_limit, d->embed, w.h, d->vocab, D, dt, st, B, s->out_stride, d->in_norm_w[0], w.hg,
@@ -731,9 +746,14 @@ static teo_decode_batch_state stream_as_batch(const teo_decode_stream_state* s) 
     return b;
 }
 
-int llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
+int llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
+                             const teo_guide* g) {
     const teo_decode_batch_state b = stream_as_batch(s);
-    return decode_batch_step_impl(d, &b, s->d_limit, ws, ws_bytes, "teo_llama_decode_stream_step", st);
+    return decode_batch_step_impl(d, &b, s->d_limit, ws, ws_bytes, g ? "teo_llama_decode_stream_step_guided" : "teo_llama_decode_stream_step", st, g);
+}
+
+int llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
+    return llama_decode_stream_step(d, s, ws, ws_bytes, st, nullptr);
 }
 
 // row `slot` of the residual stream <- embed[d_token[slot]] (skinny path: also layer 0's norm inputs for that row).  No other row is
@@ -910,6 +930,11 @@ int decode_graph_create(const teo_llama_desc* d, const teo_decode_state* s, void
     return capture_graph(st, [&]() { return llama_decode_step(d, s, ws, ws_bytes, st); }, out);
 }
 
+int decode_graph_create(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st, teo_graph** out,
+                        const teo_guide* g) {
+    return capture_graph(st, [&]() { return llama_decode_step(d, s, ws, ws_bytes, st, g); }, out);
+}
+
 int decode_batch_graph_create(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes,
                               hipStream_t st, teo_graph** out) {
     return capture_graph(st, [&]() { return llama_decode_batch_step(d, s, ws, ws_bytes, st); }, out);
@@ -918,6 +943,11 @@ int decode_batch_graph_create(const teo_llama_desc* d, const teo_decode_batch_st
 int decode_stream_graph_create(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
                                teo_graph** out) {
     return capture_graph(st, [&]() { return llama_decode_stream_step(d, s, ws, ws_bytes, st); }, out);
+}
+
+int decode_stream_graph_create(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
+                               teo_graph** out, const teo_guide* g) {
+    return capture_graph(st, [&]() { return llama_decode_stream_step(d, s, ws, ws_bytes, st, g); }, out);
 }
 
 int llama_verify_step_profile(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, float* ms_out, int* count_out,

@@ -279,6 +279,32 @@ def rope_tables(head_dim, theta, max_pos):
     return fr.cos().contiguous(), fr.sin().contiguous()
 
 
+def replay_or_step(owner, graph_attr, key_attr, key, n, use_graph, st, create, step):
+    """n decode steps of `owner` (an engine or a decoder) on stream st: plain launches (step()), or replays of the graph kept in
+    owner.<graph_attr>, captured again by create(out) whenever `key` -- everything the capture holds by value -- is not owner.<key_attr>.
+    The stream is drained behind the replays: replays still outstanding when another command is enqueued run 8 % slower (_Phase.__exit__)."""
+    if not use_graph:
+        for _ in range(n):
+            step()
+        return
+    lib = owner.lib
+    if getattr(owner, graph_attr) is None or getattr(owner, key_attr) != key:
+        if getattr(owner, graph_attr) is not None:
+            lib.teo_graph_destroy(getattr(owner, graph_attr))
+            setattr(owner, graph_attr, None)
+        g = C.c_void_p()
+        create(C.byref(g))
+        setattr(owner, graph_attr, g)
+        setattr(owner, key_attr, key)
+    L.check(lib.teo_graph_launch(getattr(owner, graph_attr), n, st), "teo_graph_launch")
+    (owner.eng if hasattr(owner, "eng") else owner).stream.synchronize()
+
+
+def guide_graph_key(gd, ws):
+    """what a guided graph holds by value: the teo_guide fields and the workspace"""
+    return (gd.d_next, gd.n_states, gd.vocab, gd.d_state, gd.fallback_token, ws.data_ptr())
+
+
 class TeoEngine:
     def __init__(self, state_dict, config, dtype=torch.bfloat16, device="cuda:0", max_seq=None, weight_format=None, mxfp4_only=False,
                  decode_pack=True):
@@ -319,7 +345,11 @@ class TeoEngine:
         self._pending_status = {}                 # workspace key -> deferred hand-off check (see _check_handoffs)
         self._option_hooks = []                   # callables(desc): keep copies of the LLaMA descriptor in step with set_options
         self._tune_hooks = []                     # callables(): a knob changed -- captured graphs bake kernel choices in and are dropped
-        self._graph = None
+        self._graph, self._graph_ws = None, None
+        # guided decoding (guide_begin): the armed teo_guide and its object, the guided step's graph and what it was captured on, the device
+        # tables kept (guide_table) and the single conversation's automaton state
+        self._guide, self._guide_obj, self._guided_graph, self._guided_key, self._guide_tables = None, None, None, None, []
+        self.d_guide_state = torch.zeros(1, dtype=torch.int32, device=device)
         # performance knobs of THIS engine: a teo_tune block every descriptor points at (include/teo_hip.h); nothing process-wide
         self.tune = L.Tune()
         self._load_vit(state_dict)
@@ -1001,6 +1031,67 @@ class TeoEngine:
         if self._graph is not None:
             self.lib.teo_graph_destroy(self._graph)
             self._graph = None
+        if self._guided_graph is not None:
+            self.lib.teo_graph_destroy(self._guided_graph)
+            self._guided_graph = None
+
+    # ------------------------------------------------------------------ guided decoding (include/teo_hip_guide.h, teochat_amd/guide.py)
+    GUIDE_TABLES_KEPT = 4
+
+    def guide_table(self, guide):
+        """The device copy of guide.next (a TokenGuide or a GuideSet), uploaded once per distinct object; the last GUIDE_TABLES_KEPT are
+        kept.  int16 storage of the uint16 values."""
+        import numpy as np
+        kept = self._guide_tables
+        for i, (g, t) in enumerate(kept):
+            if g is guide:
+                kept.append(kept.pop(i))
+                return t
+        if guide.vocab != self.cfg.vocab_size:
+            raise ValueError(f"the guide's table is {guide.vocab} tokens wide, the model's vocabulary {self.cfg.vocab_size}")
+        with self.phase():
+            t = torch.from_numpy(np.ascontiguousarray(guide.next).view(np.int16)).to(self.device)
+        kept.append((guide, t))
+        del kept[:-self.GUIDE_TABLES_KEPT]
+        return t
+
+    def guide_struct(self, guide, d_state, fallback_token=None):
+        """teo_guide over the cached table and the int32 device tensor d_state (one state per row)"""
+        g = L.Guide()
+        g.d_next, g.n_states, g.vocab = self.guide_table(guide).data_ptr(), int(guide.n_states), int(guide.vocab)
+        g.d_state = d_state.data_ptr()
+        if fallback_token is None:
+            fallback_token = guide.eos if getattr(guide, "eos", None) is not None else 0
+        g.fallback_token = int(fallback_token)
+        return g
+
+    def guide_begin(self, guide, start=None):
+        """Arm the single-conversation steps with `guide`: decode_steps runs the guided step until guide_end().  The state starts at
+        `start` (default guide.start); guide_mask / guide_advance below act on it for the first token, which the host path selects."""
+        with self.phase():
+            self.d_guide_state.fill_(int(guide.start if start is None else start))
+        self._guide = self.guide_struct(guide, self.d_guide_state)
+        self._guide_obj = guide
+
+    def guide_end(self):
+        self._guide = self._guide_obj = None
+
+    def guide_mask(self, logits, g=None):
+        """-inf over the disallowed tokens of fp32 logits [rows, V] (contiguous, on the device), in place, by the states of `g` (default:
+        the armed guide's single state)"""
+        g = self._guide if g is None else g
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or not logits.is_cuda or logits.dim() > 2:
+            raise ValueError("guide_mask: logits must be a contiguous fp32 tensor [V] or [rows, V] on the engine's device")
+        rows = 1 if logits.dim() == 1 else int(logits.shape[0])
+        with self.phase() as st:
+            L.check(self.lib.teo_guide_mask(_p(logits), int(logits.shape[-1]), rows, C.byref(g), st), "teo_guide_mask")
+
+    def guide_advance(self, tokens, g=None):
+        """state[r] = next[state[r]][tokens[r]] (int64 device tensor or a list of ints)"""
+        g = self._guide if g is None else g
+        with self.phase() as st:
+            tok = torch.as_tensor(tokens, dtype=torch.int64).reshape(-1).to(self.device)
+            L.check(self.lib.teo_guide_advance(C.byref(g), _p(tok), tok.numel(), st), "teo_guide_advance")
 
     def decode_steps(self, n, use_graph=True):
         """Run n greedy steps on the device (hipGraph replay by default).  The caller bounds n by max_seq."""
@@ -1010,23 +1101,21 @@ class TeoEngine:
             raise ValueError(f"decode_steps: {self.steps_since_begin + n} tokens since decode_begin exceed the output buffer "
                              f"({self.max_new_cap}); call decode_begin again or build the engine with a larger max_new")
         ws = self._workspace("decode", self.lib.teo_llama_decode_workspace_bytes(C.byref(self.llama_desc)))
+        d, s_ = C.byref(self.llama_desc), C.byref(self.decode_state)
+        gd = self._guide
         with self.phase() as st:
-            if use_graph:
-                if self._graph is None or self._graph_ws != ws.data_ptr():
-                    self._drop_graph()
-                    g = C.c_void_p()
-                    L.check(self.lib.teo_llama_decode_graph_create(C.byref(self.llama_desc), C.byref(self.decode_state),
-                                                                   _p(ws), ws.numel(), st, C.byref(g)),
-                            "teo_llama_decode_graph_create")
-                    self._graph, self._graph_ws = g, ws.data_ptr()
-                L.check(self.lib.teo_graph_launch(self._graph, n, st), "teo_graph_launch")
-                # drain before anything else is queued behind the replays (an event record, a D2H copy of the token buffer):
-                # replays still outstanding when such a command is enqueued run 8 % slower (see _Phase.__exit__)
-                self.stream.synchronize()
+            if gd is not None:
+                # the guided step (include/teo_hip_guide.h) and a graph of its own: the plain graph is left alone
+                g_ = C.byref(gd)
+                replay_or_step(self, "_guided_graph", "_guided_key", guide_graph_key(gd, ws), n, use_graph, st,
+                               lambda out: L.check(self.lib.teo_llama_decode_graph_create_guided(d, s_, g_, _p(ws), ws.numel(), st, out),
+                                                   "teo_llama_decode_graph_create_guided"),
+                               lambda: L.check(self.lib.teo_llama_decode_step_guided(d, s_, g_, _p(ws), ws.numel(), st), "teo_llama_decode_step_guided"))
             else:
-                for _ in range(n):
-                    L.check(self.lib.teo_llama_decode_step(C.byref(self.llama_desc), C.byref(self.decode_state), _p(ws),
-                                                           ws.numel(), st), "teo_llama_decode_step")
+                replay_or_step(self, "_graph", "_graph_ws", ws.data_ptr(), n, use_graph, st,
+                               lambda out: L.check(self.lib.teo_llama_decode_graph_create(d, s_, _p(ws), ws.numel(), st, out),
+                                                   "teo_llama_decode_graph_create"),
+                               lambda: L.check(self.lib.teo_llama_decode_step(d, s_, _p(ws), ws.numel(), st), "teo_llama_decode_step"))
         self.cache_len += n
         self.steps_since_begin = getattr(self, "steps_since_begin", 0) + n
 

@@ -37,7 +37,9 @@ def build_prompt(inp, image_paths, conv_mode="v1", prompt_strategy="interleave",
 
 def run_inference_single(model, processor, tokenizer, inp, image_paths, conv_mode="v1", timestamps=[],
                          prompt_strategy="interleave", chronological_prefix=True, temperature=0.2, max_new_tokens=256,
-                         do_sample=True, prompt_lookup_num_tokens=None, max_matching_ngram_size=None):
+                         do_sample=True, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, guide=None):
+    """guide (extra trailing keyword): a teochat_amd.guide.TokenGuide over the tokenizer's vocabulary -- the answer is generated under it
+    (model.generate(guide=...)); None: the keyword is not passed on."""
     if len(timestamps) > 0:
         order = sorted(range(len(image_paths)), key=lambda i: datetime.strptime(timestamps[i], "%Y-%m-%d"))
         image_paths = [image_paths[i] for i in order]
@@ -53,6 +55,8 @@ def run_inference_single(model, processor, tokenizer, inp, image_paths, conv_mod
             spec["prompt_lookup_num_tokens"] = prompt_lookup_num_tokens
         if max_matching_ngram_size is not None:
             spec["max_matching_ngram_size"] = max_matching_ngram_size
+        if guide is not None:
+            spec["guide"] = guide
         output_ids = model.generate(input_ids=input_ids, images=frames, do_sample=do_sample, temperature=temperature,
                                     max_new_tokens=max_new_tokens, use_cache=True, stopping_criteria=[stopping], **spec)
     return tokenizer.decode(output_ids[0, input_ids.shape[1]:]).replace("</s>", "").strip()
@@ -94,7 +98,7 @@ def run_inference_options(model, processor, tokenizer, inp, image_paths, options
 
 def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, conv_mode="v1", timestamps_list=None,
                         prompt_strategy="interleave", chronological_prefix=True, temperature=0.2, max_new_tokens=256,
-                        do_sample=True, continuous=False, slots=None, prefix_cache=False):
+                        do_sample=True, continuous=False, slots=None, prefix_cache=False, guides=None):
     """run_inference_single for up to 16 examples at once (not in the reference, whose loop is one example at a time,
     inference.py:100-113): the same prompt construction, frame order, tokenisation and stop keyword per example, then ONE
     batched generation -- every frame of every example through the tower together, one prefill per example, and a decode loop
@@ -110,13 +114,18 @@ def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, con
 
     prefix_cache=True (with continuous=True only): examples about the same image sequence share its prefill -- generate_stream's
     prefix_keys, the key being the tuple of the example's image paths after the timestamp sort (paths that are not strings: no key).
-    An example that starts from another one's rows neither opens nor preprocesses its images."""
+    An example that starts from another one's rows neither opens nor preprocesses its images.
+
+    guides (with continuous=True only): one teochat_amd.guide.TokenGuide or None per example (any sequence with len() and []), handed to
+    generate_stream(guides=...)."""
     B = len(inps)
     if prefix_cache and not continuous:
         raise ValueError("prefix_cache needs continuous=True (prefix reuse lives in the stream decoder's slots)")
+    if guides is not None and not continuous:
+        raise ValueError("guides needs continuous=True (generate_stream takes one guide per request; the fixed-group batched step takes none)")
     if continuous:
         return _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, conv_mode, timestamps_list, prompt_strategy,
-                                     chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache)
+                                     chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache, guides)
     if timestamps_list is None:
         timestamps_list = [[] for _ in range(B)]
     if len(image_paths_list) != B or len(timestamps_list) != B:
@@ -170,7 +179,7 @@ class _Prepared:
 
 
 def _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, conv_mode, timestamps_list, prompt_strategy,
-                          chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache=False):
+                          chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache=False, guides=None):
     N = len(inps)
     if N == 0:
         return []
@@ -211,7 +220,7 @@ def _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, c
     with torch.inference_mode():
         outs = model.generate_stream(prepared.column(0), prepared.column(1), slots=slots, do_sample=do_sample, temperature=temperature,
                                      max_new_tokens=max_new_tokens, stopping_criteria=prepared.column(2),
-                                     **({"prefix_keys": Keys()} if prefix_cache else {}))
+                                     **({"prefix_keys": Keys()} if prefix_cache else {}), **({"guides": guides} if guides is not None else {}))
     return [tokenizer.decode(o[n_prompt[i]:]).replace("</s>", "").strip() for i, o in enumerate(outs)]
 
 
@@ -242,7 +251,7 @@ def _record(example, response, dataset):
 
 
 def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronological_prefix, conv_mode, temperature,
-                  max_new_tokens, batch_size=1, continuous=False, prefix_cache=False):
+                  max_new_tokens, batch_size=1, continuous=False, prefix_cache=False, guide=None):
     """Dataset loop with the bookkeeping the metrics need (inference.py:88-137): response / ground truth / task per example,
     the example's polygon when it has one, and the integer boxes quoted in the question and in the reference answer.
     batch_size (extra trailing keyword, default 1 = the reference's loop): answer that many consecutive examples per
@@ -250,11 +259,17 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
     continuous=True (extra trailing keyword, default off): the whole dataset goes through ONE generate_stream over batch_size
     conversation slots (run_inference_batch(continuous=True)); examples are read and prepared as slots free up.
     prefix_cache=True (with continuous=True): examples with the same image paths share the prefill of everything up to their last
-    <image> (run_inference_batch(prefix_cache=True)); the records are the same."""
+    <image> (run_inference_batch(prefix_cache=True)); the records are the same.
+    guide (extra trailing keyword): a teochat_amd.guide.TokenGuide for every example, or a callable(example) -> TokenGuide or None.  With
+    batch_size 1 it goes to run_inference_single(guide=...), with continuous=True to generate_stream(guides=...); groups of a fixed
+    batch_size > 1 take no guide (ValueError)."""
     if not 1 <= int(batch_size) <= 16:
         raise ValueError(f"batch_size {batch_size}: 1..16 examples per generation")
     if prefix_cache and not continuous:
         raise ValueError("prefix_cache needs continuous=True")
+    if guide is not None and not continuous and batch_size != 1:
+        raise ValueError("guide needs batch_size=1 or continuous=True")
+    guide_of = guide if callable(guide) else (lambda example: guide)
     outputs = []
     if continuous:
         n = len(dataset)
@@ -272,14 +287,15 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
                                         Field(lambda e: e["video"]), conv_mode=conv_mode, timestamps_list=Field(lambda e: e["timestamp"]),
                                         prompt_strategy=prompt_strategy, chronological_prefix=chronological_prefix, temperature=temperature,
                                         max_new_tokens=max_new_tokens, continuous=True, slots=int(batch_size),
-                                        **({"prefix_cache": True} if prefix_cache else {}))
+                                        **({"prefix_cache": True} if prefix_cache else {}),
+                                        **({"guides": Field(guide_of)} if guide is not None else {}))
         return [_record(dataset[i], r, dataset) for i, r in enumerate(responses)]
     if batch_size == 1:
         for example in dataset:
             response = run_inference_single(model, processor, tokenizer, example["conversations"][0]["value"], example["video"],
                                             conv_mode=conv_mode, timestamps=example["timestamp"], prompt_strategy=prompt_strategy,
                                             chronological_prefix=chronological_prefix, temperature=temperature,
-                                            max_new_tokens=max_new_tokens)
+                                            max_new_tokens=max_new_tokens, **({"guide": guide_of(example)} if guide is not None else {}))
             outputs.append(_record(example, response, dataset))
         return outputs
     group = []

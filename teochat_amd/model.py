@@ -502,11 +502,14 @@ class LlavaLlamaForCausalLM:
         # one engine phase around the whole call: tower, projector, splice, prefill and the decode chunks run back to back on the
         # engine stream with a single hand-over to the caller's stream at the end (no stream edges between the pieces)
         with self.engine.phase():
-            return self._generate(*args, **kwargs)
+            try:
+                return self._generate(*args, **kwargs)
+            finally:
+                self.engine.guide_end()           # a guide arms the engine's steps for this call only
 
     def _generate(self, input_ids=None, images=None, do_sample=None, temperature=None, top_k=None, top_p=None,
                   max_new_tokens=20, use_cache=True, stopping_criteria=None, eos_token_id="config", attention_mask=None,
-                  generator=None, chunk=16, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, prefix_key=None, **kwargs):
+                  generator=None, chunk=16, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, prefix_key=None, guide=None, **kwargs):
         """Greedy or sampled (temperature / top-k, device sampler) decoding of ONE sequence; the loop is device-resident
         and replayed from a hipGraph.
 
@@ -523,6 +526,14 @@ class LlavaLlamaForCausalLM:
         carry other kernels' bits), at least one id left -- prefills only the rest behind those rows and skips the tower (`images` is
         not read).  Equal keys promise equal frames.  Any other generate() call, and anything that resets or prefills the engine
         cache, forgets the record.  `last_generation_stats` = {prefix_rows_reused, prefill_rows} afterwards.
+
+        guide=g (a teochat_amd.guide.TokenGuide over this model's vocabulary; one conversation, not with prompt_lookup_num_tokens):
+        guided decoding.  Every token -- the first one, which the host path selects from the prefill logits, and those of the device
+        loop -- is selected among the tokens the automaton allows in its current state (the others' logits are -inf before argmax / the
+        sampler; engine.d_logits holds the masked row afterwards), inside the step's tail kernel (include/teo_hip_guide.h), so the
+        loop stays device-resident.  EOS stays the stop; the guide decides when EOS is allowed, and `max_new_tokens` may still cut the
+        answer in the middle of the pattern.  Works with prefix_key (nothing in the prefix path reads the guide).
+        `last_generation_stats` gains guide_states and guide_table_bytes.
 
         Returns int64 [1, n_prompt + n_generated]; the prompt part still contains the -200 sentinels, as with the
         reference (eval/inference.py:75 slices at input_ids.shape[1]).  `eos_token_id=None` disables EOS stopping.
@@ -542,6 +553,12 @@ class LlavaLlamaForCausalLM:
             raise ValueError(f"prompt_lookup_num_tokens {K} outside 1..15")
         if K and input_ids.shape[0] != 1:
             raise ValueError("prompt_lookup_num_tokens applies to one conversation (batch 1)")
+        if guide is not None and K:
+            raise ValueError("guide is not combined with prompt_lookup_num_tokens")
+        if guide is not None and input_ids.shape[0] != 1:
+            raise ValueError("guide applies to one conversation (batch 1); generate_stream(guides=...) takes one guide per request")
+        if guide is not None and guide.vocab != self.engine.cfg.vocab_size:
+            raise ValueError(f"the guide's table is {guide.vocab} tokens wide, the model's vocabulary {self.engine.cfg.vocab_size}")
         if input_ids.shape[0] != 1:
             # batch of conversations: rows are cut by attention_mask, `images` is a list with one entry per conversation
             B = input_ids.shape[0]
@@ -611,6 +628,12 @@ class LlavaLlamaForCausalLM:
                 self.last_generation_stats = dict(prefix_rows_reused=reuse[1], prefill_rows=int(embeds.shape[1]))
                 if row_map is not None:             # (key, ids, rows per id, rows written by prefill, the cache's epoch)
                     self._prefix_record = (prefix_key, ids_t, row_map, eng.cache_len, eng.cache_epoch)
+        if guide is not None:
+            eng.guide_begin(guide)
+            logits = logits.contiguous()
+            eng.guide_mask(logits[:1])             # the first token comes from the prefill logits: the same mask, the same state
+            self.last_generation_stats = dict(self.last_generation_stats or {}, guide_states=int(guide.n_states),
+                                              guide_table_bytes=int(guide.table_bytes))
         if do_sample:
             tp = 1.0 if top_p is None else float(top_p)
             k = int(top_k or 0)                    # 0 = top-k filter off (HF: top_k=0 / None disables TopKLogitsWarper)
@@ -619,6 +642,8 @@ class LlavaLlamaForCausalLM:
         else:
             k, seed, tp = 0, 0, 1.0
             first = self._argmax(logits[0])
+        if guide is not None:
+            eng.guide_advance([first])
         new_tokens = [first]
 
         def done(tokens):
@@ -864,7 +889,7 @@ class LlavaLlamaForCausalLM:
 
     def _generate_stream(self, input_ids_list, images_list=None, slots=8, max_new_tokens=20, do_sample=False, temperature=None,
                          top_k=None, top_p=None, stopping_criteria=None, eos_token_id="config", generator=None, chunk=16, prefix_keys=None,
-                         min_prefix_rows=64):
+                         min_prefix_rows=64, guides=None):
         """Answer N requests (any N >= 1) over `slots` <= 16 conversation slots of the batched decode step: a slot whose request has
         finished parks -- the attention kernels skip it -- and is refilled with the next request, so a step's work follows the requests
         that are still being answered instead of the longest answer of a fixed group (teochat_amd/stream.py).
@@ -887,7 +912,14 @@ class LlavaLlamaForCausalLM:
         slot keeps a private, complete cache, so the decode step is untouched.  The stats gain prefix_hits, prefix_rows_reused, forks,
         fork_rows, frames_skipped and prefill_rows.  In fp32 the answers are those without keys; in the 16-bit types a prompt prefilled
         in two pieces is not bit for bit the prompt prefilled in one (the suffix's GEMMs and RoPE take the kernels of a short prefill), so
-        answers may differ from the keyless run's the way two orderings of a sum differ (prefix reuse)."""
+        answers may differ from the keyless run's the way two orderings of a sum differ (prefix reuse).
+
+        guides: one teochat_amd.guide.TokenGuide or None per request (any sequence with len() and []) turns guided decoding on.  The
+        distinct guides (by identity) are concatenated into one GuideSet whose table is uploaded once; None is the automaton that allows
+        everything.  A request's first token is selected from its prefill logits under its guide's start state, its slot then starts
+        from the successor; the step's tail masks, selects and moves every live slot's state (include/teo_hip_guide.h).  EOS stays the
+        stop, the guide decides when it is allowed; max_new_tokens may cut an answer mid-pattern.  The stats gain guide_states and
+        guide_table_bytes."""
         from .stream import request_seed, run_stream
         N = len(input_ids_list)
         slots = int(slots)
@@ -914,6 +946,14 @@ class LlavaLlamaForCausalLM:
         eng = self.engine
         dec = self.stream_decoder(slots, max(max(max_new), 1))
         dec.reset()
+        gset = None
+        if guides is not None:
+            from .guide import GuideSet
+            if len(guides) != N:
+                raise ValueError("guides must hold one TokenGuide (or None) per request")
+            gset = GuideSet([guides[r] for r in range(N)], vocab=eng.cfg.vocab_size,
+                            eos=eos_token_id if eos_token_id is not None else self._config_eos())
+        dec.set_guide(gset)
         ids_of, crits_of = {}, {}                 # the requests in flight (and, for ids, the finished ones: a few integers each)
         dev_stop = {"ids": None, "off": False}    # the device stop: one id sequence shared by every request admitted so far, or off
 
@@ -967,12 +1007,22 @@ class LlavaLlamaForCausalLM:
                 seqs.append(embeds[b, int(on[0]):int(on[-1]) + 1])
             return seqs
 
-        def first_tokens(reqs, logits, lens):
+        def first_tokens(reqs, logits, lens, slot_list):
             out = []
+            if gset is not None:
+                # the first token of a request comes from its prefill logits: masked by its guide's start state, and the slot starts
+                # from the successor (a slot's earlier occupant left its own last state behind)
+                st0 = torch.tensor([gset.starts[r] for r in reqs], dtype=torch.int32, device=eng.device)
+                g0 = eng.guide_struct(gset, st0)
+                logits = logits.contiguous()
+                eng.guide_mask(logits, g0)
             for b, r in enumerate(reqs):
                 seed = request_seed(base_seed, r)
                 first = eng.sample(logits[b], temperature, k, seed, 0, top_p=tp) if do_sample else self._argmax(logits[b])
                 out.append((first, min(max_new[r] - 1, eng.max_seq - lens[b]), seed))
+            if gset is not None:
+                eng.guide_advance([f[0] for f in out], g0)
+                dec.set_guide_states(slot_list, st0)
             return out
 
         def admit_past(items):
@@ -999,7 +1049,7 @@ class LlavaLlamaForCausalLM:
                 seqs.append(seq)
                 lens.append(n)
             logits = dec.refill_past([it[1] for it in items], seqs, [it[3] for it in items])
-            return [f + (maps[b], int(seqs[b].shape[0])) for b, f in enumerate(first_tokens(reqs, logits, lens))]
+            return [f + (maps[b], int(seqs[b].shape[0])) for b, f in enumerate(first_tokens(reqs, logits, lens, [it[1] for it in items]))]
 
         def admit(reqs, slot_list):
             rows, flat = register(reqs, set(reqs))
@@ -1008,7 +1058,7 @@ class LlavaLlamaForCausalLM:
             for r, n in zip(reqs, lens):
                 if max_new[r] > 0 and n + max_new[r] > eng.max_seq:
                     raise ValueError(f"request {r}: prompt ({n}) + max_new_tokens ({max_new[r]}) exceeds max_seq {eng.max_seq}")
-            return first_tokens(reqs, dec.refill(slot_list, seqs), lens)
+            return first_tokens(reqs, dec.refill(slot_list, seqs), lens, slot_list)
 
         def host_done(r, toks):
             if eos_token_id is not None and toks[-1] == eos_token_id:
@@ -1040,6 +1090,9 @@ class LlavaLlamaForCausalLM:
         if stats is None:
             stats = dict(requests=0, steps=0, live_slot_steps=0, slot_steps=0, prefill_passes=0)
         stats["requests"] = N
+        if gset is not None:
+            stats.update(guide_states=int(gset.n_states), guide_table_bytes=int(gset.table_bytes))
+        dec.set_guide(None)
         self.last_generation_stats = stats
         return outs
 

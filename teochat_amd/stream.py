@@ -16,7 +16,7 @@ from collections import deque
 import torch
 
 from . import _lib as L
-from .engine import _p
+from .engine import _p, guide_graph_key, replay_or_step
 
 SEED_STRIDE = 0x9E3779B97F4A7C15              # request i draws from the Philox stream seeded (base + i * SEED_STRIDE) mod 2^63
 
@@ -55,6 +55,10 @@ class StreamDecoder:
         self.state = s
         self._graph = None
         self._graph_ws = None
+        # guided decoding (include/teo_hip_guide.h): one automaton state per slot, owned here for the decoder's life -- the guided graph
+        # holds its address -- and the teo_guide of the set in force (set_guide), with a graph of its own beside the plain one
+        self.d_guide_state = torch.zeros(slots, dtype=torch.int32, device=dev)
+        self._guide, self._guide_obj, self._guided_graph, self._guided_key = None, None, None, None
         # the step's workspace holds the slots' residual rows BETWEEN steps: this decoder's own, never a buffer another decoder writes
         self._ws = torch.empty(max(int(self.lib.teo_llama_decode_stream_workspace_bytes(C.byref(bd.desc), slots)), 256), dtype=torch.uint8, device=dev)
         import weakref
@@ -123,6 +127,30 @@ class StreamDecoder:
         if self._graph is not None:
             self.lib.teo_graph_destroy(self._graph)
             self._graph = None
+        if self._guided_graph is not None:
+            self.lib.teo_graph_destroy(self._guided_graph)
+            self._guided_graph = None
+
+    # ------------------------------------------------------------------ guided decoding
+    def set_guide(self, guide):
+        """guide: a GuideSet (or one TokenGuide) whose table every slot's state indexes, or None for the plain step.  The table is uploaded
+        once per distinct object (engine.guide_table); steps() then runs the guided step, whose tail masks, selects and moves each live
+        slot's state (a parked slot's state does not change).  Slot states are set with set_guide_states() before arm()."""
+        if guide is None:
+            self._guide = self._guide_obj = None
+            return
+        self._guide = self.eng.guide_struct(guide, self.d_guide_state)
+        self._guide_obj = guide
+
+    def set_guide_states(self, slot_list, states):
+        """d_guide_state[slot_list[i]] = states[i] (ints or an int32 device tensor): the state a slot's next step starts from"""
+        with self.eng.phase():
+            idx = torch.as_tensor([int(s) for s in slot_list], dtype=torch.long, device=self.eng.device)
+            self.d_guide_state[idx] = torch.as_tensor(states, dtype=torch.int32).to(self.eng.device).reshape(-1)
+
+    def guide_states(self):
+        with self.eng.phase():
+            return self.d_guide_state.tolist()
 
     # ------------------------------------------------------------------ refill + arm
     def refill(self, slot_list, embeds_list, last_only=True):
@@ -245,20 +273,22 @@ class StreamDecoder:
         eng, bd = self.eng, self.bd
         n = int(n)
         ws = self._workspace()
+        d, s_ = C.byref(bd.desc), C.byref(self.state)
+        gd = self._guide
         with eng.phase() as st:
-            if use_graph:
-                if self._graph is None or self._graph_ws != ws.data_ptr():
-                    self._drop_graph()
-                    g = C.c_void_p()
-                    L.check(self.lib.teo_llama_decode_stream_graph_create(C.byref(bd.desc), C.byref(self.state), _p(ws), ws.numel(), st,
-                                                                          C.byref(g)), "teo_llama_decode_stream_graph_create")
-                    self._graph, self._graph_ws = g, ws.data_ptr()
-                L.check(self.lib.teo_graph_launch(self._graph, n, st), "teo_graph_launch")
-                eng.stream.synchronize()          # drain the replays before anything is queued behind them (engine.py _Phase.__exit__)
+            if gd is not None:
+                # the guided step (include/teo_hip_guide.h) and a graph of its own beside the plain one
+                g_ = C.byref(gd)
+                replay_or_step(self, "_guided_graph", "_guided_key", guide_graph_key(gd, ws), n, use_graph, st,
+                               lambda out: L.check(self.lib.teo_llama_decode_stream_graph_create_guided(d, s_, g_, _p(ws), ws.numel(), st, out),
+                                                   "teo_llama_decode_stream_graph_create_guided"),
+                               lambda: L.check(self.lib.teo_llama_decode_stream_step_guided(d, s_, g_, _p(ws), ws.numel(), st),
+                                               "teo_llama_decode_stream_step_guided"))
             else:
-                for _ in range(n):
-                    L.check(self.lib.teo_llama_decode_stream_step(C.byref(bd.desc), C.byref(self.state), _p(ws), ws.numel(), st),
-                            "teo_llama_decode_stream_step")
+                replay_or_step(self, "_graph", "_graph_ws", ws.data_ptr(), n, use_graph, st,
+                               lambda out: L.check(self.lib.teo_llama_decode_stream_graph_create(d, s_, _p(ws), ws.numel(), st, out),
+                                                   "teo_llama_decode_stream_graph_create"),
+                               lambda: L.check(self.lib.teo_llama_decode_stream_step(d, s_, _p(ws), ws.numel(), st), "teo_llama_decode_stream_step"))
         self._stats["steps"] += n
         self._stats["slot_steps"] += n * self.B
 
