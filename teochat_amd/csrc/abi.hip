@@ -3,7 +3,7 @@
 
 #include <new>
 
-#include "ops.h"
+#include "runtime.h"
 
 namespace teo {
 
@@ -53,47 +53,6 @@ int hip_fail(hipError_t e, const char* what) {
     return TEO_ERR_HIP;
 }
 
-size_t vit_workspace_bytes(const teo_vit_desc* d, int T);
-int vit_encode(const teo_vit_desc* d, const void* pixels, int T, void* features, void* ws, size_t ws_bytes, hipStream_t st);
-size_t projector_workspace_bytes(const teo_proj_desc* d, int rows);
-int projector(const teo_proj_desc* d, const void* x, int rows, void* y, void* ws, size_t ws_bytes, hipStream_t st);
-size_t llama_prefill_workspace_bytes(const teo_llama_desc* d, int S);
-int llama_prefill(const teo_llama_desc* d, const void* embeds, const int* positions, int S, int past, int last_only,
-                  float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, void* attentions);
-int llama_prefill_batch(const teo_llama_desc* d, const void* embeds, const int* seq_lens, int nseq, long long cache_stride,
-                        int last_only, float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states,
-                        const int* slots = nullptr, const int* pasts = nullptr);
-int llama_prefill_check_weights(const teo_llama_desc* d);
-size_t llama_decode_workspace_bytes(const teo_llama_desc* d);
-int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st);
-int llama_decode_step_profile(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, float* ms_out, int* count_out,
-                              hipStream_t st);
-int llama_decode_batch_step_profile(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes, float* ms_out,
-                                    int* count_out, hipStream_t st);
-int llama_prefill_workspace_status(const teo_llama_desc* d, int S, void* ws, size_t ws_bytes, int* host_flag, hipStream_t st);
-int vit_workspace_status(const teo_vit_desc* d, int T, void* ws, size_t ws_bytes, int* host_flag, hipStream_t st);
-int llama_decode_begin(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st);
-int decode_graph_create(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st,
-                        teo_graph** out);
-
-size_t llama_decode_batch_workspace_bytes(const teo_llama_desc* d, int batch);
-int llama_decode_batch_begin(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes, hipStream_t st);
-int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes, hipStream_t st);
-int decode_batch_graph_create(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes,
-                              hipStream_t st, teo_graph** out);
-
-int llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st);
-int llama_decode_stream_arm(const teo_llama_desc* d, const teo_decode_stream_state* s, int slot, void* ws, size_t ws_bytes, hipStream_t st);
-int decode_stream_graph_create(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
-                               teo_graph** out);
-
-size_t llama_verify_workspace_bytes(const teo_llama_desc* d, int rows);
-int llama_verify_begin(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, hipStream_t st);
-int llama_verify_step(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, hipStream_t st);
-int llama_verify_step_profile(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, float* ms_out, int* count_out,
-                              hipStream_t st);
-int verify_graph_create(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, hipStream_t st, teo_graph** out);
-
 static bool dtype_ok(int dt) { return dt == TEO_F32 || dt == TEO_BF16 || dt == TEO_F16; }
 
 // the argument checks of the single-conversation decode step: teo_llama_decode_step, its profiled form and the guided forms of
@@ -107,6 +66,41 @@ int decode_state_check(const teo_llama_desc* d, const teo_decode_state* st, cons
         TEO_CHECK_ARG(st->d_rng && st->temperature > 0.f, "%s: null d_rng or temperature %g", who, st->temperature);
         const int rc = sampler_check(d->vocab, st->top_k, st->top_p); if (rc != TEO_OK) return rc;
     }
+    return TEO_OK;
+}
+
+// teo_llama_desc.prefill_w4 and the 16-bit layer pointers it makes optional: argument checks of every prefill entry (those of prefix.hip
+// and branches.hip too), before any launch
+int llama_prefill_check_weights(const teo_llama_desc* d) {
+    TEO_CHECK_ARG(!d->prefill_w4a8 || d->prefill_w4, "prefill: prefill_w4a8 is an option of prefill_w4 = 1");
+    if (!d->prefill_w4) {
+        TEO_CHECK_ARG(d->qkv_w && d->o_w && d->gateup_w && d->down_w,
+                      "prefill: the 16-bit qkv / o / gateup / down matrices are missing (a 4-bit-only descriptor needs prefill_w4 = 1)");
+        return TEO_OK;
+    }
+    TEO_CHECK_ARG(d->qkv_w4 && d->qkv_e4 && d->o_w4 && d->o_e4 && d->gateup_w4 && d->gateup_e4 && d->down_w4 && d->down_e4,
+                  "prefill: prefill_w4 needs all of qkv/o/gateup/down _w4 and _e4");
+    TEO_CHECK_ARG(!d->qkv_w8 && !d->o_w8 && !d->gateup_w8 && !d->down_w8 && !d->lm_head8,
+                  "prefill: a descriptor carries fp8 (w8) or MXFP4 (w4) weights, not both");
+    TEO_CHECK_ARG(d->dtype == TEO_BF16, "prefill: prefill_w4 needs bf16 activations");
+    TEO_CHECK_ARG(!d->prefill_fp8, "prefill: prefill_w4 and prefill_fp8 exclude each other");
+    if (d->hidden % 128 != 0 || d->inter % 128 != 0 || (d->heads * d->head_dim) % 128 != 0) {
+        set_error("prefill: prefill_w4 needs hidden %d, heads * head_dim %d and inter %d to be multiples of 128", d->hidden,
+                  d->heads * d->head_dim, d->inter);
+        return TEO_ERR_UNSUPPORTED;
+    }
+    if (d->prefill_w4a8 && (d->hidden > 12288 || d->inter > 12288 || d->heads * d->head_dim > 12288)) {
+        set_error("prefill: prefill_w4a8 quantises rows of at most 12288 elements (hidden %d, heads * head_dim %d, inter %d)", d->hidden,
+                  d->heads * d->head_dim, d->inter);
+        return TEO_ERR_UNSUPPORTED;
+    }
+    return TEO_OK;
+}
+
+// entry i of the slot list of teo_llama_prefill_slots / teo_llama_prefill_slots_past: in range, and not named by an earlier entry
+int prefill_slot_check(const int* slots, int i, const char* who) {
+    TEO_CHECK_ARG(slots[i] >= 0 && slots[i] < TEO_MAX_DECODE_BATCH, "%s: slots[%d] = %d outside 0..%d", who, i, slots[i], TEO_MAX_DECODE_BATCH - 1);
+    for (int j = 0; j < i; ++j) TEO_CHECK_ARG(slots[j] != slots[i], "%s: slot %d named twice", who, slots[i]);
     return TEO_OK;
 }
 
@@ -466,54 +460,29 @@ int teo_projector(const teo_proj_desc* d, const void* x, int rows, void* y, void
     return projector(d, x, rows, y, ws, wsb, ST(s));
 }
 
-// teo_llama_desc.prefill_w4 and the 16-bit layer pointers it makes optional: argument checks of every prefill entry, before any launch
-static int check_prefill_weights(const teo_llama_desc* d) {
-    TEO_CHECK_ARG(!d->prefill_w4a8 || d->prefill_w4, "prefill: prefill_w4a8 is an option of prefill_w4 = 1");
-    if (!d->prefill_w4) {
-        TEO_CHECK_ARG(d->qkv_w && d->o_w && d->gateup_w && d->down_w,
-                      "prefill: the 16-bit qkv / o / gateup / down matrices are missing (a 4-bit-only descriptor needs prefill_w4 = 1)");
-        return TEO_OK;
-    }
-    TEO_CHECK_ARG(d->qkv_w4 && d->qkv_e4 && d->o_w4 && d->o_e4 && d->gateup_w4 && d->gateup_e4 && d->down_w4 && d->down_e4,
-                  "prefill: prefill_w4 needs all of qkv/o/gateup/down _w4 and _e4");
-    TEO_CHECK_ARG(!d->qkv_w8 && !d->o_w8 && !d->gateup_w8 && !d->down_w8 && !d->lm_head8,
-                  "prefill: a descriptor carries fp8 (w8) or MXFP4 (w4) weights, not both");
-    TEO_CHECK_ARG(d->dtype == TEO_BF16, "prefill: prefill_w4 needs bf16 activations");
-    TEO_CHECK_ARG(!d->prefill_fp8, "prefill: prefill_w4 and prefill_fp8 exclude each other");
-    if (d->hidden % 128 != 0 || d->inter % 128 != 0 || (d->heads * d->head_dim) % 128 != 0) {
-        set_error("prefill: prefill_w4 needs hidden %d, heads * head_dim %d and inter %d to be multiples of 128", d->hidden,
-                  d->heads * d->head_dim, d->inter);
-        return TEO_ERR_UNSUPPORTED;
-    }
-    if (d->prefill_w4a8 && (d->hidden > 12288 || d->inter > 12288 || d->heads * d->head_dim > 12288)) {
-        set_error("prefill: prefill_w4a8 quantises rows of at most 12288 elements (hidden %d, heads * head_dim %d, inter %d)", d->hidden,
-                  d->heads * d->head_dim, d->inter);
-        return TEO_ERR_UNSUPPORTED;
-    }
-    return TEO_OK;
-}
-
 size_t teo_llama_prefill_workspace_bytes(const teo_llama_desc* d, int S) { return d ? llama_prefill_workspace_bytes(d, S) : 0; }
+// teo_llama_prefill and teo_llama_prefill_attentions (which has checked its `attentions`)
+static int prefill_entry(const char* who, const teo_llama_desc* d, const void* emb, const int* pos, int S, int past, int last_only, float* logits,
+                         void* ws, size_t wsb, teo_stream_t s, void* hidden_states, void* attentions) {
+    TuneScope tune_scope(d->tune);
+    TEO_CHECK_ARG(S >= 0 && past >= 0, "%s: S %d past %d", who, S, past);
+    if (S) {
+        TEO_CHECK_ARG(emb, "%s: null embeds", who); TEO_CHECK_ARG(logits, "%s: null logits", who); TEO_CHECK_ARG(ws, "%s: null workspace", who);
+    }
+    TEO_TRY(llama_prefill_check_weights(d));
+    return llama_prefill(d, emb, pos, S, past, last_only, logits, ws, wsb, ST(s), hidden_states, attentions, who);
+}
 int teo_llama_prefill(const teo_llama_desc* d, const void* emb, const int* pos, int S, int past, int last_only,
                       float* logits, void* ws, size_t wsb, teo_stream_t s, void* hidden_states) {
     ENTER();
     NEED(d, "desc"); NEED_DT(d->dtype);
-    TuneScope tune_scope(d->tune);
-    TEO_CHECK_ARG(S >= 0 && past >= 0, "teo_llama_prefill: S %d past %d", S, past);
-    if (S) { NEED(emb, "embeds"); NEED(logits, "logits"); NEED(ws, "workspace"); }
-    { const int rc = check_prefill_weights(d); if (rc != TEO_OK) return rc; }
-    return llama_prefill(d, emb, pos, S, past, last_only, logits, ws, wsb, ST(s), hidden_states, nullptr);
+    return prefill_entry(__func__, d, emb, pos, S, past, last_only, logits, ws, wsb, s, hidden_states, nullptr);
 }
-
 int teo_llama_prefill_attentions(const teo_llama_desc* d, const void* emb, const int* pos, int S, int past, int last_only,
                                  float* logits, void* ws, size_t wsb, teo_stream_t s, void* hidden_states, void* attentions) {
     ENTER();
     NEED(d, "desc"); NEED_DT(d->dtype); NEED(attentions, "attentions");
-    TuneScope tune_scope(d->tune);
-    TEO_CHECK_ARG(S >= 0 && past >= 0, "teo_llama_prefill_attentions: S %d past %d", S, past);
-    if (S) { NEED(emb, "embeds"); NEED(logits, "logits"); NEED(ws, "workspace"); }
-    { const int rc = check_prefill_weights(d); if (rc != TEO_OK) return rc; }
-    return llama_prefill(d, emb, pos, S, past, last_only, logits, ws, wsb, ST(s), hidden_states, attentions);
+    return prefill_entry(__func__, d, emb, pos, S, past, last_only, logits, ws, wsb, s, hidden_states, attentions);
 }
 
 int teo_llama_prefill_batch(const teo_llama_desc* d, const void* emb, const int* seq_lens, int nseq, long long cache_stride,
@@ -524,8 +493,8 @@ int teo_llama_prefill_batch(const teo_llama_desc* d, const void* emb, const int*
     TEO_CHECK_ARG(nseq >= 0 && (nseq <= 1 || cache_stride > 0), "teo_llama_prefill_batch: nseq %d cache_stride %lld", nseq, cache_stride);
     if (nseq == 0) return TEO_OK;
     NEED(emb, "embeds"); NEED(logits, "logits"); NEED(ws, "workspace");
-    { const int rc = check_prefill_weights(d); if (rc != TEO_OK) return rc; }
-    return llama_prefill_batch(d, emb, seq_lens, nseq, cache_stride, last_only, logits, ws, wsb, ST(s), hidden_states);
+    TEO_TRY(llama_prefill_check_weights(d));
+    return llama_prefill_batch(d, emb, seq_lens, nseq, cache_stride, last_only, logits, ws, wsb, ST(s), hidden_states, __func__);
 }
 
 int teo_llama_prefill_slots(const teo_llama_desc* d, const void* emb, const int* seq_lens, const int* slots, int nseq, long long cache_stride,
@@ -536,14 +505,10 @@ int teo_llama_prefill_slots(const teo_llama_desc* d, const void* emb, const int*
     TEO_CHECK_ARG(nseq >= 0 && nseq <= TEO_MAX_DECODE_BATCH && cache_stride > 0, "teo_llama_prefill_slots: nseq %d cache_stride %lld", nseq,
                   cache_stride);
     if (nseq == 0) return TEO_OK;
-    for (int i = 0; i < nseq; ++i) {
-        TEO_CHECK_ARG(slots[i] >= 0 && slots[i] < TEO_MAX_DECODE_BATCH, "teo_llama_prefill_slots: slots[%d] = %d outside 0..%d", i, slots[i],
-                      TEO_MAX_DECODE_BATCH - 1);
-        for (int j = 0; j < i; ++j) TEO_CHECK_ARG(slots[j] != slots[i], "teo_llama_prefill_slots: slot %d named twice", slots[i]);
-    }
+    for (int i = 0; i < nseq; ++i) TEO_TRY(prefill_slot_check(slots, i, __func__));
     NEED(emb, "embeds"); NEED(logits, "logits"); NEED(ws, "workspace");
-    { const int rc = check_prefill_weights(d); if (rc != TEO_OK) return rc; }
-    return llama_prefill_batch(d, emb, seq_lens, nseq, cache_stride, last_only, logits, ws, wsb, ST(s), hidden_states, slots);
+    TEO_TRY(llama_prefill_check_weights(d));
+    return llama_prefill_batch(d, emb, seq_lens, nseq, cache_stride, last_only, logits, ws, wsb, ST(s), hidden_states, __func__, slots);
 }
 
 size_t teo_llama_decode_workspace_bytes(const teo_llama_desc* d) { return d ? llama_decode_workspace_bytes(d) : 0; }
@@ -895,9 +860,6 @@ int teo_gemm_skinny_w4(const void* x, const void* W4, const void* e8m0, const vo
 }
 
 }  // extern "C"
-
-// the prefill entry points of the second header (include/teo_hip_prefix.h, prefix.hip) run the same weight checks
-int teo::llama_prefill_check_weights(const teo_llama_desc* d) { return check_prefill_weights(d); }
 
 namespace teo {
 // the stream step's argument checks for the guided entry points (guide.hip)

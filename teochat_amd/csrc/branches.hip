@@ -18,14 +18,10 @@
 #include <string.h>
 
 #include "common.h"
-#include "ops.h"
+#include "runtime.h"
 #include "../../include/teo_hip_score.h"
 
 namespace teo {
-
-int llama_prefill_branches(const teo_llama_desc* d, const void* embeds, const int* positions, const int* branch_start, int S, int past,
-                           float* logits, void* ws, size_t ws_bytes, hipStream_t st);      // runtime.hip
-int llama_prefill_check_weights(const teo_llama_desc* d);                                    // abi.hip
 
 typedef __attribute__((ext_vector_type(8))) short br_h16x8;
 typedef __attribute__((ext_vector_type(16))) float br_f32x16;
@@ -429,7 +425,7 @@ int teo_llama_prefill_branches(const teo_llama_desc* d, const void* emb, const i
     TEO_CHECK_ARG(S >= 1 && past >= 0 && past <= d->max_seq - S, "teo_llama_prefill_branches: S %d past %d outside max_seq %d", S, past,
                   d->max_seq);
     TEO_CHECK_ARG(emb && pos && branch_start && logits && ws, "teo_llama_prefill_branches: null embeds / positions / branch_start / logits / workspace");
-    { const int rc = llama_prefill_check_weights(d); if (rc != TEO_OK) return rc; }
+    TEO_TRY(llama_prefill_check_weights(d));
     return llama_prefill_branches(d, emb, pos, branch_start, S, past, logits, ws, wsb, (hipStream_t)s);
 }
 

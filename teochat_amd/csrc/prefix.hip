@@ -1,13 +1,8 @@
 // Prefix reuse for the stream decoder (include/teo_hip_prefix.h): the KV fork kernel and the two entry points of the second header.
-#include "ops.h"
+#include "runtime.h"
 #include "../../include/teo_hip_prefix.h"
 
 namespace teo {
-
-int llama_prefill_batch(const teo_llama_desc* d, const void* embeds, const int* seq_lens, int nseq, long long cache_stride,
-                        int last_only, float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, const int* slots,
-                        const int* pasts);
-int llama_prefill_check_weights(const teo_llama_desc* d);       // abi.hip: the weight checks every prefill entry point runs
 
 // ---- teo_kv_fork -------------------------------------------------------------------------------------------------------------------
 // A slot's cache is, per layer, three arrays of RUNS: K and V hold one run of rows * head_dim elements per KV head (head stride
@@ -121,15 +116,13 @@ int teo_llama_prefill_slots_past(const teo_llama_desc* d, const void* emb, const
                   cache_stride);
     if (nseq == 0) return TEO_OK;
     for (int i = 0; i < nseq; ++i) {
-        TEO_CHECK_ARG(slots[i] >= 0 && slots[i] < TEO_MAX_DECODE_BATCH, "teo_llama_prefill_slots_past: slots[%d] = %d outside 0..%d", i, slots[i],
-                      TEO_MAX_DECODE_BATCH - 1);
-        for (int j = 0; j < i; ++j) TEO_CHECK_ARG(slots[j] != slots[i], "teo_llama_prefill_slots_past: slot %d named twice", slots[i]);
+        TEO_TRY(prefill_slot_check(slots, i, __func__));
         TEO_CHECK_ARG(seq_lens[i] >= 1 && pasts[i] >= 0 && pasts[i] <= d->max_seq - seq_lens[i],
                       "teo_llama_prefill_slots_past: pasts[%d] = %d + seq_lens[%d] = %d outside 0..max_seq %d", i, pasts[i], i, seq_lens[i], d->max_seq);
     }
     TEO_CHECK_ARG(emb && logits && ws, "teo_llama_prefill_slots_past: null embeds / logits / workspace");
-    { const int rc = llama_prefill_check_weights(d); if (rc != TEO_OK) return rc; }
-    return llama_prefill_batch(d, emb, seq_lens, nseq, cache_stride, last_only, logits, ws, wsb, (hipStream_t)s, hidden_states, slots, pasts);
+    TEO_TRY(llama_prefill_check_weights(d));
+    return llama_prefill_batch(d, emb, seq_lens, nseq, cache_stride, last_only, logits, ws, wsb, (hipStream_t)s, hidden_states, __func__, slots, pasts);
 }
 
 int teo_kv_fork(const teo_llama_desc* d, int src_slot, const int* dst_slots, int n_dst, int rows, long long cache_stride, teo_stream_t s) {

@@ -4,7 +4,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "ops.h"
+#include "runtime.h"
 #include "guide_dev.h"
 
 namespace teo {
@@ -19,12 +19,6 @@ struct Carver {
     }
     bool ok() const { return off <= cap; }
 };
-
-#define TEO_TRY(expr)                  \
-    do {                               \
-        int rc__ = (expr);             \
-        if (rc__ != TEO_OK) return rc__; \
-    } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // ViT
@@ -167,64 +161,6 @@ static PrefillWs prefill_carve(const teo_llama_desc* d, int S, void* ws, size_t 
     return w;
 }
 
-// prefill Linear layers on the fp8 MFMA (activations quantised per token, the decode path's e4m3 weights): the descriptor's
-// `prefill_fp8` option -- lossy w8a8, selectable per engine, never a default
-static bool prefill_uses_fp8(const teo_llama_desc* d) {
-    const int Hq = d->heads * d->head_dim;
-    return d->prefill_fp8 && d->dtype == TEO_BF16 && d->qkv_w8 && d->o_w8 && d->gateup_w8 && d->down_w8 && d->hidden % 128 == 0 &&
-           d->inter % 128 == 0 && Hq % 128 == 0 && d->inter <= 12288 && d->hidden <= 12288;
-}
-// one decoder layer's four Linear layers in w8a8 form; `attend` runs RoPE / KV append / attention on w.qkv -> w.attn
-template <typename F>
-static int prefill_layer_fp8(const teo_llama_desc* d, const PrefillWs& w, int l, int S, F attend, hipStream_t st) {
-    const int dt = d->dtype;
-    const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim, Fi = d->inter;
-    const int QKV = (H + 2 * Hk) * hd;
-    TEO_TRY(quant_rows_fp8(w.h, d->in_norm_w[l], w.q8, w.qs, S, D, D, d->eps, st));
-    TEO_TRY(gemm_fp8(w.q8, w.qs, d->qkv_w8[l], d->qkv_s[l], nullptr, w.qkv, S, QKV, D, D, QKV, 0, dt, st));
-    TEO_TRY(attend());
-    TEO_TRY(quant_rows_fp8(w.attn, nullptr, w.q8, w.qs, S, H * hd, H * hd, d->eps, st));
-    TEO_TRY(gemm_fp8(w.q8, w.qs, d->o_w8[l], d->o_s[l], w.h, w.h, S, D, H * hd, H * hd, D, 0, dt, st, w.sk));
-    TEO_TRY(quant_rows_fp8(w.h, d->post_norm_w[l], w.q8, w.qs, S, D, D, d->eps, st));
-    TEO_TRY(gemm_fp8(w.q8, w.qs, d->gateup_w8[l], d->gateup_s[l], nullptr, w.act, S, 2 * Fi, D, D, Fi, TEO_GEMM_SWIGLU16, dt, st));
-    TEO_TRY(quant_rows_fp8(w.act, nullptr, w.q8, w.qs, S, Fi, Fi, d->eps, st));
-    return gemm_fp8(w.q8, w.qs, d->down_w8[l], d->down_s[l], w.h, w.h, S, D, Fi, Fi, D, 0, dt, st, w.sk);
-}
-
-// one decoder layer's four Linear layers on the MXFP4 prefill GEMM (gemm_w4.hip; the descriptor's `prefill_w4` option, checked by the C
-// entry points): the row-major *_w4 / *_e4 arrays, the bits of the bf16 GEMMs on the dequantised matrices.  The 16-bit pointers are not read
-template <typename F>
-static int prefill_layer_w4(const teo_llama_desc* d, const PrefillWs& w, int l, int S, F attend, hipStream_t st) {
-    const int dt = d->dtype;
-    const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim, Fi = d->inter;
-    const int QKV = (H + 2 * Hk) * hd;
-    TEO_TRY(rmsnorm(w.h, d->in_norm_w[l], w.n, S, D, d->eps, dt, st));
-    TEO_TRY(gemm_w4(w.n, d->qkv_w4[l], d->qkv_e4[l], nullptr, w.qkv, S, QKV, D, D, QKV, 0, dt, st));
-    TEO_TRY(attend());
-    TEO_TRY(gemm_w4(w.attn, d->o_w4[l], d->o_e4[l], w.h, w.h, S, D, H * hd, H * hd, D, 0, dt, st));
-    TEO_TRY(rmsnorm(w.h, d->post_norm_w[l], w.n, S, D, d->eps, dt, st));
-    TEO_TRY(gemm_w4(w.n, d->gateup_w4[l], d->gateup_e4[l], nullptr, w.act, S, 2 * Fi, D, D, Fi, TEO_GEMM_SWIGLU16, dt, st));
-    return gemm_w4(w.act, d->down_w4[l], d->down_e4[l], w.h, w.h, S, D, Fi, Fi, D, 0, dt, st);
-}
-
-// the same four Linear layers in w4a8 form (gemm_w4a8.hip; `prefill_w4a8` on top of `prefill_w4`, lossy, never a default): the order of
-// prefill_layer_fp8 -- RMSNorm fused into the quantiser for qkv and gate/up -- on the row-major *_w4 / *_e4 arrays, q8 / qs of the workspace
-template <typename F>
-static int prefill_layer_w4a8(const teo_llama_desc* d, const PrefillWs& w, int l, int S, F attend, hipStream_t st) {
-    const int dt = d->dtype;
-    const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim, Fi = d->inter;
-    const int QKV = (H + 2 * Hk) * hd;
-    TEO_TRY(quant_rows_fp8(w.h, d->in_norm_w[l], w.q8, w.qs, S, D, D, d->eps, st));
-    TEO_TRY(gemm_w4a8(w.q8, w.qs, d->qkv_w4[l], d->qkv_e4[l], nullptr, w.qkv, S, QKV, D, D, QKV, 0, dt, st));
-    TEO_TRY(attend());
-    TEO_TRY(quant_rows_fp8(w.attn, nullptr, w.q8, w.qs, S, H * hd, H * hd, d->eps, st));
-    TEO_TRY(gemm_w4a8(w.q8, w.qs, d->o_w4[l], d->o_e4[l], w.h, w.h, S, D, H * hd, H * hd, D, 0, dt, st));
-    TEO_TRY(quant_rows_fp8(w.h, d->post_norm_w[l], w.q8, w.qs, S, D, D, d->eps, st));
-    TEO_TRY(gemm_w4a8(w.q8, w.qs, d->gateup_w4[l], d->gateup_e4[l], nullptr, w.act, S, 2 * Fi, D, D, Fi, TEO_GEMM_SWIGLU16, dt, st));
-    TEO_TRY(quant_rows_fp8(w.act, nullptr, w.q8, w.qs, S, Fi, Fi, d->eps, st));
-    return gemm_w4a8(w.q8, w.qs, d->down_w4[l], d->down_e4[l], w.h, w.h, S, D, Fi, Fi, D, 0, dt, st);
-}
-
 size_t llama_prefill_workspace_bytes(const teo_llama_desc* d, int S) { return prefill_carve(d, S, nullptr, 0).total; }
 // sticky hand-off error word of the GEMM workspace inside a prefill / tower workspace (0 = fine); synchronises the stream
 int llama_prefill_workspace_status(const teo_llama_desc* d, int S, void* ws, size_t ws_bytes, int* host_flag, hipStream_t st) {
@@ -238,6 +174,61 @@ int vit_workspace_status(const teo_vit_desc* d, int T, void* ws, size_t ws_bytes
     return gemm_sk_workspace_status(w.sk, host_flag, st);
 }
 
+// prefill Linear layers on the fp8 MFMA (activations quantised per token, the decode path's e4m3 weights): the descriptor's
+// `prefill_fp8` option -- lossy w8a8, selectable per engine, never a default.  Where these shape conditions fail the option is quietly
+// ignored: the pass runs the 16-bit GEMMs
+static bool prefill_uses_fp8(const teo_llama_desc* d) {
+    const int Hq = d->heads * d->head_dim;
+    return d->prefill_fp8 && d->dtype == TEO_BF16 && d->qkv_w8 && d->o_w8 && d->gateup_w8 && d->down_w8 && d->hidden % 128 == 0 &&
+           d->inter % 128 == 0 && Hq % 128 == 0 && d->inter <= 12288 && d->hidden <= 12288;
+}
+
+// One decoder layer on the residual stream w.h over the S rows of a pass; `attend` runs RoPE / KV append / attention on w.qkv -> w.attn.
+// Its four Linear layers take the form the descriptor selects:
+//   16-bit : RMSNorm -> gemm on the *_w matrices
+//   w4     : RMSNorm -> gemm_w4 on the row-major MXFP4 *_w4 / *_e4 arrays (`prefill_w4`, checked by the C entry points): the bits of the
+//            16-bit GEMMs on the dequantised matrices; the 16-bit pointers are not read
+//   fp8    : quant_rows_fp8 (the norm fused into the quantiser) -> gemm_fp8 on the *_w8 / *_s copies; q8 / qs of the workspace
+//   w4a8   : the same order -> gemm_w4a8 on the *_w4 / *_e4 arrays (`prefill_w4a8` on top of `prefill_w4`, lossy, never a default)
+enum PrefillMode { PF_W16, PF_W4, PF_FP8, PF_W4A8 };
+static PrefillMode prefill_mode(const teo_llama_desc* d) {
+    return prefill_uses_fp8(d) ? PF_FP8 : (d->prefill_w4 ? (d->prefill_w4a8 ? PF_W4A8 : PF_W4) : PF_W16);
+}
+struct LinearForms {        // the per-layer arrays of one Linear layer in every weight format (those its mode does not use may be null)
+    const void* const* w16; const void* const* w8; const float* const* s8; const void* const* w4; const uint8_t* const* e4;
+};
+#define TEO_LINEAR_FORMS(n) LinearForms{d->n##_w, d->n##_w8, d->n##_s, d->n##_w4, d->n##_e4}
+
+template <typename F>
+static int prefill_layer(const teo_llama_desc* d, const PrefillWs& w, PrefillMode mode, int l, int S, F attend, hipStream_t st) {
+    const int dt = d->dtype, D = d->hidden, Hq = d->heads * d->head_dim, QKV = Hq + 2 * d->kv_heads * d->head_dim, Fi = d->inter;
+    const bool a8 = mode == PF_FP8 || mode == PF_W4A8;
+    // out[S, N] = x[S, K] . W^T (+ res); x is w.q8 / w.qs in the a8 modes.  The stream-K workspace goes to every 16-bit GEMM, to the fp8
+    // GEMM of o and down only and to no MXFP4 GEMM: the planners choose by it
+    auto matmul = [&](const void* x, const LinearForms& f, const void* res, void* out, int N, int K, int ldc, unsigned flags) -> int {
+        switch (mode) {
+        case PF_FP8: return gemm_fp8(w.q8, w.qs, f.w8[l], f.s8[l], res, out, S, N, K, K, ldc, flags, dt, st, res ? w.sk : nullptr);
+        case PF_W4A8: return gemm_w4a8(w.q8, w.qs, f.w4[l], f.e4[l], res, out, S, N, K, K, ldc, flags, dt, st);
+        case PF_W4: return gemm_w4(x, f.w4[l], f.e4[l], res, out, S, N, K, K, ldc, flags, dt, st);
+        default: return gemm(x, f.w16[l], nullptr, res, out, S, N, K, K, ldc, TEO_ACT_NONE, flags, dt, dt, st, w.sk);
+        }
+    };
+    auto project_normed = [&](const void* norm_w, const LinearForms& f, void* out, int N, int ldc, unsigned flags) -> int {   // out = Linear(RMSNorm(w.h))
+        if (a8) TEO_TRY(quant_rows_fp8(w.h, norm_w, w.q8, w.qs, S, D, D, d->eps, st));
+        else TEO_TRY(rmsnorm(w.h, norm_w, w.n, S, D, d->eps, dt, st));
+        return matmul(w.n, f, nullptr, out, N, D, ldc, flags);
+    };
+    auto project_residual = [&](const void* x, const LinearForms& f, int K) -> int {                                             // w.h += Linear(x)
+        if (a8) TEO_TRY(quant_rows_fp8(x, nullptr, w.q8, w.qs, S, K, K, d->eps, st));
+        return matmul(x, f, w.h, w.h, D, K, D, 0);
+    };
+    TEO_TRY(project_normed(d->in_norm_w[l], TEO_LINEAR_FORMS(qkv), w.qkv, QKV, QKV, 0));
+    TEO_TRY(attend());
+    TEO_TRY(project_residual(w.attn, TEO_LINEAR_FORMS(o), Hq));
+    TEO_TRY(project_normed(d->post_norm_w[l], TEO_LINEAR_FORMS(gateup), w.act, 2 * Fi, Fi, TEO_GEMM_SWIGLU16));
+    return project_residual(w.act, TEO_LINEAR_FORMS(down), Fi);
+}
+
 // hidden_states (optional, `output_hidden_states` of the kept forward signature, llava_llama.py:56-69): [layers + 1][S][hidden] in the model
 // dtype -- snapshot 0 = the input embeddings, l = the residual stream after layer l - 1, the last one AFTER the final RMSNorm (what
 // LlamaModel.forward collects: lm_head(hidden_states[-1]) == logits)
@@ -247,181 +238,126 @@ static int snapshot_rows(void* hs, int idx, const void* src, int S, int D, size_
     return he == hipSuccess ? TEO_OK : hip_fail(he, "prefill: hidden-state snapshot");
 }
 
+// causal attention of the q_len rows of `qkv` (row stride: the fused QKV width) over one conversation's K / V / V^T cache of kv_len keys
+static teo_attn_args cache_attn_args(const teo_llama_desc* d, const void* qkv, const void* kc, const void* vc, const void* vtc, void* out,
+                                     int q_len, int kv_len) {
+    const int H = d->heads, Hk = d->kv_heads, hd = d->head_dim;
+    teo_attn_args a;
+    memset(&a, 0, sizeof(a));
+    a.q = qkv; a.k = kc; a.v = vc; a.vt = vtc; a.o = out;
+    a.q_bs = 0; a.q_hs = hd; a.q_rs = (H + 2 * Hk) * hd;
+    a.k_bs = 0; a.k_hs = (long long)d->max_seq * hd; a.k_rs = hd;
+    a.v_bs = 0; a.v_hs = (long long)d->max_seq * hd; a.v_rs = hd;
+    a.vt_bs = 0; a.vt_hs = (long long)hd * d->max_seq; a.vt_rs = d->max_seq;
+    a.o_bs = 0; a.o_rs = (long long)H * hd;
+    a.batch = 1; a.heads = H; a.kv_heads = Hk; a.head_dim = hd; a.q_len = q_len; a.kv_len = kv_len;
+    a.causal = 1;
+    a.scale = 1.0f / sqrtf((float)hd);
+    return a;
+}
+
+// One prefill pass, the walk of every prefill entry point (`who`, for the error text): the rows of nseq sequences, packed one behind the
+// other, so that the norms and the GEMMs run once over all of them (better tile quantisation than nseq separate problems); RoPE + KV
+// append and the causal attention run per sequence on its row block and its own cache.
+// logits: [nseq, vocab] with last_only (the last row of every sequence), else [rows, vocab].  For ONE sequence only:
+// positions (optional): the RoPE positions of the rows; NULL = past, past + 1, ...
 // attentions (optional, `output_attentions` of the kept forward signature, llava_llama.py:65,95): [layers][heads][S][past + S] in the model dtype
 // branch_start (optional, include/teo_hip_score.h): the S rows are packed branches of the cached prefix -- the attention is attn_branches
-static int llama_prefill_rows(const teo_llama_desc* d, const void* embeds, const int* positions, int S, int past, int last_only,
-                              float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, void* attentions,
-                              const int* branch_start) {
-    if (S == 0) return TEO_OK;
-    TEO_CHECK_ARG(past + S <= d->max_seq, "teo_llama_prefill: past %d + S %d exceeds max_seq %d", past, S, d->max_seq);
+struct PrefillSeq {
+    int len, past;          // rows of this sequence, appended at positions past .. behind what its cache already holds
+    size_t cache_off;       // bytes from every layer's k / v / vt cache pointer to this sequence's slot
+};
+
+static int prefill_pass(const teo_llama_desc* d, const char* who, const PrefillSeq* seqs, int nseq, const void* embeds, const int* positions,
+                        int last_only, float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, void* attentions,
+                        const int* branch_start) {
+    TEO_CHECK_ARG(nseq == 1 || (!positions && !attentions && !branch_start), "%s: positions / attentions / branch_start take one sequence, not %d",
+                  who, nseq);
+    int S = 0;
+    for (int b = 0; b < nseq; ++b) {
+        TEO_CHECK_ARG(seqs[b].len >= 1 && seqs[b].len <= d->max_seq && seqs[b].past <= d->max_seq - seqs[b].len,
+                      "%s: sequence %d: past %d + rows %d outside 1..max_seq %d", who, b, seqs[b].past, seqs[b].len, d->max_seq);
+        S += seqs[b].len;
+    }
     const PrefillWs w = prefill_carve(d, S, ws, ws_bytes);
     if (w.total > ws_bytes) {
-        set_error("teo_llama_prefill: workspace %zu < %zu", ws_bytes, w.total);
+        set_error("%s: workspace %zu < %zu", who, ws_bytes, w.total);
         return TEO_ERR_WORKSPACE;
     }
     const int dt = d->dtype;
     const size_t e = esize(dt);
-    const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim, F = d->inter;
+    const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim;
     const int QKV = (H + 2 * Hk) * hd;
     hipError_t he = hipMemcpyAsync(w.h, embeds, (size_t)S * D * e, hipMemcpyDeviceToDevice, st);
     if (he != hipSuccess) return hip_fail(he, "prefill copy embeds");
     TEO_TRY(gemm_sk_workspace_init(w.sk, st));
     TEO_TRY(snapshot_rows(hidden_states, 0, w.h, S, D, e, st));
-    const bool fp8 = prefill_uses_fp8(d);
+    const PrefillMode mode = prefill_mode(d);
     for (int l = 0; l < d->layers; ++l) {
         if (l > 0) TEO_TRY(snapshot_rows(hidden_states, l, w.h, S, D, e, st));         // the residual stream after layer l - 1
         auto attend = [&]() -> int {
-        TEO_TRY(rope_kv_append(w.qkv, QKV, positions, d->rope_cos, d->rope_sin, d->k_cache[l], d->v_cache[l],
-                               d->vt_cache[l], S, past, nullptr, d->max_seq, H, Hk, hd, dt, st));
-        teo_attn_args a;
-        memset(&a, 0, sizeof(a));
-        a.q = w.qkv; a.k = d->k_cache[l]; a.v = d->v_cache[l]; a.vt = d->vt_cache[l]; a.o = w.attn;
-        a.q_bs = 0; a.q_hs = hd; a.q_rs = QKV;
-        a.k_bs = 0; a.k_hs = (long long)d->max_seq * hd; a.k_rs = hd;
-        a.v_bs = 0; a.v_hs = (long long)d->max_seq * hd; a.v_rs = hd;
-        a.vt_bs = 0; a.vt_hs = (long long)hd * d->max_seq; a.vt_rs = d->max_seq;
-        a.o_bs = 0; a.o_rs = (long long)H * hd;
-        a.batch = 1; a.heads = H; a.kv_heads = Hk; a.head_dim = hd; a.q_len = S; a.kv_len = past + S;
-        a.causal = 1;
-        a.scale = 1.0f / sqrtf((float)hd);
-        if (attentions)      // the maps of this layer, from the operands the attention kernel is about to read (rotated q, cached k)
-            TEO_TRY(attention_probs(&a, dt, (unsigned char*)attentions + (size_t)l * H * S * (size_t)(past + S) * e, st));
-        return branch_start ? attn_branches(&a, branch_start, dt, st) : attention(&a, dt, st);
+            int row0 = 0;
+            for (int b = 0; b < nseq; ++b) {
+                const PrefillSeq& q = seqs[b];
+                unsigned char* qkv_b = (unsigned char*)w.qkv + (size_t)row0 * QKV * e;
+                unsigned char* kc = (unsigned char*)d->k_cache[l] + q.cache_off;
+                unsigned char* vc = (unsigned char*)d->v_cache[l] + q.cache_off;
+                unsigned char* vtc = (unsigned char*)d->vt_cache[l] + q.cache_off;
+                TEO_TRY(rope_kv_append(qkv_b, QKV, positions, d->rope_cos, d->rope_sin, kc, vc, vtc, q.len, q.past, nullptr, d->max_seq, H, Hk,
+                                       hd, dt, st));
+                const teo_attn_args a = cache_attn_args(d, qkv_b, kc, vc, vtc, (unsigned char*)w.attn + (size_t)row0 * H * hd * e, q.len,
+                                                        q.past + q.len);
+                if (attentions)      // the maps of this layer, from the operands the attention kernel is about to read (rotated q, cached k)
+                    TEO_TRY(attention_probs(&a, dt, (unsigned char*)attentions + (size_t)l * H * S * (size_t)(q.past + S) * e, st));
+                TEO_TRY(branch_start ? attn_branches(&a, branch_start, dt, st) : attention(&a, dt, st));
+                row0 += q.len;
+            }
+            return TEO_OK;
         };
-        if (fp8) {
-            TEO_TRY(prefill_layer_fp8(d, w, l, S, attend, st));
-            continue;
-        }
-        if (d->prefill_w4 && d->prefill_w4a8) {
-            TEO_TRY(prefill_layer_w4a8(d, w, l, S, attend, st));
-            continue;
-        }
-        if (d->prefill_w4) {
-            TEO_TRY(prefill_layer_w4(d, w, l, S, attend, st));
-            continue;
-        }
-        TEO_TRY(rmsnorm(w.h, d->in_norm_w[l], w.n, S, D, d->eps, dt, st));
-        TEO_TRY(gemm(w.n, d->qkv_w[l], nullptr, nullptr, w.qkv, S, QKV, D, D, QKV, TEO_ACT_NONE, 0, dt, dt, st, w.sk));
-        TEO_TRY(attend());
-        TEO_TRY(gemm(w.attn, d->o_w[l], nullptr, w.h, w.h, S, D, H * hd, H * hd, D, TEO_ACT_NONE, 0, dt, dt, st, w.sk));
-        TEO_TRY(rmsnorm(w.h, d->post_norm_w[l], w.n, S, D, d->eps, dt, st));
-        TEO_TRY(gemm(w.n, d->gateup_w[l], nullptr, nullptr, w.act, S, 2 * F, D, D, F, TEO_ACT_NONE, TEO_GEMM_SWIGLU16, dt, dt, st, w.sk));
-        TEO_TRY(gemm(w.act, d->down_w[l], nullptr, w.h, w.h, S, D, F, F, D, TEO_ACT_NONE, 0, dt, dt, st, w.sk));
+        TEO_TRY(prefill_layer(d, w, mode, l, S, attend, st));
     }
     if (last_only) {
         if (hidden_states) TEO_TRY(rmsnorm(w.h, d->final_norm_w, (unsigned char*)hidden_states + (size_t)d->layers * S * D * e, S, D, d->eps, dt, st));
-        const void* hl = (const unsigned char*)w.h + (size_t)(S - 1) * D * e;
-        return gemv(hl, d->lm_head, d->final_norm_w, nullptr, logits, d->vocab, D, d->eps, 0, dt, TEO_F32, st);
+        int row_end = 0;
+        for (int b = 0; b < nseq; ++b) {
+            row_end += seqs[b].len;
+            const void* hl = (const unsigned char*)w.h + (size_t)(row_end - 1) * D * e;
+            TEO_TRY(gemv(hl, d->lm_head, d->final_norm_w, nullptr, logits + (size_t)b * d->vocab, d->vocab, D, d->eps, 0, dt, TEO_F32, st));
+        }
+        return TEO_OK;
     }
-    TEO_TRY(rmsnorm(w.h, d->final_norm_w, w.n, S, D, d->eps, dt, st));
+    TEO_TRY(rmsnorm(w.h, d->final_norm_w, w.n, S, D, d->eps, dt, st));          // training-shape forward: logits of every row
     TEO_TRY(snapshot_rows(hidden_states, d->layers, w.n, S, D, e, st));
     return gemm(w.n, d->lm_head, nullptr, nullptr, logits, S, d->vocab, D, D, d->vocab, TEO_ACT_NONE, 0, dt, TEO_F32, st, w.sk);
 }
 
-int llama_prefill(const teo_llama_desc* d, const void* embeds, const int* positions, int S, int past, int last_only,
-                  float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, void* attentions) {
-    return llama_prefill_rows(d, embeds, positions, S, past, last_only, logits, ws, ws_bytes, st, hidden_states, attentions, nullptr);
+// one conversation in the descriptor's own cache
+int llama_prefill(const teo_llama_desc* d, const void* embeds, const int* positions, int S, int past, int last_only, float* logits, void* ws,
+                  size_t ws_bytes, hipStream_t st, void* hidden_states, void* attentions, const char* who) {
+    if (S == 0) return TEO_OK;
+    const PrefillSeq one = {S, past, 0};
+    return prefill_pass(d, who, &one, 1, embeds, positions, last_only, logits, ws, ws_bytes, st, hidden_states, attentions, nullptr);
 }
-
 int llama_prefill_branches(const teo_llama_desc* d, const void* embeds, const int* positions, const int* branch_start, int S, int past,
                            float* logits, void* ws, size_t ws_bytes, hipStream_t st) {
-    return llama_prefill_rows(d, embeds, positions, S, past, 0, logits, ws, ws_bytes, st, nullptr, nullptr, branch_start);
+    if (S == 0) return TEO_OK;
+    const PrefillSeq one = {S, past, 0};
+    return prefill_pass(d, "teo_llama_prefill_branches", &one, 1, embeds, positions, 0, logits, ws, ws_bytes, st, nullptr, nullptr, branch_start);
 }
 
-// Multi-sequence prefill (batched generate): the rows of nseq new conversations are concatenated so the norms and the
-// GEMMs run once over sum(S_b) rows (better tile quantisation than nseq separate M = S_b problems); RoPE + KV append and
-// the causal attention run per sequence on its row block and its own cache slot (slot b = cache pointer + b*cache_stride
-// elements, fresh caches: past = 0).  logits [nseq, vocab]: last position of every sequence.
+// Multi-sequence prefill (batched generate): sequence b goes into cache slot b (slot = cache pointer + b * cache_stride elements) at
+// past = 0.
 // slots != NULL (teo_llama_prefill_slots): sequence i goes into cache slot slots[i] instead of slot i -- the refill pass of the stream
 // decoder, every slot freed in a round in one pass over the weights.
 // pasts != NULL (teo_llama_prefill_slots_past, include/teo_hip_prefix.h): sequence i's rows are appended at positions pasts[i] .. behind
-// what its slot already holds (RoPE, KV rows and kv_len as llama_prefill's `past`); the entry point has checked the bounds.
-int llama_prefill_batch(const teo_llama_desc* d, const void* embeds, const int* seq_lens, int nseq, long long cache_stride,
-                        int last_only, float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, const int* slots,
+// what its slot already holds (RoPE, KV rows and kv_len as llama_prefill's `past`).
+int llama_prefill_batch(const teo_llama_desc* d, const void* embeds, const int* seq_lens, int nseq, long long cache_stride, int last_only,
+                        float* logits, void* ws, size_t ws_bytes, hipStream_t st, void* hidden_states, const char* who, const int* slots,
                         const int* pasts) {
-    int total = 0;
-    for (int b = 0; b < nseq; ++b) {
-        TEO_CHECK_ARG(seq_lens[b] >= 1 && seq_lens[b] <= d->max_seq, "teo_llama_prefill_batch: seq_lens[%d] = %d", b, seq_lens[b]);
-        total += seq_lens[b];
-    }
-    const PrefillWs w = prefill_carve(d, total, ws, ws_bytes);
-    if (w.total > ws_bytes) {
-        set_error("teo_llama_prefill_batch: workspace %zu < %zu", ws_bytes, w.total);
-        return TEO_ERR_WORKSPACE;
-    }
-    const int dt = d->dtype;
-    const size_t e = esize(dt);
-    const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim, F = d->inter;
-    const int QKV = (H + 2 * Hk) * hd;
-    const int S = total;
-    hipError_t he = hipMemcpyAsync(w.h, embeds, (size_t)S * D * e, hipMemcpyDeviceToDevice, st);
-    if (he != hipSuccess) return hip_fail(he, "prefill copy embeds");
-    TEO_TRY(gemm_sk_workspace_init(w.sk, st));
-    TEO_TRY(snapshot_rows(hidden_states, 0, w.h, S, D, e, st));
-    const bool fp8 = prefill_uses_fp8(d);
-    for (int l = 0; l < d->layers; ++l) {
-        if (l > 0) TEO_TRY(snapshot_rows(hidden_states, l, w.h, S, D, e, st));         // the residual stream after layer l - 1
-        auto attend = [&]() -> int {
-        int row0 = 0;
-        for (int b = 0; b < nseq; ++b) {
-            const int Sb = seq_lens[b];
-            unsigned char* qkv_b = (unsigned char*)w.qkv + (size_t)row0 * QKV * e;
-            const size_t slot = slots ? (size_t)slots[b] : (size_t)b;
-            const int past = pasts ? pasts[b] : 0;
-            unsigned char* kc = (unsigned char*)d->k_cache[l] + slot * cache_stride * e;
-            unsigned char* vc = (unsigned char*)d->v_cache[l] + slot * cache_stride * e;
-            unsigned char* vtc = (unsigned char*)d->vt_cache[l] + slot * cache_stride * e;
-            TEO_TRY(rope_kv_append(qkv_b, QKV, nullptr, d->rope_cos, d->rope_sin, kc, vc, vtc, Sb, past, nullptr, d->max_seq, H, Hk,
-                                   hd, dt, st));
-            teo_attn_args a;
-            memset(&a, 0, sizeof(a));
-            a.q = qkv_b; a.k = kc; a.v = vc; a.vt = vtc; a.o = (unsigned char*)w.attn + (size_t)row0 * H * hd * e;
-            a.q_bs = 0; a.q_hs = hd; a.q_rs = QKV;
-            a.k_bs = 0; a.k_hs = (long long)d->max_seq * hd; a.k_rs = hd;
-            a.v_bs = 0; a.v_hs = (long long)d->max_seq * hd; a.v_rs = hd;
-            a.vt_bs = 0; a.vt_hs = (long long)hd * d->max_seq; a.vt_rs = d->max_seq;
-            a.o_bs = 0; a.o_rs = (long long)H * hd;
-            a.batch = 1; a.heads = H; a.kv_heads = Hk; a.head_dim = hd; a.q_len = Sb; a.kv_len = past + Sb;
-            a.causal = 1;
-            a.scale = 1.0f / sqrtf((float)hd);
-            TEO_TRY(attention(&a, dt, st));
-            row0 += Sb;
-        }
-        return TEO_OK;
-        };
-        if (fp8) {
-            TEO_TRY(prefill_layer_fp8(d, w, l, S, attend, st));
-            continue;
-        }
-        if (d->prefill_w4 && d->prefill_w4a8) {
-            TEO_TRY(prefill_layer_w4a8(d, w, l, S, attend, st));
-            continue;
-        }
-        if (d->prefill_w4) {
-            TEO_TRY(prefill_layer_w4(d, w, l, S, attend, st));
-            continue;
-        }
-        TEO_TRY(rmsnorm(w.h, d->in_norm_w[l], w.n, S, D, d->eps, dt, st));
-        TEO_TRY(gemm(w.n, d->qkv_w[l], nullptr, nullptr, w.qkv, S, QKV, D, D, QKV, TEO_ACT_NONE, 0, dt, dt, st, w.sk));
-        TEO_TRY(attend());
-        TEO_TRY(gemm(w.attn, d->o_w[l], nullptr, w.h, w.h, S, D, H * hd, H * hd, D, TEO_ACT_NONE, 0, dt, dt, st, w.sk));
-        TEO_TRY(rmsnorm(w.h, d->post_norm_w[l], w.n, S, D, d->eps, dt, st));
-        TEO_TRY(gemm(w.n, d->gateup_w[l], nullptr, nullptr, w.act, S, 2 * F, D, D, F, TEO_ACT_NONE, TEO_GEMM_SWIGLU16, dt, dt, st, w.sk));
-        TEO_TRY(gemm(w.act, d->down_w[l], nullptr, w.h, w.h, S, D, F, F, D, TEO_ACT_NONE, 0, dt, dt, st, w.sk));
-    }
-    if (!last_only) {                                    // training-shape forward: logits of every row, [sum(seq_lens), vocab]
-        TEO_TRY(rmsnorm(w.h, d->final_norm_w, w.n, S, D, d->eps, dt, st));
-        TEO_TRY(snapshot_rows(hidden_states, d->layers, w.n, S, D, e, st));
-        return gemm(w.n, d->lm_head, nullptr, nullptr, logits, S, d->vocab, D, D, d->vocab, TEO_ACT_NONE, 0, dt, TEO_F32, st, w.sk);
-    }
-    if (hidden_states) TEO_TRY(rmsnorm(w.h, d->final_norm_w, (unsigned char*)hidden_states + (size_t)d->layers * S * D * e, S, D, d->eps, dt, st));
-    int row_end = 0;
-    for (int b = 0; b < nseq; ++b) {
-        row_end += seq_lens[b];
-        const void* hl = (const unsigned char*)w.h + (size_t)(row_end - 1) * D * e;
-        TEO_TRY(gemv(hl, d->lm_head, d->final_norm_w, nullptr, logits + (size_t)b * d->vocab, d->vocab, D, d->eps, 0, dt, TEO_F32, st));
-    }
-    return TEO_OK;
+    std::vector<PrefillSeq> seqs(nseq);
+    for (int b = 0; b < nseq; ++b)
+        seqs[b] = {seq_lens[b], pasts ? pasts[b] : 0, (size_t)(slots ? slots[b] : b) * cache_stride * esize(d->dtype)};
+    return prefill_pass(d, who, seqs.data(), nseq, embeds, nullptr, last_only, logits, ws, ws_bytes, st, hidden_states, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------

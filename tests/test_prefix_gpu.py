@@ -256,6 +256,16 @@ def test_prefill_slots_past_under_prefill_mxfp4():
         model.engine.set_options(prefill_mxfp4=False)
 
 
+def test_prefill_slots_past_under_prefill_mxfp4_a8():
+    model = build("tinyB", BF, weight_format="mxfp4")
+    model.engine.set_options(prefill_mxfp4=True, prefill_mxfp4_a8=True)
+    try:
+        assert model.engine.llama_desc.prefill_w4a8 == 1
+        run_past_cases(model, "prefill_mxfp4_a8")
+    finally:
+        model.engine.set_options(prefill_mxfp4=False, prefill_mxfp4_a8=False)
+
+
 # ------------------------------------------------------------------------------------------------------------------ 4. end to end
 # "Split equals whole" -- one prefill of [0, L) against [0, P) then [P, L) -- is NOT a property of the 16-bit prefill: measured on tinyB
 # fp16, single K entries of layer 0 differ in their last bit in 6 of 42 probes (P, L, seed), e.g. (70, 79), (128, 140), (5, 75), and the
