@@ -208,6 +208,20 @@ __device__ __forceinline__ uint4 ld16(const void* p) {
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
+// An element's bit pattern, held unwidened in a register: a small load taken ahead of the weight stream stays a plain load (no conversion
+// next to it for the compiler to wait on) and is widened where it is used.  held_value is opaque to the scheduler, so the widening -- and
+// the wait for the load -- cannot move back up in front of it.
+template <typename T> using RawBits = typename std::conditional<sizeof(T) == 2, unsigned short, unsigned>::type;
+template <typename T>
+__device__ __forceinline__ RawBits<T> raw_bits(const T* p) { return *reinterpret_cast<const RawBits<T>*>(p); }
+template <typename T>
+__device__ __forceinline__ float held_value(RawBits<T> bits) {
+    unsigned b = bits;
+    asm volatile("" : "+v"(b));
+    const RawBits<T> r = (RawBits<T>)b;
+    return Elem<T>::ld(reinterpret_cast<const T*>(&r));
+}
+
 // Tunables (teo_tune, tune.h): gemv_nt non-temporal loads on/off, gemv_max_blocks workgroup cap, gemv_variant of the row-group kernel, ...
 
 // LDS image of f(x) for weight chunks of VE elements: the lanes of a wave read chunk (cb*64 + lane), so the image is
@@ -504,6 +518,17 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const T* __restrict__ 
         }
     };
     int grp = blockIdx.x * GV_WAVES + wid;
+    // w13 row table entries of group g, clamped to the last group (nothing past the table is read).  They run ONE GROUP AHEAD of the
+    // weights -- the first group's ahead of the x prologue, group g + nwaves' at the head of group g: read at the head of their own group,
+    // the row bases stand between the entries' loads and the group's first weight request, and every group starts with a dependent
+    // memory round trip.  A group ahead, the loads are older than weights that have already been consumed (vmcnt retires in order).
+    auto load_rt = [&](int g, unsigned (&t)[R]) {
+        const int gc = min(g, ngroups - 1);
+#pragma unroll
+        for (int r = 0; r < R; ++r) t[r] = IsP13<WT>::v ? img.rt[row_of(gc, r)] : 0u;
+    };
+    unsigned rtn[R];
+    load_rt(grp, rtn);
     // PF (host guarantees nchunk >= STEP): NO branch around the prefetch -- at a control-flow merge hipcc waits vmcnt(0),
     // which would drain the weights before the prologue.  Waves past the last group prefetch a clamped (valid) row.
     stage_x<T, VE, RowsImage16<T, WT>::v, XPT>(x, norm_w, xs, red, K, eps, [&]() {
@@ -530,9 +555,10 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const T* __restrict__ 
         float sc[R];                                 // row scales: loaded ahead of the weight stream, never waited on later
 #pragma unroll
         for (int r = 0; r < R; ++r) sc[r] = (!IsMx<WT>::v && !IsP13<WT>::v && wscale) ? (float)wscale[rows[r]] : 1.f;
-        unsigned rt[R], rpm[R];                      // w13 row table entries, loaded here for the same reason
+        unsigned rt[R], rpm[R];                      // w13 row table entries: requested a group ago, the next group's requested here
 #pragma unroll
-        for (int r = 0; r < R; ++r) { rt[r] = IsP13<WT>::v ? img.rt[rows[r]] : 0u; rpm[r] = p13_rpm(rt[r]); }
+        for (int r = 0; r < R; ++r) { rt[r] = rtn[r]; rpm[r] = p13_rpm(rt[r]); }
+        load_rt(grp + nwaves, rtn);
         float acc[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = 0.f;
@@ -603,15 +629,19 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
     const int row0 = blockIdx.x * R;
     const float my_scale = (!IsMx<WT>::v && !IsP13<WT>::v && wscale && tid < R && row0 + tid < N) ? (float)wscale[row0 + tid] : 1.f;   // ahead of the stream
     // the residual too: read after the reduction barrier it is a dependent global round trip at the tail of EVERY workgroup
-    // (all of them are resident at once, so the whole launch ends one memory latency later); only this thread writes y[n]
-    const float my_res = (res && tid < R && row0 + tid < N) ? Elem<T>::ld(res + row0 + tid) : 0.f;
+    // (all of them are resident at once, so the whole launch ends one memory latency later); only this thread writes y[n].
+    // Only its raw bits are taken here: widened in this branch, the load is waited for (vmcnt(0)) before wave 0's first weight request.
+    // They are widened after the reduction barrier.
+    RawBits<T> my_res_bits = 0;
+    if (res && tid < R && row0 + tid < N) my_res_bits = raw_bits(res + row0 + tid);
     float acc[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[r] = 0.f;
     const WT* wrow[R];
     const unsigned char* srow[R];                         // MXFP4: the rows' e8m0 bytes, one per chunk
     const unsigned char* grow[R];                         // w13 image: wrow / srow / grow are the rows' LO / NIB / SGN bytes
-    unsigned rt[R], rpm[R];                               // and its row table entries, ahead of the stream like the scales
+    // and its row table entries: requested here (scalar loads, all R before any is looked at), consumed behind each step's loads
+    unsigned rt[R], rpm[R];
     P13Img img = {};
     if constexpr (IsP13<WT>::v) img = p13_img(W, N, K);
 #pragma unroll
@@ -625,7 +655,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
             srow[r] = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) + row * nchunk : nullptr;
             grow[r] = nullptr; rt[r] = 0u;
         }
-        rpm[r] = p13_rpm(rt[r]);
+        rpm[r] = 0u;
     }
     // chunk index for (iteration, unroll u): c = cb + u*256 + wid*64 + lane
     auto step = [&](int cb, auto full_tag) {
@@ -657,6 +687,23 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
                     w[u][r] = (FULL || c < nchunk) ? p13_load<NT>(reinterpret_cast<const unsigned char*>(wrow[r]), srow[r], grow[r], c) : make_uint4(0, 0, 0, 0);
                 else
                     w[u][r] = (FULL || c < nchunk) ? ld16<NT>(wrow[r] + (long long)c * CU<WT>::v) : make_uint4(0, 0, 0, 0);
+            }
+        }
+        if constexpr (IsP13<WT>::v) {
+            // the row bases, taken from the entries BEHIND the step's loads: the entries are scalar loads, whose wait (lgkmcnt(0)) the
+            // compiler otherwise places -- one per entry -- in front of the first weight request of a one-to-three-step kernel.  The
+            // empty asm is opaque and ordered against the loads, so the arithmetic on an entry cannot be scheduled above them; three
+            // scalar instructions per row and step.  (No sched_barrier: it also fixes the order of the step's loads -- LO first -- and the
+            // rebuild then starts later than with the small NIB / SGN loads in front: down projection 14.75 -> 14.96 us.)
+            // Nothing but the schedule holds this order and the bits are the same either way, so after a compiler change read it again:
+            //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-kernarg-preload-count=16 --cuda-device-only -S gemv.hip
+            // In gemv_splitk_kernel<bf16, bf16, p13_t, 2, 2, true> the first s_waitcnt lgkmcnt(0) behind the two s_load_dword of the
+            // entries must stand BEHIND the loop's 2 + 12 global_load (profiles/r17_gemv_stream_head.md, section 2).
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                unsigned t = rt[r];
+                asm volatile("" : "+s"(t));
+                rpm[r] = p13_rpm(t);
             }
         }
         rebuild_block<WT, R, U, true>(w, rpm);
@@ -724,7 +771,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
         if (n < N) {
             float v = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
             v *= my_scale;
-            v += my_res;
+            v += held_value<T>(my_res_bits);
             Elem<TO>::st(y + n, v);
         }
     }
@@ -786,6 +833,16 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_qkv_rope_kernel(const WT* __r
         }
     };
     const int grp0 = blockIdx.x * GV_WAVES + wid;
+    // w13 row table entries of group g (clamped to the last group), one group ahead of the weights: as in gemv_kernel
+    auto load_rt = [&](int g, unsigned (&t)[R]) {
+        long long rows[R];
+        int head, i0;
+        rows_of(min(g, ngroups - 1), rows, head, i0);
+#pragma unroll
+        for (int r = 0; r < R; ++r) t[r] = IsP13<WT>::v ? img.rt[rows[r]] : 0u;
+    };
+    unsigned rtn[R];
+    load_rt(grp0, rtn);
     stage_x<T, VE, BfImage<T, WT>::v, XPT>(x, norm_w, xs, red, K, eps, [&]() {
         if (PF) {                                         // branch-free (see gemv_kernel)
             long long rows[R];
@@ -808,14 +865,20 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_qkv_rope_kernel(const WT* __r
         const unsigned char *srow[R], *grow[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) row_ptrs(rows[r], rowp[r], srow[r], grow[r]);
-        // rotation coefficients of this pair: loaded before the weight stream so the epilogue never waits on memory
-        float rc = 1.f, rs = 0.f;
-        if (is_qk) { rc = cs[(long long)pos * half + i0]; rs = sn[(long long)pos * half + i0]; }
+        // rotation coefficients of this pair: loaded before the weight stream so the epilogue never waits on memory.  No branch around
+        // the loads (a v group reads the valid pair 0 and never looks at it): at the merge of one hipcc waits vmcnt(0) before the group's
+        // first weight request.  Only the q / k epilogue reads rc / rs.
+        const long long ci = (long long)pos * half + (is_qk ? i0 : 0);
+        const float rc = cs[ci], rs = sn[ci];
         constexpr bool SCALED = !IsMx<WT>::v && !IsP13<WT>::v;
         const float sc0 = (SCALED && wscale) ? (float)wscale[rows[0]] : 1.f, sc1 = (SCALED && wscale) ? (float)wscale[rows[1]] : 1.f;
-        unsigned rt[R], rpm[R];                          // w13 row table entries: ahead of the stream too
+        // w13 row table entries: requested a group ago, the next group's requested here.  (An entry is the same in every lane: taken into
+        // a scalar register, the row bases and the escaped-row test cost no vector registers -- held per lane across the group, as in
+        // gemv_kernel, they took this kernel from 123 to 154 VGPRs and from four waves per SIMD to three.)
+        unsigned rt[R], rpm[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) { rt[r] = IsP13<WT>::v ? img.rt[rows[r]] : 0u; rpm[r] = p13_rpm(rt[r]); }
+        for (int r = 0; r < R; ++r) { rt[r] = IsP13<WT>::v ? __builtin_amdgcn_readfirstlane(rtn[r]) : 0u; rpm[r] = p13_rpm(rt[r]); }
+        load_rt(grp + nwaves, rtn);
         float acc[R] = {0.f, 0.f};
         int c0 = 0;
         if (have) {

@@ -14,45 +14,93 @@ for C in FETCH_SIZE WRITE_SIZE TCC_EA0_RDREQ_sum; do
   rc=$?; if [ $rc -ne 0 ]; then echo "pass $C failed ($rc): no further GPU passes"; exit $rc; fi
 done
 python3 - "$COMMIT" "$ROOT" <<'PY'
-import glob, json, os, sqlite3, sys
-KERNELS = {   # name -> (substring test on the kernel name, algorithmic bytes per launch at LLaMA-2-7B bf16, ctx ~2175)
-    "gateup_gemv": (lambda n: "gemv_kernel<" in n and "true, true, true" in n, 2 * 11008 * 4096 * 2),
-    "qkv_rope_gemv": (lambda n: "gemv_qkv_rope_kernel<" in n, 12288 * 4096 * 2),
-    "o_gemv": (lambda n: "gemv_splitk_kernel<" in n and ", 2, 2, true>" in n, 4096 * 4096 * 2),
-    "down_gemv": (lambda n: "gemv_splitk_kernel<" in n and ", 2, 6, true>" in n, 4096 * 11008 * 2),
-    "lm_head_gemv": (lambda n: "gemv_kernel<" in n and "float" in n.split("<")[1].split(",")[1], 32000 * 4096 * 2),
-    "attn_decode_partial": (lambda n: "attn_decode_partial_kernel<" in n, 2 * 32 * 2175 * 128 * 2),
-    "attn_decode_combine": (lambda n: "attn_decode_combine_kernel<" in n, None),
+import glob, json, os, re, sqlite3, sys
+# LLaMA-2-7B, ctx ~2175.  Bytes per launch of a matrix: 2 per weight, or the w13 image's (csrc/p13.h: RT + LO + NIB + SGN, each section
+# rounded up to 256 bytes; the few escaped rows of ESC are left out) when the kernel that ran is a p13_t instantiation.
+SHAPES = {"gateup_gemv": (2 * 11008, 4096), "qkv_rope_gemv": (12288, 4096), "o_gemv": (4096, 4096), "down_gemv": (4096, 11008), "lm_head_gemv": (32000, 4096)}
+def up(v): return (v + 255) // 256 * 256
+def matrix_bytes(key, name):
+    N, K = SHAPES[key]
+    return (up(4 * N) + up(N * K) + up(N * K // 2) + up(N * K // 8)) if "p13_t" in name else 2 * N * K
+def targs(n):           # template arguments of the kernel name
+    m = re.search(r"<(.*?)>\(", n) or re.search(r"<(.*)>", n)
+    return [a.strip() for a in m.group(1).split(",")] if m else []
+# gemv_kernel<T, TO, WT, R, U, PF, NT, SWIGLU, XPT>: gate/up is the SwiGLU form (whatever PF is: the image kernel runs without the prefetch),
+# lm_head the fp32-output form.  Where several instantiations match (bench.py --full also runs a decode_pack-off phase), the one with
+# the most launches is the one the default path runs.
+MATCH = {
+    "gateup_gemv": lambda n: "gemv_kernel<" in n and len(targs(n)) == 9 and targs(n)[7] == "true",
+    "qkv_rope_gemv": lambda n: "gemv_qkv_rope_kernel<" in n,
+    "lm_head_gemv": lambda n: "gemv_kernel<" in n and len(targs(n)) == 9 and targs(n)[1] == "float",
+    "attn_decode_partial": lambda n: "attn_decode_partial_kernel<" in n,
+    "attn_decode_combine": lambda n: "attn_decode_combine_kernel<" in n,
 }
-raw = {}
-for c in ("FETCH_SIZE", "WRITE_SIZE", "TCC_EA0_RDREQ_sum"):
+ATTN_BYTES = 2 * 32 * 2175 * 128 * 2
+COUNTERS = ("FETCH_SIZE", "WRITE_SIZE", "TCC_EA0_RDREQ_sum")
+vals = {}               # counter -> kernel name -> values of every launch
+for c in COUNTERS:
+    vals[c] = {}
     dbs = glob.glob(f"/tmp/pmcd_{c}/**/*.db", recursive=True)
-    if not dbs:
-        raw[c] = {}
-        continue
-    cur = sqlite3.connect(dbs[0]).cursor()
-    rows = list(cur.execute("select kernel_name, count(*), avg(value) from counters_collection where counter_name = ? group by kernel_name", (c,)))
-    raw[c] = {r[0]: (r[1], r[2]) for r in rows}
+    if dbs:
+        for name, v in sqlite3.connect(dbs[0]).cursor().execute("select kernel_name, value from counters_collection where counter_name = ?", (c,)):
+            vals[c].setdefault(name, []).append(v)
+def mean(v): return sum(v) / len(v) if v else 0.0
+def entry(key, name, pick=lambda c, v: v):
+    """one kernel's summary from the launches of `name`; pick(counter, values) selects the launches that belong to `key`"""
+    f, w, r = (pick(c, vals[c].get(name, [])) for c in COUNTERS)
+    alg = matrix_bytes(key, name) if key in SHAPES else (ATTN_BYTES if key == "attn_decode_partial" else None)
+    e = {"algorithmic_bytes": alg, "kernel": name[:140], "launches_sampled": len(f), "FETCH_SIZE_KB_avg": mean(f), "WRITE_SIZE_KB_avg": mean(w),
+         "TCC_EA0_RDREQ_sum_avg": mean(r), "hbm_bytes_per_launch": int(2 * mean(f) * 1024 + mean(w) * 1024), "rdreq_bytes_per_launch": int(mean(r) * 128)}
+    if key in SHAPES:
+        e["bytes_16bit"] = 2 * SHAPES[key][0] * SHAPES[key][1]
+    if alg:
+        e["traffic_over_algorithmic"] = round(e["hbm_bytes_per_launch"] / alg, 4)
+    return e
+def most_launched(match):
+    names = [n for n in vals["FETCH_SIZE"] if match(n)]
+    return max(names, key=lambda n: len(vals["FETCH_SIZE"][n]))
 out = {"source": "tools/pmc_decode_traffic.sh: three separate rocprofv3 --kernel-trace --pmc passes over `python3 bench.py --full --steps 1 --warmup 0 --new 12 --no-cpu-baseline --no-graph` (rounds 3-4)",
        "commit": sys.argv[1], "csrc_sha16": __import__("subprocess").check_output(["python3", os.path.join(sys.argv[2], "tools", "src_hash.py")]).decode().strip(),
        "correction": "gfx950: read bytes = 2 * FETCH_SIZE * 1024 (128-B requests tallied at 64 B) + WRITE_SIZE * 1024; cross-check TCC_EA0_RDREQ_sum * 128 B",
+       "algorithmic_bytes": "what the kernel that ran streams: 2 bytes per weight, or the w13 image (0.8125 x + the row table) for a p13_t instantiation; bytes_16bit is the former",
        "kernels": {}}
-for key, (match, alg) in KERNELS.items():
-    e = {"algorithmic_bytes": alg}
+for key, match in MATCH.items():
     try:
-        names = [n for n in raw["FETCH_SIZE"] if match(n)]
-        name = max(names, key=lambda n: raw["FETCH_SIZE"][n][0])
-        f, w, r = raw["FETCH_SIZE"][name], raw["WRITE_SIZE"].get(name, (0, 0.0)), raw["TCC_EA0_RDREQ_sum"].get(name, (0, 0.0))
-        e.update({"kernel": name[:140], "launches_sampled": f[0], "FETCH_SIZE_KB_avg": f[1], "WRITE_SIZE_KB_avg": w[1], "TCC_EA0_RDREQ_sum_avg": r[1],
-                  "hbm_bytes_per_launch": int(2 * f[1] * 1024 + w[1] * 1024), "rdreq_bytes_per_launch": int(r[1] * 128)})
-        if alg:
-            e["traffic_over_algorithmic"] = round(e["hbm_bytes_per_launch"] / alg, 4)
+        out["kernels"][key] = entry(key, most_launched(match))
     except Exception as ex:  # noqa: BLE001
-        e["error"] = str(ex)
-    out["kernels"][key] = e
+        out["kernels"][key] = {"error": str(ex)}
+# split-K: gemv_splitk_kernel<T, TO, WT, R, U, NT>.  On the 16-bit matrices o and down are two instantiations (U = 2 and U = 6); on the images
+# both run U = 2 -- one kernel name, launched o, down, o, down, ... -- and differ by what they read: down streams 2.7 x o's bytes, so
+# the launches of a read counter fall into two groups around the midpoint of its range (asserted: each group within 20 % of its mean).
+# Both write the same 4096 outputs: WRITE_SIZE is taken over all launches.
+try:
+    sk = most_launched(lambda n: "gemv_splitk_kernel<" in n)
+    fv = vals["FETCH_SIZE"][sk]
+    if max(fv) > 1.5 * min(fv):                                   # one instantiation for both matrices
+        def side(high):
+            def pick(c, v):
+                if c == "WRITE_SIZE" or not v:
+                    return v
+                mid = (min(v) + max(v)) / 2
+                g = [x for x in v if (x > mid) == high]
+                assert g and all(abs(x - mean(g)) <= 0.2 * mean(g) for x in g), f"{c}: the launches of {sk[:60]} do not fall into two groups"
+                return g
+            return pick
+        out["kernels"]["o_gemv"] = entry("o_gemv", sk, side(False))
+        out["kernels"]["down_gemv"] = entry("down_gemv", sk, side(True))
+        n_o, n_d = out["kernels"]["o_gemv"]["launches_sampled"], out["kernels"]["down_gemv"]["launches_sampled"]
+        assert n_o == n_d, f"o and down launches differ: {n_o} / {n_d}"
+    else:
+        for key, u in (("o_gemv", "2"), ("down_gemv", "6")):
+            out["kernels"][key] = entry(key, most_launched(lambda n, u=u: "gemv_splitk_kernel<" in n and targs(n)[3:5] == ["2", u]))
+except Exception as ex:  # noqa: BLE001
+    out["kernels"]["o_gemv"] = out["kernels"]["down_gemv"] = {"error": str(ex)}
+bad = [k for k, e in out["kernels"].items() if "error" in e]
 gu = out["kernels"].get("gateup_gemv", {})
 out["hbm_bytes_per_launch"] = gu.get("hbm_bytes_per_launch")        # the dominant kernel: bench.py's roofline.traffic
-out["kernel"] = "gemv_kernel<bf16,bf16,R=2,U=4,NT,SWIGLU> N=22016 K=4096 (decode rmsnorm + gate/up + SwiGLU)"
+out["kernel"] = gu.get("kernel", "?").split("(")[0] + " N=22016 K=4096 (decode rmsnorm + gate/up + SwiGLU)"
 json.dump(out, open(os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out/r06p/r06_pmc_decode_traffic.json", "w"), indent=1)
 print(json.dumps(out)[:3000])
+if bad:
+    sys.exit(f"no figure for {bad}: do not commit this summary")
 PY
