@@ -16,10 +16,12 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .engine import _p, dequantize_mxfp4_blocks, reinterleave_gate_up, tile_weights, tile_weights_mxfp4
+from .decode_host import (SEED_MASK, PtrArrays, StepGraphs, _p, alloc_loop_state, arm_sampler, prefill_append, profile_steps, run_prefill,
+                          sync_desc_options)
+from .engine import dequantize_mxfp4_blocks, reinterleave_gate_up, tile_weights, tile_weights_mxfp4
 
 
-class BatchDecoder:
+class BatchDecoder(StepGraphs, PtrArrays):
     def __init__(self, engine, batch, max_new=1024, tiled=True):
         if not 1 <= batch <= L.MAX_DECODE_BATCH:
             raise ValueError(f"batch {batch} outside 1..{L.MAX_DECODE_BATCH}")
@@ -55,7 +57,7 @@ class BatchDecoder:
         self.block8 = False
         # engine option batch_mxfp4: stream tiled MXFP4 copies of qkv / o / gateup / down (one k-step = 128 k).  Sizes that are not
         # multiples of 128 fall back to the 16-bit tiled step below (w4 stays False)
-        self.w4_requested = bool(getattr(engine, "batch_mxfp4", False))
+        self.w4_requested = bool(engine.batch_mxfp4)
         self.w4 = self.w4_requested and engine.llama_w4 is not None and self.tiled and dt == torch.bfloat16 and c.hidden_size % 128 == 0 \
             and c.intermediate_size % 128 == 0 and (c.num_attention_heads * hd) % 128 == 0
         if self.w4:
@@ -78,7 +80,7 @@ class BatchDecoder:
             d.gateup_w4, d.gateup_e4 = self._arr(tq["gateup"]), self._arr(te["gateup"])
             d.down_w4, d.down_e4 = self._arr(tq["down"]), self._arr(te["down"])
             d.lm_head = head.data_ptr()
-        elif getattr(engine, "mxfp4_only", False):
+        elif engine.mxfp4_only:
             # an mxfp4_only engine has no 16-bit layer matrices and this decoder cannot take the tiled 4-bit step (tiled=False): it owns
             # 16-bit copies rebuilt from the codes (exactly the dequantised weights), tiled when the 16-bit step is
             q4, e4 = engine.llama_w4
@@ -116,54 +118,23 @@ class BatchDecoder:
                 d.gateup_w, d.down_w = self._arr(tw["gateup"]), self._arr(tw["down"])
                 d.lm_head = head.data_ptr()
         self.desc = d
-        # the engine's per-engine options (TeoEngine.set_options) reach the copies made above
-        import weakref
-        me = weakref.ref(self)
-
-        def _sync_options(src):
-            o = me()
-            if o is not None:
-                for dd in o.slot_desc + [o.desc]:
-                    dd.prefill_fp8, dd.rope_in_attn = src.prefill_fp8, src.rope_in_attn
-                for dd in o.slot_desc:            # row-major *_w4 arrays; the step descriptor's are tiled and keep prefill_w4 = 0
-                    dd.prefill_w4 = src.prefill_w4
-                    dd.prefill_w4a8 = src.prefill_w4a8
-        engine._option_hooks.append(_sync_options)
-
-        def _knob_changed():                      # TeoEngine.tune_set: the captured batched step keeps the choices of its capture
-            o = me()
-            if o is not None:
-                o._drop_graph()
-        engine._tune_hooks.append(_knob_changed)
+        # the engine's per-engine options (TeoEngine.set_options) reach the copies made above: the slot descriptors' *_w4 arrays are
+        # row-major, the step descriptor's tiled; TeoEngine.tune_set: the captured batched step keeps the choices of its capture
+        engine.on_options(self, lambda o, src: sync_desc_options(src, o.slot_desc, [o.desc]))
+        engine.on_tune(self, BatchDecoder._drop_graph)
         # device state
-        self.d_token = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.d_pos = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.d_out = torch.zeros(B, self.max_new, dtype=torch.int64, device=dev)
-        self.d_count = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.d_stop = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.d_stop_ids = torch.zeros(16, dtype=torch.int64, device=dev)
-        self.d_logits = torch.zeros(B, c.vocab_size, dtype=torch.float32, device=dev)
-        self.d_rng = torch.zeros(B, 2, dtype=torch.int64, device=dev)
         s = L.DecodeBatchState()
+        alloc_loop_state(self, s, dev, self.max_new, (B, c.vocab_size), rows=B)
         s.batch, s.out_stride = B, self.max_new
         s.cache_stride = self.k_cache.stride(1)
         assert self.v_cache.stride(1) == s.cache_stride and self.vt_cache.stride(1) == s.cache_stride
         s.w_tiled = 1 if self.tiled else 0
         s.gateup_block8 = 1 if self.block8 else 0
         s.w_mxfp4 = 1 if self.w4 else 0
-        s.d_token, s.d_pos, s.d_out_tokens = self.d_token.data_ptr(), self.d_pos.data_ptr(), self.d_out.data_ptr()
-        s.d_out_count, s.d_stop = self.d_count.data_ptr(), self.d_stop.data_ptr()
-        s.d_stop_ids, s.n_stop_ids, s.d_logits = self.d_stop_ids.data_ptr(), 0, self.d_logits.data_ptr()
-        s.do_sample, s.top_k, s.temperature, s.d_rng, s.top_p = 0, 0, 1.0, self.d_rng.data_ptr(), 1.0
         self.state = s
-        self._graph = None
+        StepGraphs.__init__(self)
         self._steps_done = 0
         self._armed = False
-
-    def _arr(self, tensors):
-        arr, pp = L.ptr_array([t.data_ptr() for t in tensors])
-        self._keep.append((arr, tensors))
-        return pp
 
     # ------------------------------------------------------------------ prefill (one conversation at a time)
     def reset(self):
@@ -172,25 +143,9 @@ class BatchDecoder:
 
     def prefill(self, slot, embeds, last_only=True):
         """Append embeds [S, D] to conversation `slot`; returns fp32 logits ([1, V] with last_only)."""
-        eng = self.eng
-        S = embeds.shape[0]
         past = self.cache_len[slot]
-        if past + S > eng.max_seq:
-            raise ValueError(f"sequence length {past + S} exceeds the engine's max_seq {eng.max_seq}")
-        d = self.slot_desc[slot]
-        with eng.phase() as st:
-            e = embeds.to(device=eng.device, dtype=eng.dtype).contiguous()
-            pos = torch.arange(past, past + S, dtype=torch.int32, device=eng.device)
-            rows = 1 if last_only else S
-            logits = torch.empty(rows, eng.cfg.vocab_size, dtype=torch.float32, device=eng.device)
-            eng._flush_handoff_checks("prefill")
-            ws = eng._workspace("prefill", self.lib.teo_llama_prefill_workspace_bytes(C.byref(d), S))
-            L.check(self.lib.teo_llama_prefill(C.byref(d), _p(e), _p(pos), S, past, 1 if last_only else 0, _p(logits), _p(ws),
-                                               ws.numel(), st, None), "teo_llama_prefill")
-            sid = C.c_void_p(eng.stream.cuda_stream)
-            eng._check_handoffs("prefill", lambda f: self.lib.teo_llama_prefill_workspace_status(C.byref(d), S, _p(ws), ws.numel(), C.byref(f), sid),
-                                "teo_llama_prefill")
-        self.cache_len[slot] = past + S
+        logits = prefill_append(self.eng, self.slot_desc[slot], embeds, past, last_only)
+        self.cache_len[slot] = past + embeds.shape[0]
         self._armed = False                       # forward_step's device positions are stale for this slot now: it re-arms from cache_len
         return logits
 
@@ -206,21 +161,17 @@ class BatchDecoder:
         if max(lens) > eng.max_seq:
             raise ValueError(f"sequence length {max(lens)} exceeds the engine's max_seq {eng.max_seq}")
         total = sum(lens)
-        with eng.phase() as st:
+        with eng.phase():
             rows = torch.cat([e.to(device=eng.device, dtype=eng.dtype) for e in embeds_list], dim=0).contiguous()
             logits = torch.empty(self.B if last_only else total, eng.cfg.vocab_size, dtype=torch.float32, device=eng.device)
             hs = (torch.empty(eng.cfg.num_hidden_layers + 1, total, eng.cfg.hidden_size, dtype=eng.dtype, device=eng.device)
                   if hidden_states else None)
-            eng._flush_handoff_checks("prefill")
             d0 = self.slot_desc[0]
-            ws = eng._workspace("prefill", self.lib.teo_llama_prefill_workspace_bytes(C.byref(d0), total))
             arr = (C.c_int * self.B)(*lens)
-            L.check(self.lib.teo_llama_prefill_batch(C.byref(d0), _p(rows), arr, self.B, self.k_cache.stride(1), 1 if last_only else 0,
-                                                     _p(logits), _p(ws), ws.numel(), st, _p(hs) if hs is not None else None),
-                    "teo_llama_prefill_batch")
-            sid = C.c_void_p(eng.stream.cuda_stream)
-            eng._check_handoffs("prefill", lambda f: self.lib.teo_llama_prefill_workspace_status(C.byref(d0), total, _p(ws), ws.numel(), C.byref(f), sid),
-                                "teo_llama_prefill_batch")
+            run_prefill(eng, d0, total, "teo_llama_prefill_batch",
+                        lambda ws, st: self.lib.teo_llama_prefill_batch(C.byref(d0), _p(rows), arr, self.B, self.k_cache.stride(1),
+                                                                        1 if last_only else 0, _p(logits), _p(ws), ws.numel(), st,
+                                                                        _p(hs) if hs is not None else None))
         self.cache_len = list(lens)
         self._armed = False
         return (logits, hs) if hidden_states else logits
@@ -228,11 +179,6 @@ class BatchDecoder:
     # ------------------------------------------------------------------ decode
     def _workspace(self):
         return self.eng._workspace("decode_batch", self.lib.teo_llama_decode_batch_workspace_bytes(C.byref(self.desc), self.B))
-
-    def _drop_graph(self):
-        if self._graph is not None:
-            self.lib.teo_graph_destroy(self._graph)
-            self._graph = None
 
     def begin(self, first_tokens, stop_ids=None, do_sample=False, temperature=1.0, top_k=0, seeds=None, draws_done=1, top_p=1.0):
         """Arm the loop: first_tokens[b] is the input of conversation b's next step, at position cache_len[b]."""
@@ -245,15 +191,8 @@ class BatchDecoder:
             self.d_count.zero_()
             self.d_stop.zero_()
             seeds = list(seeds) if seeds is not None else [0] * self.B
-            self.d_rng.copy_(torch.tensor([[int(sd) & (2 ** 63 - 1), int(draws_done)] for sd in seeds], dtype=torch.int64))
-            n = 0
-            if stop_ids:
-                n = min(len(stop_ids), 16)
-                self.d_stop_ids[:n] = torch.tensor(list(stop_ids)[-n:], dtype=torch.int64, device=eng.device)
-            s = self.state
-            key = (n, int(bool(do_sample)), int(top_k or 0), C.c_float(float(temperature)).value, C.c_float(float(top_p or 1.0)).value)
-            if key != (s.n_stop_ids, s.do_sample, s.top_k, float(s.temperature), float(s.top_p)):
-                s.n_stop_ids, s.do_sample, s.top_k, s.temperature, s.top_p = key
+            self.d_rng.copy_(torch.tensor([[int(sd) & SEED_MASK, int(draws_done)] for sd in seeds], dtype=torch.int64))
+            if arm_sampler(self.state, self.d_stop_ids, stop_ids, do_sample, temperature, top_k, top_p):
                 self._drop_graph()
         ws = self._workspace()
         with eng.phase() as st:
@@ -269,46 +208,28 @@ class BatchDecoder:
         if self._steps_done + n > self.max_new:
             raise ValueError(f"decode would exceed the output buffer ({self.max_new} tokens)")
         ws = self._workspace()
+        d, s_ = C.byref(self.desc), C.byref(self.state)
         with eng.phase() as st:
-            if use_graph:
-                if self._graph is None or self._graph_ws != ws.data_ptr():
-                    self._drop_graph()
-                    g = C.c_void_p()
-                    L.check(self.lib.teo_llama_decode_batch_graph_create(C.byref(self.desc), C.byref(self.state), _p(ws),
-                                                                         ws.numel(), st, C.byref(g)),
-                            "teo_llama_decode_batch_graph_create")
-                    self._graph, self._graph_ws = g, ws.data_ptr()
-                L.check(self.lib.teo_graph_launch(self._graph, n, st), "teo_graph_launch")
-                eng.stream.synchronize()        # drain the replays before anything is queued behind them (engine.py _Phase.__exit__)
-            else:
-                for _ in range(n):
-                    L.check(self.lib.teo_llama_decode_batch_step(C.byref(self.desc), C.byref(self.state), _p(ws), ws.numel(),
-                                                                 st), "teo_llama_decode_batch_step")
+            self.replay_or_step(eng.stream, ws.data_ptr(), n, use_graph,
+                                lambda out: L.check(self.lib.teo_llama_decode_batch_graph_create(d, s_, _p(ws), ws.numel(), st, out),
+                                                    "teo_llama_decode_batch_graph_create"),
+                                lambda: L.check(self.lib.teo_llama_decode_batch_step(d, s_, _p(ws), ws.numel(), st), "teo_llama_decode_batch_step"))
         self.cache_len = [x + n for x in self.cache_len]
         self._steps_done += n
 
     def steps_profiled(self, n):
         """n batched steps as plain launches, every kernel timed by its own dispatch timestamps (teo_llama_decode_batch_step_profile).
         Returns {class: (launches per step, mean microseconds per launch)}; advances the caches like steps()."""
-        from .engine import TeoEngine
         eng = self.eng
         if max(self.cache_len) + n > eng.max_seq or self._steps_done + n > self.max_new:
             raise ValueError("steps_profiled: would exceed max_seq / the output buffer")
         ws = self._workspace()
-        names = TeoEngine.PROF_CLASSES
-        K = len(names)
-        tot, cnt = [0.0] * K, [0] * K
-        ms, ct = (C.c_float * K)(), (C.c_int * K)()
         with eng.phase() as st:
-            for _ in range(n):
-                L.check(self.lib.teo_llama_decode_batch_step_profile(C.byref(self.desc), C.byref(self.state), _p(ws), ws.numel(), ms, ct, st),
-                        "teo_llama_decode_batch_step_profile")
-                for k in range(K):
-                    tot[k] += ms[k]
-                    cnt[k] += ct[k]
+            prof = profile_steps(n, lambda ms, ct: L.check(self.lib.teo_llama_decode_batch_step_profile(
+                C.byref(self.desc), C.byref(self.state), _p(ws), ws.numel(), ms, ct, st), "teo_llama_decode_batch_step_profile"))
         self.cache_len = [x + n for x in self.cache_len]
         self._steps_done += n
-        return {name: (cnt[k] // n, tot[k] / cnt[k] * 1e3) for k, name in enumerate(names) if cnt[k]}
+        return prof
 
     def forward_step(self, tokens):
         """One batched step fed with CALLER-chosen tokens (the continuation of LlavaLlamaForCausalLM.forward(past_key_values=...) at
@@ -319,7 +240,7 @@ class BatchDecoder:
         if len(toks) != self.B:
             raise ValueError(f"need {self.B} tokens")
         s = self.state
-        fresh = (not getattr(self, "_armed", False)) or self._steps_done + 1 > self.max_new \
+        fresh = (not self._armed) or self._steps_done + 1 > self.max_new \
             or (s.n_stop_ids, s.do_sample) != (0, 0)
         if fresh:
             self.begin(toks)                       # greedy, no device stop: positions from cache_len, counters zeroed
@@ -339,9 +260,3 @@ class BatchDecoder:
         """[B, steps] int64: the tokens produced by the steps so far (the first token of each conversation excluded)."""
         n = self._steps_done
         return self.d_out[:, :n].clone()
-
-    def __del__(self):
-        try:
-            self._drop_graph()
-        except Exception:  # noqa: BLE001
-            pass

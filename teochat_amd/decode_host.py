@@ -1,0 +1,192 @@
+"""The host side of a pass over the model, once: what TeoEngine, BatchDecoder, SpecDecoder and StreamDecoder all do around their ctypes
+calls.  Each rule that is easy to copy wrongly is stated here and nowhere else:
+
+  run_prefill        flush the workspace's unread status BEFORE the call re-arms it, call, check the hand-offs (deferred in a nested phase)
+  prefill_append     one conversation's rows behind its past through any descriptor copy (BatchDecoder.prefill = SpecDecoder.prefill)
+  arm_sampler        stop ids + sampler into a loop state; says whether a field a captured graph holds BY VALUE changed
+  StepGraphs         mixin: the plain and the guided step graph with their keys, capture-or-replay with the stream drained behind the
+                     replays, _drop_graph and the one __del__
+  profile_steps      the per-class accumulator of the profiled steps
+  alloc_loop_state   the eight device tensors of a decode loop and the state fields that point at them
+  PtrArrays          mixin: _arr, a pointer array kept alive beside its tensors
+  HookList           set_options / tune_set callbacks held through a weak reference to their owner; sync_desc_options, the rule for which
+                     descriptor copy receives which option
+
+engine.py imports this module; this module never imports engine.py.
+"""
+import ctypes as C
+import weakref
+
+import torch
+
+from . import _lib as L
+
+SEED_MASK = 2 ** 63 - 1            # d_rng is int64 on the host side: one mask for the first draw and every device loop
+MAX_STOP_IDS = 16                  # d_stop_ids holds the LAST 16 ids of a longer stop sequence
+PROF_CLASSES = ("qkv_rope_gemv", "attn_decode_partial", "attn_decode_combine", "o_gemv", "gateup_gemv", "down_gemv", "lm_head_gemv",
+                "decode_tail")
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+class PtrArrays:
+    """mixin over `self._keep` (a list): host pointer arrays live as long as their owner, beside the tensors they point at"""
+
+    def _arr(self, tensors):
+        arr, pp = L.ptr_array([t.data_ptr() for t in tensors])
+        self._keep.append((arr, tensors))
+        return pp
+
+
+# ---------------------------------------------------------------------- prefill
+def run_prefill(eng, desc, rows, what, call):
+    """One prefill entry on the engine stream (inside eng.phase()): `call(ws, stream)` makes the ctypes call named `what` for `rows` rows
+    through descriptor `desc` and returns its status.  An unread hand-off status of the "prefill" workspace is read BEFORE the call
+    re-arms the word; the check behind the call is TeoEngine._check_handoffs' (deferred inside a nested phase)."""
+    lib = eng.lib
+    eng._flush_handoff_checks("prefill")
+    ws = eng._workspace("prefill", lib.teo_llama_prefill_workspace_bytes(C.byref(desc), rows))
+    sid = C.c_void_p(eng.stream.cuda_stream)
+    L.check(call(ws, sid), what)
+    eng._check_handoffs("prefill", lambda f: lib.teo_llama_prefill_workspace_status(C.byref(desc), rows, _p(ws), ws.numel(), C.byref(f), sid),
+                        what)
+
+
+def prefill_append(eng, desc, embeds, past, last_only):
+    """Append embeds [S, D] behind `past` cached rows of the conversation whose caches `desc` names (teo_llama_prefill); returns fp32
+    logits [S, V] ([1, V] with last_only)."""
+    S = embeds.shape[0]
+    if past + S > eng.max_seq:
+        raise ValueError(f"sequence length {past + S} exceeds the engine's max_seq {eng.max_seq}")
+    with eng.phase():
+        e = embeds.to(device=eng.device, dtype=eng.dtype).contiguous()
+        pos = torch.arange(past, past + S, dtype=torch.int32, device=eng.device)
+        logits = torch.empty(1 if last_only else S, eng.cfg.vocab_size, dtype=torch.float32, device=eng.device)
+        run_prefill(eng, desc, S, "teo_llama_prefill",
+                    lambda ws, st: eng.lib.teo_llama_prefill(C.byref(desc), _p(e), _p(pos), S, past, 1 if last_only else 0, _p(logits), _p(ws),
+                                                             ws.numel(), st, None))
+    return logits
+
+
+# ---------------------------------------------------------------------- loop state, sampler
+def alloc_loop_state(owner, state, device, out_cap, logits_shape, rows=None):
+    """The device side of a decode loop as attributes of `owner` -- d_token, d_pos, d_out, d_count, d_stop, d_stop_ids, d_logits, d_rng --
+    and the fields of `state` (teo_decode_state / teo_decode_batch_state / teo_verify_state) that point at them, with a greedy sampler and
+    no stop ids.  rows=None: one conversation (d_out [out_cap], d_rng {seed, draws so far}); rows=B: one row per conversation."""
+    n = 1 if rows is None else rows
+    lead = () if rows is None else (rows,)
+    owner.d_token = torch.zeros(n, dtype=torch.int64, device=device)
+    owner.d_pos = torch.zeros(n, dtype=torch.int32, device=device)
+    owner.d_out = torch.zeros(*lead, out_cap, dtype=torch.int64, device=device)
+    owner.d_count = torch.zeros(n, dtype=torch.int32, device=device)
+    owner.d_stop = torch.zeros(n, dtype=torch.int32, device=device)
+    owner.d_stop_ids = torch.zeros(MAX_STOP_IDS, dtype=torch.int64, device=device)
+    owner.d_logits = torch.zeros(*logits_shape, dtype=torch.float32, device=device)
+    owner.d_rng = torch.zeros(*lead, 2, dtype=torch.int64, device=device)
+    for field, t in (("d_token", owner.d_token), ("d_pos", owner.d_pos), ("d_out_tokens", owner.d_out), ("d_out_count", owner.d_count),
+                     ("d_stop", owner.d_stop), ("d_stop_ids", owner.d_stop_ids), ("d_logits", owner.d_logits), ("d_rng", owner.d_rng)):
+        setattr(state, field, t.data_ptr())
+    state.n_stop_ids, state.do_sample, state.top_k, state.temperature, state.top_p = 0, 0, 0, 1.0, 1.0
+
+
+def arm_sampler(state, d_stop_ids, stop_ids, do_sample, temperature, top_k, top_p, extra=()):
+    """Write the stop ids (the last MAX_STOP_IDS of them) and set the sampler fields of `state`, plus `extra` (field, value) pairs.
+    All of these a captured step graph holds by value: returns True when any of them changed -- the caller drops its graphs.  The floats
+    go through c_float so that the comparison is against what the struct can hold."""
+    n = 0
+    if stop_ids:
+        n = min(len(stop_ids), MAX_STOP_IDS)
+        d_stop_ids[:n] = torch.tensor(list(stop_ids)[-n:], dtype=torch.int64, device=d_stop_ids.device)
+    fields = ("n_stop_ids", "do_sample", "top_k", "temperature", "top_p") + tuple(f for f, _ in extra)
+    key = (n, int(bool(do_sample)), int(top_k or 0), C.c_float(float(temperature)).value, C.c_float(float(top_p or 1.0)).value) \
+        + tuple(v for _, v in extra)
+    if key == tuple(getattr(state, f) for f in fields):
+        return False
+    for f, v in zip(fields, key):
+        setattr(state, f, v)
+    return True
+
+
+# ---------------------------------------------------------------------- step graphs
+class StepGraphs:
+    """mixin over `self.lib`: the captured plain step (`_graph`, None when there is none) and the guided step beside it, each with its key
+    -- everything its capture holds by value."""
+
+    def __init__(self):
+        self._graph, self._graph_ws = None, None
+        self._guided_graph, self._guided_key = None, None
+
+    def replay_or_step(self, stream, key, n, use_graph, create, step, guided=False):
+        """n decode steps on the engine's `stream`: plain launches (step()), or replays of the plain (or the guided) graph, captured again
+        by create(out) whenever `key` is not the key of its capture.  The stream is drained behind the replays: replays still outstanding
+        when another command is enqueued run 8 % slower (TeoEngine._Phase.__exit__)."""
+        if not use_graph:
+            for _ in range(n):
+                step()
+            return
+        g_attr, k_attr = ("_guided_graph", "_guided_key") if guided else ("_graph", "_graph_ws")
+        if getattr(self, g_attr) is None or getattr(self, k_attr) != key:
+            self._destroy_graph(g_attr)
+            g = C.c_void_p()
+            create(C.byref(g))
+            setattr(self, g_attr, g)
+            setattr(self, k_attr, key)
+        L.check(self.lib.teo_graph_launch(getattr(self, g_attr), n, C.c_void_p(stream.cuda_stream)), "teo_graph_launch")
+        stream.synchronize()
+
+    def _destroy_graph(self, g_attr):
+        if getattr(self, g_attr) is not None:
+            self.lib.teo_graph_destroy(getattr(self, g_attr))
+            setattr(self, g_attr, None)
+
+    def _drop_graph(self):
+        self._destroy_graph("_graph")
+        self._destroy_graph("_guided_graph")
+
+    def __del__(self):
+        try:
+            self._drop_graph()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def profile_steps(n, step_call):
+    """n profiled steps: step_call(ms, ct) runs one and fills the per-class milliseconds and launch counts (PROF_CLASSES order).
+    Returns {class: (launches per step, mean microseconds per launch)} over the classes that launched."""
+    K = len(PROF_CLASSES)
+    tot, cnt = [0.0] * K, [0] * K
+    ms, ct = (C.c_float * K)(), (C.c_int * K)()
+    for _ in range(n):
+        step_call(ms, ct)
+        for k in range(K):
+            tot[k] += ms[k]
+            cnt[k] += ct[k]
+    return {name: (cnt[k] // n, tot[k] / cnt[k] * 1e3) for k, name in enumerate(PROF_CLASSES) if cnt[k]}
+
+
+# ---------------------------------------------------------------------- engine hooks
+class HookList(list):
+    """Callbacks of an engine (TeoEngine.on_options / on_tune), each held beside a WEAK reference to its owner and called as
+    fn(owner, *args): a hook never keeps its owner alive, and one whose owner is gone is forgotten at the next dispatch."""
+
+    def add(self, owner, fn):
+        if not any(ref() is owner and f is fn for ref, f in self):       # the same hook of the same owner is one hook
+            self.append((weakref.ref(owner), fn))
+
+    def fire(self, *args):
+        self[:] = [h for h in self if h[0]() is not None]
+        for ref, fn in list(self):
+            owner = ref()
+            if owner is not None:
+                fn(owner, *args)
+
+
+def sync_desc_options(src, row_major, tiled=()):
+    """set_options on the engine's LLaMA descriptor `src` reaches its copies: prefill_fp8 and rope_in_attn go to every copy; prefill_w4 /
+    prefill_w4a8 only to the copies whose *_w4 arrays are ROW-MAJOR (prefill descriptors) -- a step descriptor's are tiled and keep 0."""
+    for d in (*row_major, *tiled):
+        d.prefill_fp8, d.rope_in_attn = src.prefill_fp8, src.rope_in_attn
+    for d in row_major:
+        d.prefill_w4, d.prefill_w4a8 = src.prefill_w4, src.prefill_w4a8

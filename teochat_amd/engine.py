@@ -20,10 +20,11 @@ import warnings
 import torch
 
 from . import _lib as L
+from .decode_host import (PROF_CLASSES, SEED_MASK, HookList, PtrArrays, StepGraphs, _p, alloc_loop_state, arm_sampler, profile_steps,
+                          run_prefill, sync_desc_options)
 
 _ACT = {"quick_gelu": L.ACT_QUICK_GELU, "gelu": L.ACT_GELU_ERF}
 VIT_PREFIX = "model.image_tower.image_tower."
-SEED_MASK = 2 ** 63 - 1            # d_rng is int64 on the host side: one mask for the first draw and the device loop
 
 
 def _dt(dtype):
@@ -34,10 +35,6 @@ def _dt(dtype):
     if dtype == torch.float16:
         return L.TEO_F16
     raise ValueError(f"unsupported engine dtype {dtype}; use torch.float32, torch.bfloat16 or torch.float16")
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def tile_weights(W):
@@ -279,33 +276,12 @@ def rope_tables(head_dim, theta, max_pos):
     return fr.cos().contiguous(), fr.sin().contiguous()
 
 
-def replay_or_step(owner, graph_attr, key_attr, key, n, use_graph, st, create, step):
-    """n decode steps of `owner` (an engine or a decoder) on stream st: plain launches (step()), or replays of the graph kept in
-    owner.<graph_attr>, captured again by create(out) whenever `key` -- everything the capture holds by value -- is not owner.<key_attr>.
-    The stream is drained behind the replays: replays still outstanding when another command is enqueued run 8 % slower (_Phase.__exit__)."""
-    if not use_graph:
-        for _ in range(n):
-            step()
-        return
-    lib = owner.lib
-    if getattr(owner, graph_attr) is None or getattr(owner, key_attr) != key:
-        if getattr(owner, graph_attr) is not None:
-            lib.teo_graph_destroy(getattr(owner, graph_attr))
-            setattr(owner, graph_attr, None)
-        g = C.c_void_p()
-        create(C.byref(g))
-        setattr(owner, graph_attr, g)
-        setattr(owner, key_attr, key)
-    L.check(lib.teo_graph_launch(getattr(owner, graph_attr), n, st), "teo_graph_launch")
-    (owner.eng if hasattr(owner, "eng") else owner).stream.synchronize()
-
-
 def guide_graph_key(gd, ws):
     """what a guided graph holds by value: the teo_guide fields and the workspace"""
     return (gd.d_next, gd.n_states, gd.vocab, gd.d_state, gd.fallback_token, ws.data_ptr())
 
 
-class TeoEngine:
+class TeoEngine(StepGraphs, PtrArrays):
     def __init__(self, state_dict, config, dtype=torch.bfloat16, device="cuda:0", max_seq=None, weight_format=None, mxfp4_only=False,
                  decode_pack=True):
         self.lib = L.load()                       # raises TeoLibraryError when the HIP library is missing
@@ -343,12 +319,14 @@ class TeoEngine:
         self._ws = {}
         self._phase_depth = 0
         self._pending_status = {}                 # workspace key -> deferred hand-off check (see _check_handoffs)
-        self._option_hooks = []                   # callables(desc): keep copies of the LLaMA descriptor in step with set_options
-        self._tune_hooks = []                     # callables(): a knob changed -- captured graphs bake kernel choices in and are dropped
-        self._graph, self._graph_ws = None, None
-        # guided decoding (guide_begin): the armed teo_guide and its object, the guided step's graph and what it was captured on, the device
-        # tables kept (guide_table) and the single conversation's automaton state
-        self._guide, self._guide_obj, self._guided_graph, self._guided_key, self._guide_tables = None, None, None, None, []
+        self._option_hooks = HookList()           # fn(owner, desc): keep copies of the LLaMA descriptor in step with set_options (on_options)
+        self._tune_hooks = HookList()             # fn(owner): a knob changed -- captured graphs bake kernel choices in and are dropped (on_tune)
+        StepGraphs.__init__(self)                 # the plain decode step's graph and the guided step's, with what each was captured on
+        self._fwd_slots = None                    # prefill_batch's scratch KV slot
+        self.cache_epoch = 0
+        # guided decoding (guide_begin): the armed teo_guide and its object, the device tables kept (guide_table) and the single
+        # conversation's automaton state
+        self._guide, self._guide_obj, self._guide_tables = None, None, []
         self.d_guide_state = torch.zeros(1, dtype=torch.int32, device=device)
         # performance knobs of THIS engine: a teo_tune block every descriptor points at (include/teo_hip.h); nothing process-wide
         self.tune = L.Tune()
@@ -369,11 +347,6 @@ class TeoEngine:
     # ------------------------------------------------------------------ weights
     def _dev(self, t):
         return t.to(device=self.device, dtype=self.dtype).contiguous()
-
-    def _arr(self, tensors):
-        arr, pp = L.ptr_array([t.data_ptr() for t in tensors])
-        self._keep.append((arr, tensors))
-        return pp
 
     def _load_vit(self, sd):
         v = self.vcfg
@@ -634,22 +607,10 @@ class TeoEngine:
         self.llama_desc = d
 
     def _alloc_decode_state(self, max_new=4096):
-        dev = self.device
-        self.d_token = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.d_pos = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.d_out = torch.zeros(max_new, dtype=torch.int64, device=dev)
-        self.d_count = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.d_stop = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.d_stop_ids = torch.zeros(16, dtype=torch.int64, device=dev)
-        self.d_logits = torch.zeros(self.cfg.vocab_size, dtype=torch.float32, device=dev)
-        self.d_rng = torch.zeros(2, dtype=torch.int64, device=dev)       # {seed, draws so far} of the device sampler
+        self.decode_state = L.DecodeState()
+        alloc_loop_state(self, self.decode_state, self.device, max_new, (self.cfg.vocab_size,))
         self.max_new_cap = max_new
-        s = L.DecodeState()
-        s.d_token, s.d_pos, s.d_out_tokens = self.d_token.data_ptr(), self.d_pos.data_ptr(), self.d_out.data_ptr()
-        s.d_out_count, s.d_stop = self.d_count.data_ptr(), self.d_stop.data_ptr()
-        s.d_stop_ids, s.n_stop_ids, s.d_logits = self.d_stop_ids.data_ptr(), 0, self.d_logits.data_ptr()
-        s.do_sample, s.top_k, s.temperature, s.d_rng, s.top_p = 0, 0, 1.0, self.d_rng.data_ptr(), 1.0
-        self.decode_state = s
+        self.steps_since_begin = 0
 
     # ------------------------------------------------------------------ plumbing
     def _workspace(self, key, nbytes):
@@ -772,7 +733,7 @@ class TeoEngine:
     # ------------------------------------------------------------------ LLaMA
     def reset_cache(self):
         self.cache_len = 0
-        self.cache_epoch = getattr(self, "cache_epoch", 0) + 1     # what generate(prefix_key=) remembers about the cache no longer holds
+        self.cache_epoch += 1                     # what generate(prefix_key=) remembers about the cache no longer holds
 
     def prefill(self, embeds, positions=None, last_only=False, hidden_states=False, attentions=False):
         """embeds [S, D] appended to the cache; returns fp32 logits [S, V] (or [1, V]).  With hidden_states: (logits, hs) where hs is
@@ -784,32 +745,26 @@ class TeoEngine:
         past = self.cache_len
         if past + S > self.max_seq:
             raise ValueError(f"sequence length {past + S} exceeds the engine's max_seq {self.max_seq}")
-        with self.phase() as st:
+        d, lib, last = C.byref(self.llama_desc), self.lib, 1 if last_only else 0
+        with self.phase():
             e = embeds.to(device=self.device, dtype=self.dtype).contiguous()
             if positions is None:
                 pos = torch.arange(past, past + S, dtype=torch.int32, device=self.device)
             else:
                 pos = positions.to(device=self.device, dtype=torch.int32).contiguous()
-            rows = 1 if last_only else S
-            logits = torch.empty(rows, self.cfg.vocab_size, dtype=torch.float32, device=self.device)
-            need = self.lib.teo_llama_prefill_workspace_bytes(C.byref(self.llama_desc), S)
-            self._flush_handoff_checks("prefill")
-            ws = self._workspace("prefill", need)
+            logits = torch.empty(1 if last_only else S, self.cfg.vocab_size, dtype=torch.float32, device=self.device)
             hs = torch.empty(self.cfg.num_hidden_layers + 1, S, self.cfg.hidden_size, dtype=self.dtype, device=self.device) if hidden_states else None
-            att = None
+            hs_p = _p(hs) if hs is not None else None
             if attentions:
                 att = torch.empty(self.cfg.num_hidden_layers, self.cfg.num_attention_heads, S, past + S, dtype=self.dtype, device=self.device)
-                L.check(self.lib.teo_llama_prefill_attentions(C.byref(self.llama_desc), _p(e), _p(pos), S, past, 1 if last_only else 0,
-                                                              _p(logits), _p(ws), ws.numel(), st, _p(hs) if hs is not None else None, _p(att)),
-                        "teo_llama_prefill_attentions")
+                run_prefill(self, self.llama_desc, S, "teo_llama_prefill_attentions",
+                            lambda ws, st: lib.teo_llama_prefill_attentions(d, _p(e), _p(pos), S, past, last, _p(logits), _p(ws), ws.numel(), st,
+                                                                            hs_p, _p(att)))
             else:
-                L.check(self.lib.teo_llama_prefill(C.byref(self.llama_desc), _p(e), _p(pos), S, past, 1 if last_only else 0,
-                                                   _p(logits), _p(ws), ws.numel(), st, _p(hs) if hs is not None else None), "teo_llama_prefill")
-            sid = C.c_void_p(self.stream.cuda_stream)
-            self._check_handoffs("prefill", lambda f: self.lib.teo_llama_prefill_workspace_status(C.byref(self.llama_desc), S, _p(ws), ws.numel(),
-                                                                                                  C.byref(f), sid), "teo_llama_prefill")
+                run_prefill(self, self.llama_desc, S, "teo_llama_prefill",
+                            lambda ws, st: lib.teo_llama_prefill(d, _p(e), _p(pos), S, past, last, _p(logits), _p(ws), ws.numel(), st, hs_p))
         self.cache_len = past + S
-        self.cache_epoch = getattr(self, "cache_epoch", 0) + 1
+        self.cache_epoch += 1
         if attentions:
             return (logits, hs, att) if hidden_states else (logits, att)
         return (logits, hs) if hidden_states else logits
@@ -825,20 +780,15 @@ class TeoEngine:
             raise ValueError(f"{S} branch rows behind {past} cached rows: need 1 <= rows and at most the engine's max_seq {self.max_seq}")
         if len(positions) != S or len(branch_start) != S:
             raise ValueError(f"positions ({len(positions)}) and branch_start ({len(branch_start)}) must name all {S} rows")
-        with self.phase() as st:
+        with self.phase():
             e = embeds.to(device=self.device, dtype=self.dtype).contiguous()
             pos = torch.as_tensor(positions).to(device=self.device, dtype=torch.int32).contiguous()
             bs = torch.as_tensor(branch_start).to(device=self.device, dtype=torch.int32).contiguous()
             logits = torch.empty(S, self.cfg.vocab_size, dtype=torch.float32, device=self.device)
-            need = self.lib.teo_llama_prefill_workspace_bytes(C.byref(self.llama_desc), S)
-            self._flush_handoff_checks("prefill")
-            ws = self._workspace("prefill", need)
-            L.check(self.lib.teo_llama_prefill_branches(C.byref(self.llama_desc), _p(e), _p(pos), _p(bs), S, past, _p(logits), _p(ws), ws.numel(),
-                                                        st), "teo_llama_prefill_branches")
-            sid = C.c_void_p(self.stream.cuda_stream)
-            self._check_handoffs("prefill", lambda f: self.lib.teo_llama_prefill_workspace_status(C.byref(self.llama_desc), S, _p(ws), ws.numel(),
-                                                                                                  C.byref(f), sid), "teo_llama_prefill_branches")
-        self.cache_epoch = getattr(self, "cache_epoch", 0) + 1
+            run_prefill(self, self.llama_desc, S, "teo_llama_prefill_branches",
+                        lambda ws, st: self.lib.teo_llama_prefill_branches(C.byref(self.llama_desc), _p(e), _p(pos), _p(bs), S, past, _p(logits),
+                                                                           _p(ws), ws.numel(), st))
+        self.cache_epoch += 1
         return logits
 
     def token_logprobs(self, logits, rows, labels):
@@ -874,7 +824,7 @@ class TeoEngine:
         # layer's cache pointer aliases ONE [B, Hkv, S64, hd] buffer (S64 = the longest sequence rounded up to the 64-key tile of the
         # flash kernel), sized by what is asked for, not by the engine's max_seq: 7B at B = 16, S = 4096 is 3 x 0.5 GB instead of 3 x 17 GB
         S64 = (max(lens) + 63) // 64 * 64
-        slot = getattr(self, "_fwd_slots", None)
+        slot = self._fwd_slots
         if slot is None or slot["B"] < B or slot["S"] < S64:
             # regrow to the maximum of the old and the new shape (alternating (B = 4, S = 64) / (B = 2, S = 128) calls must not
             # reallocate every time); the pointer arrays of the slot live in the slot, not in the engine-lifetime `_keep` list, so a
@@ -888,31 +838,25 @@ class TeoEngine:
             arrs = [L.ptr_array([t.data_ptr()] * Lr) for t in (kv[0][0], kv[1][0], vt[0])]
             d.k_cache, d.v_cache, d.vt_cache = arrs[0][1], arrs[1][1], arrs[2][1]
             slot = self._fwd_slots = {"B": Bn, "S": Sn, "k": kv[0], "v": kv[1], "vt": vt, "desc": d, "arrs": arrs, "tune": self.tune}
-
-            def _sync(src, eng=self):                 # ONE hook for whatever descriptor copy is current (a regrow replaces the copy, not the hook)
-                cur = getattr(eng, "_fwd_slots", None)
-                if cur is not None:
-                    cur["desc"].prefill_fp8, cur["desc"].rope_in_attn = src.prefill_fp8, src.rope_in_attn
-                    cur["desc"].prefill_w4 = src.prefill_w4          # (a copy of the engine's descriptor: row-major *_w4 arrays)
-                    cur["desc"].prefill_w4a8 = src.prefill_w4a8
-            if not getattr(self, "_fwd_hooked", False):
-                self._option_hooks.append(_sync)
-                self._fwd_hooked = True
+            self.on_options(self, TeoEngine._sync_fwd_slot)
         d = slot["desc"]
         total = sum(lens)
-        with self.phase() as st:
+        with self.phase():
             rows = torch.cat([e.to(device=self.device, dtype=self.dtype) for e in embeds_list], dim=0).contiguous()
             logits = torch.empty(total, c.vocab_size, dtype=torch.float32, device=self.device)
-            self._flush_handoff_checks("prefill")
-            ws = self._workspace("prefill", self.lib.teo_llama_prefill_workspace_bytes(C.byref(d), total))
             arr = (C.c_int * B)(*lens)
             hs = torch.empty(c.num_hidden_layers + 1, total, c.hidden_size, dtype=self.dtype, device=self.device) if hidden_states else None
-            L.check(self.lib.teo_llama_prefill_batch(C.byref(d), _p(rows), arr, B, slot["k"].stride(0), 0, _p(logits), _p(ws), ws.numel(), st,
-                                                     _p(hs) if hs is not None else None), "teo_llama_prefill_batch")
-            sid = C.c_void_p(self.stream.cuda_stream)
-            self._check_handoffs("prefill", lambda f: self.lib.teo_llama_prefill_workspace_status(C.byref(d), total, _p(ws), ws.numel(), C.byref(f), sid),
-                                 "teo_llama_prefill_batch")
+            run_prefill(self, d, total, "teo_llama_prefill_batch",
+                        lambda ws, st: self.lib.teo_llama_prefill_batch(C.byref(d), _p(rows), arr, B, slot["k"].stride(0), 0, _p(logits), _p(ws),
+                                                                        ws.numel(), st, _p(hs) if hs is not None else None))
         return (logits, hs) if hidden_states else logits
+
+    @staticmethod
+    def _sync_fwd_slot(eng, src):
+        """ONE option hook for whatever descriptor copy prefill_batch's slot holds (a regrow replaces the copy, not the hook; registering
+        it again is no second hook); the copy's *_w4 arrays are the engine's: row-major"""
+        if eng._fwd_slots is not None:
+            sync_desc_options(src, [eng._fwd_slots["desc"]])
 
     def sample(self, logits, temperature, top_k, seed, draw, top_p=1.0):
         """One draw of the device sampler (temperature -> top-k -> softmax -> multinomial) from fp32 logits [V]."""
@@ -934,15 +878,8 @@ class TeoEngine:
             self.d_rng[0] = int(seed) & SEED_MASK            # the same 63-bit seed teo_sample_topk gets for draw 0
             self.steps_since_begin = 0
             self.d_rng[1] = int(draws_done)
-            n = 0
-            if stop_ids:
-                n = min(len(stop_ids), 16)
-                self.d_stop_ids[:n] = torch.tensor(list(stop_ids)[-n:], dtype=torch.int64, device=self.device)
-            s = self.decode_state
-            key = (n, int(bool(do_sample)), int(top_k or 0), C.c_float(float(temperature)).value, C.c_float(float(top_p or 1.0)).value)
-            if key != (s.n_stop_ids, s.do_sample, s.top_k, float(s.temperature), float(s.top_p)):
-                s.n_stop_ids, s.do_sample, s.top_k, s.temperature, s.top_p = key     # baked into the captured launch: re-capture
-                self._drop_graph()
+            if arm_sampler(self.decode_state, self.d_stop_ids, stop_ids, do_sample, temperature, top_k, top_p):
+                self._drop_graph()                # baked into the captured launch: re-capture
         ws = self._workspace("decode", self.lib.teo_llama_decode_workspace_bytes(C.byref(self.llama_desc)))
         with self.phase() as st:
             L.check(self.lib.teo_llama_decode_begin(C.byref(self.llama_desc), C.byref(self.decode_state), _p(ws), ws.numel(),
@@ -1001,8 +938,7 @@ class TeoEngine:
                 raise ValueError("batch_mxfp4 needs weight_format='mxfp4' (the MXFP4 weight copies)")
             if bool(batch_mxfp4) != self.batch_mxfp4:
                 self.batch_mxfp4 = bool(batch_mxfp4)
-                for hook in self._tune_hooks:     # a captured batched step belongs to the decoder built under the old setting
-                    hook()
+                self._tune_hooks.fire()           # a captured batched step belongs to the decoder built under the old setting
         if prefill_fp8 is not None:
             if prefill_fp8 and self.llama_w8 is None:
                 raise ValueError("prefill_fp8 needs weight_format='fp8' (the e4m3 weight copies)")
@@ -1010,30 +946,27 @@ class TeoEngine:
         if rope_in_attn is not None and int(bool(rope_in_attn)) != d.rope_in_attn:
             d.rope_in_attn = 1 if rope_in_attn else 0
             self._drop_graph()                    # the placement is baked into the captured decode step
-        for hook in getattr(self, "_option_hooks", []):
-            hook(d)
+        self._option_hooks.fire(d)
+
+    def on_options(self, owner, fn):
+        """fn(owner, desc) after every set_options, for as long as `owner` lives (held weakly): keeps descriptor copies in step"""
+        self._option_hooks.add(owner, fn)
+
+    def on_tune(self, owner, fn):
+        """fn(owner) whenever a knob (or batch_mxfp4) changed, for as long as `owner` lives (held weakly): drops captured graphs"""
+        self._tune_hooks.add(owner, fn)
 
     def tune_set(self, key, value):
         """A performance knob of THIS engine (teo_tune_set on the engine's own block; keys in include/teo_hip.h).  Captured decode
         graphs keep the kernel choices of their capture, so they are dropped."""
         self.tune.set(key, value)                 # raises TeoError on an unknown key / rejected value
         self._drop_graph()
-        for hook in self._tune_hooks:
-            hook()
+        self._tune_hooks.fire()
 
     def tune_reset(self):
         self.tune.reset()
         self._drop_graph()
-        for hook in self._tune_hooks:
-            hook()
-
-    def _drop_graph(self):
-        if self._graph is not None:
-            self.lib.teo_graph_destroy(self._graph)
-            self._graph = None
-        if self._guided_graph is not None:
-            self.lib.teo_graph_destroy(self._guided_graph)
-            self._guided_graph = None
+        self._tune_hooks.fire()
 
     # ------------------------------------------------------------------ guided decoding (include/teo_hip_guide.h, teochat_amd/guide.py)
     GUIDE_TABLES_KEPT = 4
@@ -1097,7 +1030,7 @@ class TeoEngine:
         """Run n greedy steps on the device (hipGraph replay by default).  The caller bounds n by max_seq."""
         if self.cache_len + n > self.max_seq:
             raise ValueError(f"decode would exceed max_seq {self.max_seq}")
-        if getattr(self, "steps_since_begin", 0) + n > self.max_new_cap:
+        if self.steps_since_begin + n > self.max_new_cap:
             raise ValueError(f"decode_steps: {self.steps_since_begin + n} tokens since decode_begin exceed the output buffer "
                              f"({self.max_new_cap}); call decode_begin again or build the engine with a larger max_new")
         ws = self._workspace("decode", self.lib.teo_llama_decode_workspace_bytes(C.byref(self.llama_desc)))
@@ -1107,50 +1040,37 @@ class TeoEngine:
             if gd is not None:
                 # the guided step (include/teo_hip_guide.h) and a graph of its own: the plain graph is left alone
                 g_ = C.byref(gd)
-                replay_or_step(self, "_guided_graph", "_guided_key", guide_graph_key(gd, ws), n, use_graph, st,
-                               lambda out: L.check(self.lib.teo_llama_decode_graph_create_guided(d, s_, g_, _p(ws), ws.numel(), st, out),
-                                                   "teo_llama_decode_graph_create_guided"),
-                               lambda: L.check(self.lib.teo_llama_decode_step_guided(d, s_, g_, _p(ws), ws.numel(), st), "teo_llama_decode_step_guided"))
+                self.replay_or_step(self.stream, guide_graph_key(gd, ws), n, use_graph,
+                                    lambda out: L.check(self.lib.teo_llama_decode_graph_create_guided(d, s_, g_, _p(ws), ws.numel(), st, out),
+                                                        "teo_llama_decode_graph_create_guided"),
+                                    lambda: L.check(self.lib.teo_llama_decode_step_guided(d, s_, g_, _p(ws), ws.numel(), st),
+                                                    "teo_llama_decode_step_guided"), guided=True)
             else:
-                replay_or_step(self, "_graph", "_graph_ws", ws.data_ptr(), n, use_graph, st,
-                               lambda out: L.check(self.lib.teo_llama_decode_graph_create(d, s_, _p(ws), ws.numel(), st, out),
-                                                   "teo_llama_decode_graph_create"),
-                               lambda: L.check(self.lib.teo_llama_decode_step(d, s_, _p(ws), ws.numel(), st), "teo_llama_decode_step"))
+                self.replay_or_step(self.stream, ws.data_ptr(), n, use_graph,
+                                    lambda out: L.check(self.lib.teo_llama_decode_graph_create(d, s_, _p(ws), ws.numel(), st, out),
+                                                        "teo_llama_decode_graph_create"),
+                                    lambda: L.check(self.lib.teo_llama_decode_step(d, s_, _p(ws), ws.numel(), st), "teo_llama_decode_step"))
         self.cache_len += n
-        self.steps_since_begin = getattr(self, "steps_since_begin", 0) + n
+        self.steps_since_begin += n
 
-    PROF_CLASSES = ("qkv_rope_gemv", "attn_decode_partial", "attn_decode_combine", "o_gemv", "gateup_gemv", "down_gemv", "lm_head_gemv",
-                    "decode_tail")
+    PROF_CLASSES = PROF_CLASSES
 
     def decode_steps_profiled(self, n):
         """n decode steps as plain launches, every kernel timed by its own dispatch timestamps (teo_llama_decode_step_profile).
         Returns {class: (launches per step, mean microseconds per launch)}; advances the cache like decode_steps."""
         if self.cache_len + n > self.max_seq:
             raise ValueError(f"decode would exceed max_seq {self.max_seq}")
-        if getattr(self, "steps_since_begin", 0) + n > self.max_new_cap:
+        if self.steps_since_begin + n > self.max_new_cap:
             raise ValueError(f"decode_steps_profiled: {self.steps_since_begin + n} tokens since decode_begin exceed the output buffer "
                              f"({self.max_new_cap})")
         ws = self._workspace("decode", self.lib.teo_llama_decode_workspace_bytes(C.byref(self.llama_desc)))
-        K = len(self.PROF_CLASSES)
-        tot, cnt = [0.0] * K, [0] * K
-        ms, ct = (C.c_float * K)(), (C.c_int * K)()
         with self.phase() as st:
-            for _ in range(n):
-                L.check(self.lib.teo_llama_decode_step_profile(C.byref(self.llama_desc), C.byref(self.decode_state), _p(ws), ws.numel(),
-                                                               ms, ct, st), "teo_llama_decode_step_profile")
-                for k in range(K):
-                    tot[k] += ms[k]
-                    cnt[k] += ct[k]
+            prof = profile_steps(n, lambda ms, ct: L.check(self.lib.teo_llama_decode_step_profile(
+                C.byref(self.llama_desc), C.byref(self.decode_state), _p(ws), ws.numel(), ms, ct, st), "teo_llama_decode_step_profile"))
         self.cache_len += n
-        self.steps_since_begin = getattr(self, "steps_since_begin", 0) + n
-        return {name: (cnt[k] // n, tot[k] / cnt[k] * 1e3) for k, name in enumerate(self.PROF_CLASSES) if cnt[k]}
+        self.steps_since_begin += n
+        return prof
 
     def generated(self):
         n = int(self.d_count.item())
         return self.d_out[:n].clone()
-
-    def __del__(self):
-        try:
-            self._drop_graph()
-        except Exception:  # noqa: BLE001
-            pass

@@ -755,7 +755,7 @@ class LlavaLlamaForCausalLM:
     # --- speculative verify steps (prompt lookup): R rows of one conversation per pass over the weights
     def spec_decoder(self, rows, max_new=1024, ngram_max=2):
         from .speculative import SpecDecoder
-        w4 = bool(getattr(self.engine, "batch_mxfp4", False))
+        w4 = bool(self.engine.batch_mxfp4)
         cur = getattr(self, "_spec_decoder", None)
         if cur is None or cur.R != rows or cur.max_new < max_new or cur.ngram_max != ngram_max or cur.w4_requested != w4:
             self._spec_decoder = None           # free the old cache first
@@ -770,7 +770,7 @@ class LlavaLlamaForCausalLM:
     def batch_decoder(self, batch, max_new=1024):
         from .batch import BatchDecoder
         cur = getattr(self, "_batch_decoder", None)
-        if cur is None or cur.B != batch or cur.max_new < max_new or cur.w4_requested != bool(getattr(self.engine, "batch_mxfp4", False)):
+        if cur is None or cur.B != batch or cur.max_new < max_new or cur.w4_requested != bool(self.engine.batch_mxfp4):
             self._batch_decoder = None          # free the old caches first
             cur = BatchDecoder(self.engine, batch, max_new=max(max_new, 64))
             self._batch_decoder = cur

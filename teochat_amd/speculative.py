@@ -11,7 +11,11 @@ rows is `teo_attn_verify` (include/teo_hip.h), bound below as `attn_verify`.
 import ctypes as C
 import math
 
+import torch
+
 from . import _lib as L
+from .batch import BatchDecoder
+from .decode_host import SEED_MASK, PtrArrays, StepGraphs, _p, alloc_loop_state, arm_sampler, prefill_append, profile_steps, sync_desc_options
 
 MAX_ROWS = L.MAX_DECODE_BATCH
 
@@ -80,7 +84,6 @@ def attn_verify(qkv, k_cache, v_cache, vt_cache, rope_cos, rope_sin, d_pos, head
     qkv.stride(0)) for positions d_pos[0] .. d_pos[0] + R - 1 of the conversation whose caches are k_cache / v_cache
     [kv_heads, max_seq, head_dim] and vt_cache [kv_heads, head_dim, max_seq] (or None).  Appends the R rows to the caches and returns
     the attention output [R, heads * head_dim].  d_pos: int32 device tensor (read on the device: graph-replayable)."""
-    import torch
     lib = L.load()
     dts = {torch.float32: L.TEO_F32, torch.bfloat16: L.TEO_BF16, torch.float16: L.TEO_F16}
     R = qkv.shape[0]
@@ -98,7 +101,7 @@ def attn_verify(qkv, k_cache, v_cache, vt_cache, rope_cos, rope_sin, d_pos, head
     return out
 
 
-class SpecDecoder:
+class SpecDecoder(StepGraphs, PtrArrays):
     """Verify-step decoding of ONE conversation on a TeoEngine: R = `rows` tokens per pass over the weights (teo_llama_verify_step).
 
     The weights are BatchDecoder's preparation (tiled bf16 / fp8 copies, or tiled MXFP4 with set_options(batch_mxfp4=True)): pass the
@@ -108,8 +111,6 @@ class SpecDecoder:
     launches, one step at a time, the drafts written by the host: what the tests inject drafts with)."""
 
     def __init__(self, engine, rows, max_new=1024, draft_source="ngram", ngram_max=2, batch_decoder=None):
-        import torch
-        from .batch import BatchDecoder
         if not 1 <= int(rows) <= MAX_ROWS:
             raise ValueError(f"rows {rows} outside 1..{MAX_ROWS}")
         if draft_source != "ngram" and not callable(draft_source):
@@ -145,83 +146,35 @@ class SpecDecoder:
         self.d_hist = torch.zeros(engine.max_seq + self.max_new + 16, dtype=torch.int64, device=dev)
         self.d_hist_len = torch.zeros(1, dtype=torch.int32, device=dev)
         self.d_stats = torch.zeros(3, dtype=torch.int32, device=dev)
-        self.d_token = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.d_pos = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.d_out = torch.zeros(self.max_new, dtype=torch.int64, device=dev)
-        self.d_count = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.d_stop = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.d_stop_ids = torch.zeros(16, dtype=torch.int64, device=dev)
-        self.d_logits = torch.zeros(self.R, c.vocab_size, dtype=torch.float32, device=dev)
-        self.d_rng = torch.zeros(2, dtype=torch.int64, device=dev)
         s = L.VerifyState()
+        alloc_loop_state(self, s, dev, self.max_new, (self.R, c.vocab_size))
         s.rows, s.max_new, s.ngram_max = self.R, self.max_new, self.ngram_max
         s.w_tiled, s.gateup_block8, s.w_mxfp4 = int(bd.tiled), int(bd.block8), int(bd.w4)
-        s.d_rows, s.d_n_draft, s.d_hist, s.d_hist_len = _p(self.d_rows), _p(self.d_n_draft), _p(self.d_hist), _p(self.d_hist_len)
-        s.d_stats, s.d_token, s.d_pos, s.d_out_tokens = _p(self.d_stats), _p(self.d_token), _p(self.d_pos), _p(self.d_out)
-        s.d_out_count, s.d_stop, s.d_stop_ids, s.n_stop_ids = _p(self.d_count), _p(self.d_stop), _p(self.d_stop_ids), 0
-        s.d_logits, s.do_sample, s.top_k, s.temperature, s.d_rng, s.top_p = _p(self.d_logits), 0, 0, 1.0, _p(self.d_rng), 1.0
+        s.d_rows, s.d_n_draft, s.d_hist = self.d_rows.data_ptr(), self.d_n_draft.data_ptr(), self.d_hist.data_ptr()
+        s.d_hist_len, s.d_stats = self.d_hist_len.data_ptr(), self.d_stats.data_ptr()
         self.state = s
-        self._graph = None
+        StepGraphs.__init__(self)
         self._limit = self.max_new
-        import weakref
-        me = weakref.ref(self)
-
-        def _sync_options(src):
-            o = me()
-            if o is not None:
-                for dd in (o.prefill_desc, o.desc):
-                    dd.prefill_fp8, dd.rope_in_attn = src.prefill_fp8, src.rope_in_attn
-                o.prefill_desc.prefill_w4, o.prefill_desc.prefill_w4a8 = src.prefill_w4, src.prefill_w4a8
-        engine._option_hooks.append(_sync_options)
-
-        def _knob_changed():
-            o = me()
-            if o is not None:
-                o._drop_graph()
-        engine._tune_hooks.append(_knob_changed)
-
-    def _arr(self, tensors):
-        arr, pp = L.ptr_array([t.data_ptr() for t in tensors])
-        self._keep.append((arr, tensors))
-        return pp
+        # set_options reaches both copies (the prefill descriptor's *_w4 arrays are row-major, the step descriptor's tiled); a knob drops the graph
+        engine.on_options(self, lambda o, src: sync_desc_options(src, [o.prefill_desc], [o.desc]))
+        engine.on_tune(self, SpecDecoder._drop_graph)
 
     def reset(self):
         self.cache_len = 0
 
     def prefill(self, embeds, last_only=True):
         """Append embeds [S, D] to the conversation; returns fp32 logits ([1, V] with last_only)."""
-        import torch
-        eng, d = self.eng, self.prefill_desc
-        S, past = embeds.shape[0], self.cache_len
-        if past + S > eng.max_seq:
-            raise ValueError(f"sequence length {past + S} exceeds the engine's max_seq {eng.max_seq}")
-        with eng.phase() as st:
-            e = embeds.to(device=eng.device, dtype=eng.dtype).contiguous()
-            pos = torch.arange(past, past + S, dtype=torch.int32, device=eng.device)
-            logits = torch.empty(1 if last_only else S, eng.cfg.vocab_size, dtype=torch.float32, device=eng.device)
-            eng._flush_handoff_checks("prefill")
-            ws = eng._workspace("prefill", self.lib.teo_llama_prefill_workspace_bytes(C.byref(d), S))
-            L.check(self.lib.teo_llama_prefill(C.byref(d), _p(e), _p(pos), S, past, 1 if last_only else 0, _p(logits), _p(ws), ws.numel(),
-                                               st, None), "teo_llama_prefill")
-            sid = C.c_void_p(eng.stream.cuda_stream)
-            eng._check_handoffs("prefill", lambda f: self.lib.teo_llama_prefill_workspace_status(C.byref(d), S, _p(ws), ws.numel(), C.byref(f), sid),
-                                "teo_llama_prefill")
-        self.cache_len = past + S
+        logits = prefill_append(self.eng, self.prefill_desc, embeds, self.cache_len, last_only)
+        self.cache_len += embeds.shape[0]
         return logits
 
     def _workspace(self):
         return self.eng._workspace("verify", self.lib.teo_llama_verify_workspace_bytes(C.byref(self.desc), self.R))
 
-    def _drop_graph(self):
-        if self._graph is not None:
-            self.lib.teo_graph_destroy(self._graph)
-            self._graph = None
-
     def begin(self, first_token, history, stop_ids=None, do_sample=False, temperature=1.0, top_k=0, seed=0, draws_done=1, top_p=1.0,
               max_new=None):
         """Arm the loop: `first_token` is the pending token (position cache_len), `history` the ids the proposer searches -- the prompt
         as the caller passed it (sentinels included) with first_token at its end.  At most `max_new` tokens are emitted by the steps."""
-        import torch
         eng = self.eng
         limit = self.max_new if max_new is None else int(max_new)
         if not 1 <= limit <= self.max_new:
@@ -239,15 +192,8 @@ class SpecDecoder:
             self.d_hist_len.fill_(len(hist))
             for t in (self.d_n_draft, self.d_stats, self.d_count, self.d_stop):
                 t.zero_()
-            self.d_rng.copy_(torch.tensor([int(seed) & (2 ** 63 - 1), int(draws_done)], dtype=torch.int64))
-            n = 0
-            if stop_ids:
-                n = min(len(stop_ids), 16)
-                self.d_stop_ids[:n] = torch.tensor(list(stop_ids)[-n:], dtype=torch.int64, device=eng.device)
-            s = self.state
-            key = (n, int(bool(do_sample)), int(top_k or 0), C.c_float(float(temperature)).value, C.c_float(float(top_p or 1.0)).value, limit)
-            if key != (s.n_stop_ids, s.do_sample, s.top_k, float(s.temperature), float(s.top_p), s.max_new):
-                s.n_stop_ids, s.do_sample, s.top_k, s.temperature, s.top_p, s.max_new = key
+            self.d_rng.copy_(torch.tensor([int(seed) & SEED_MASK, int(draws_done)], dtype=torch.int64))
+            if arm_sampler(self.state, self.d_stop_ids, stop_ids, do_sample, temperature, top_k, top_p, extra=(("max_new", limit),)):
                 self._drop_graph()
         self._limit = limit
         self._pos0 = self.cache_len
@@ -259,7 +205,6 @@ class SpecDecoder:
 
     def _host_drafts(self):
         """drafts of a host callable for the next step, written over the proposer's"""
-        import torch
         n = int(self.d_hist_len.item())
         drafts = [int(t) for t in self.draft_source(self.d_hist[:n].tolist())][:self.R - 1]
         rows = [int(self.d_rows[0].item())] * self.R
@@ -272,45 +217,31 @@ class SpecDecoder:
         reads position, count and stats afterwards.  Returns the number of tokens emitted so far."""
         eng = self.eng
         ws = self._workspace()
+        d, s_ = C.byref(self.desc), C.byref(self.state)
         with eng.phase() as st:
+            def step():
+                L.check(self.lib.teo_llama_verify_step(d, s_, _p(ws), ws.numel(), st), "teo_llama_verify_step")
             if callable(self.draft_source):
                 for _ in range(n):
-                    L.check(self.lib.teo_llama_verify_step(C.byref(self.desc), C.byref(self.state), _p(ws), ws.numel(), st), "teo_llama_verify_step")
+                    step()
                     if int(self.d_stop.item()):
                         break
                     self._host_drafts()
-            elif use_graph:
-                if self._graph is None or self._graph_ws != ws.data_ptr():
-                    self._drop_graph()
-                    g = C.c_void_p()
-                    L.check(self.lib.teo_llama_verify_graph_create(C.byref(self.desc), C.byref(self.state), _p(ws), ws.numel(), st, C.byref(g)),
-                            "teo_llama_verify_graph_create")
-                    self._graph, self._graph_ws = g, ws.data_ptr()
-                L.check(self.lib.teo_graph_launch(self._graph, n, st), "teo_graph_launch")
-                eng.stream.synchronize()
             else:
-                for _ in range(n):
-                    L.check(self.lib.teo_llama_verify_step(C.byref(self.desc), C.byref(self.state), _p(ws), ws.numel(), st), "teo_llama_verify_step")
+                self.replay_or_step(eng.stream, ws.data_ptr(), n, use_graph,
+                                    lambda out: L.check(self.lib.teo_llama_verify_graph_create(d, s_, _p(ws), ws.numel(), st, out),
+                                                        "teo_llama_verify_graph_create"), step)
             self.cache_len = int(self.d_pos.item())
             return int(self.d_count.item())
 
     def steps_profiled(self, n):
         """n verify steps as plain launches with every kernel timed (teo_llama_verify_step_profile): {class: (launches per step, mean us)}."""
-        from .engine import TeoEngine
-        names = TeoEngine.PROF_CLASSES
-        K = len(names)
-        tot, cnt = [0.0] * K, [0] * K
-        ms, ct = (C.c_float * K)(), (C.c_int * K)()
         ws = self._workspace()
         with self.eng.phase() as st:
-            for _ in range(n):
-                L.check(self.lib.teo_llama_verify_step_profile(C.byref(self.desc), C.byref(self.state), _p(ws), ws.numel(), ms, ct, st),
-                        "teo_llama_verify_step_profile")
-                for k in range(K):
-                    tot[k] += ms[k]
-                    cnt[k] += ct[k]
+            prof = profile_steps(n, lambda ms, ct: L.check(self.lib.teo_llama_verify_step_profile(
+                C.byref(self.desc), C.byref(self.state), _p(ws), ws.numel(), ms, ct, st), "teo_llama_verify_step_profile"))
             self.cache_len = int(self.d_pos.item())
-        return {name: (cnt[k] // n, tot[k] / cnt[k] * 1e3) for k, name in enumerate(names) if cnt[k]}
+        return prof
 
     def stopped(self):
         return bool(int(self.d_stop.item()))
@@ -322,13 +253,3 @@ class SpecDecoder:
     def stats(self):
         st = self.d_stats.tolist()
         return {"steps": st[0], "proposed": st[1], "accepted": st[2], "emitted": int(self.d_count.item())}
-
-    def __del__(self):
-        try:
-            self._drop_graph()
-        except Exception:  # noqa: BLE001
-            pass
-
-
-def _p(t):
-    return t.data_ptr()

@@ -16,22 +16,23 @@ from collections import deque
 import torch
 
 from . import _lib as L
-from .engine import _p, guide_graph_key, replay_or_step
+from .batch import BatchDecoder
+from .decode_host import SEED_MASK, StepGraphs, _p, arm_sampler, run_prefill
+from .engine import guide_graph_key
 
 SEED_STRIDE = 0x9E3779B97F4A7C15              # request i draws from the Philox stream seeded (base + i * SEED_STRIDE) mod 2^63
 
 
 def request_seed(base_seed, i):
-    return (int(base_seed) + SEED_STRIDE * int(i)) & (2 ** 63 - 1)
+    return (int(base_seed) + SEED_STRIDE * int(i)) & SEED_MASK
 
 
-class StreamDecoder:
+class StreamDecoder(StepGraphs):
     """`slots` conversation slots over one engine.  batch_decoder: a BatchDecoder of that engine with B == slots whose caches, per-slot
     descriptors and tiled weight copies are borrowed (no second copy of the weights; its own begin()/steps() state is invalidated by a
     refill here); left out, one is created and owned."""
 
     def __init__(self, engine, slots, max_new=1024, batch_decoder=None):
-        from .batch import BatchDecoder
         slots = int(slots)
         if not 1 <= slots <= L.MAX_DECODE_BATCH:
             raise ValueError(f"slots {slots} outside 1..{L.MAX_DECODE_BATCH}")
@@ -53,23 +54,16 @@ class StreamDecoder:
         s.n_stop_ids, s.do_sample, s.top_k, s.temperature, s.top_p = 0, 0, 0, 1.0, 1.0
         s.d_limit = self.d_limit.data_ptr()
         self.state = s
-        self._graph = None
-        self._graph_ws = None
+        StepGraphs.__init__(self)
         # guided decoding (include/teo_hip_guide.h): one automaton state per slot, owned here for the decoder's life -- the guided graph
         # holds its address -- and the teo_guide of the set in force (set_guide), with a graph of its own beside the plain one
         self.d_guide_state = torch.zeros(slots, dtype=torch.int32, device=dev)
-        self._guide, self._guide_obj, self._guided_graph, self._guided_key = None, None, None, None
+        self._guide, self._guide_obj = None, None
         # the step's workspace holds the slots' residual rows BETWEEN steps: this decoder's own, never a buffer another decoder writes
         self._ws = torch.empty(max(int(self.lib.teo_llama_decode_stream_workspace_bytes(C.byref(bd.desc), slots)), 256), dtype=torch.uint8, device=dev)
-        import weakref
-        me = weakref.ref(self)
-
-        def _changed(*_):                        # a knob (tune_set) or an option (set_options): the captured step keeps its capture's choices
-            o = me()
-            if o is not None:
-                o._drop_graph()
-        engine._tune_hooks.append(_changed)
-        engine._option_hooks.append(_changed)
+        # a knob (tune_set) or an option (set_options): the captured step keeps its capture's choices
+        engine.on_tune(self, StreamDecoder._drop_graph)
+        engine.on_options(self, lambda o, _desc: o._drop_graph())
         self.reset()
 
     # ------------------------------------------------------------------ state
@@ -96,16 +90,9 @@ class StreamDecoder:
 
     def configure(self, stop_ids=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0):
         """The step's shared options: the device stop (an id sequence every live slot stops on, or None) and the sampler."""
-        s, bd = self.state, self.bd
-        n = 0
         with self.eng.phase():
-            if stop_ids:
-                n = min(len(stop_ids), 16)
-                bd.d_stop_ids[:n] = torch.tensor(list(stop_ids)[-n:], dtype=torch.int64, device=self.eng.device)
-        key = (n, int(bool(do_sample)), int(top_k or 0), C.c_float(float(temperature)).value, C.c_float(float(top_p or 1.0)).value)
-        if key != (s.n_stop_ids, s.do_sample, s.top_k, float(s.temperature), float(s.top_p)):
-            s.n_stop_ids, s.do_sample, s.top_k, s.temperature, s.top_p = key
-            self._drop_graph()
+            if arm_sampler(self.state, self.bd.d_stop_ids, stop_ids, do_sample, temperature, top_k, top_p):
+                self._drop_graph()
 
     def _workspace(self):
         return self._ws
@@ -122,14 +109,6 @@ class StreamDecoder:
         hg = ws[row:row + self.B * D * e].view(self.eng.dtype).view(self.B, D)
         ssq = ws[2 * row:2 * row + self.B * nparts * 4].view(torch.float32).view(self.B, nparts)
         return h, hg, ssq
-
-    def _drop_graph(self):
-        if self._graph is not None:
-            self.lib.teo_graph_destroy(self._graph)
-            self._graph = None
-        if self._guided_graph is not None:
-            self.lib.teo_graph_destroy(self._guided_graph)
-            self._guided_graph = None
 
     # ------------------------------------------------------------------ guided decoding
     def set_guide(self, guide):
@@ -156,68 +135,51 @@ class StreamDecoder:
     def refill(self, slot_list, embeds_list, last_only=True):
         """Prefill embeds_list[i] ([S_i, D]) into cache slot slot_list[i] from position 0: ONE pass over the weights for all of them
         (teo_llama_prefill_slots).  Returns the fp32 last-position logits [len(slot_list), V]."""
-        eng, bd = self.eng, self.bd
-        slot_list = [int(s) for s in slot_list]
-        if len(slot_list) != len(embeds_list) or not slot_list:
-            raise ValueError("refill: one sequence per slot, at least one")
-        if len(set(slot_list)) != len(slot_list) or min(slot_list) < 0 or max(slot_list) >= self.B:
-            raise ValueError(f"refill: slots {slot_list} are not distinct numbers in 0..{self.B - 1}")
-        if any(self.live[s] for s in slot_list):
-            raise ValueError(f"refill: slot(s) {[s for s in slot_list if self.live[s]]} are live")
-        lens = [int(e.shape[0]) for e in embeds_list]
-        if min(lens) < 1 or max(lens) > eng.max_seq:
-            raise ValueError(f"sequence lengths {lens} outside 1..max_seq {eng.max_seq}")
-        total, n = sum(lens), len(lens)
-        with eng.phase() as st:
-            rows = torch.cat([e.to(device=eng.device, dtype=eng.dtype) for e in embeds_list], dim=0).contiguous()
-            logits = torch.empty(n if last_only else total, eng.cfg.vocab_size, dtype=torch.float32, device=eng.device)
-            eng._flush_handoff_checks("prefill")
-            d0 = bd.slot_desc[0]
-            ws = eng._workspace("prefill", self.lib.teo_llama_prefill_workspace_bytes(C.byref(d0), total))
-            L.check(self.lib.teo_llama_prefill_slots(C.byref(d0), _p(rows), (C.c_int * n)(*lens), (C.c_int * n)(*slot_list), n,
-                                                     bd.k_cache.stride(1), 1 if last_only else 0, _p(logits), _p(ws), ws.numel(), st, None),
-                    "teo_llama_prefill_slots")
-            sid = C.c_void_p(eng.stream.cuda_stream)
-            eng._check_handoffs("prefill", lambda f: self.lib.teo_llama_prefill_workspace_status(C.byref(d0), total, _p(ws), ws.numel(), C.byref(f), sid),
-                                "teo_llama_prefill_slots")
-        for s, n_ in zip(slot_list, lens):
-            bd.cache_len[s] = n_
-            self.held[s] = None                  # what the slot held is overwritten; the scheduler records what it holds now
-        bd._armed = False
-        self._stats["prefill_passes"] += 1
-        return logits
+        return self._refill("refill", slot_list, embeds_list, None, last_only)
 
     def refill_past(self, slot_list, embeds_list, pasts, last_only=True):
         """refill() behind a past per slot: embeds_list[i] ([S_i, D]) is appended to cache slot slot_list[i] at positions pasts[i] ..
         pasts[i] + S_i - 1, rows [0, pasts[i]) being what the slot holds (its own earlier prefill or a fork()): ONE pass over the weights
         (teo_llama_prefill_slots_past, include/teo_hip_prefix.h).  Returns the fp32 last-position logits [len(slot_list), V]."""
-        eng, bd = self.eng, self.bd
-        slot_list, pasts = [int(s) for s in slot_list], [int(p) for p in pasts]
-        if not (len(slot_list) == len(embeds_list) == len(pasts)) or not slot_list:
+        return self._refill("refill_past", slot_list, embeds_list, [int(p) for p in pasts], last_only)
+
+    def _refill(self, name, slot_list, embeds_list, pasts, last_only):
+        """the body of refill (pasts is None: every sequence from position 0) and refill_past; `name` prefixes the error texts"""
+        eng, bd, lib = self.eng, self.bd, self.lib
+        slot_list = [int(s) for s in slot_list]
+        if pasts is None:
+            if len(slot_list) != len(embeds_list) or not slot_list:
+                raise ValueError("refill: one sequence per slot, at least one")
+        elif not (len(slot_list) == len(embeds_list) == len(pasts)) or not slot_list:
             raise ValueError("refill_past: one sequence and one past per slot, at least one")
         if len(set(slot_list)) != len(slot_list) or min(slot_list) < 0 or max(slot_list) >= self.B:
-            raise ValueError(f"refill_past: slots {slot_list} are not distinct numbers in 0..{self.B - 1}")
+            raise ValueError(f"{name}: slots {slot_list} are not distinct numbers in 0..{self.B - 1}")
         if any(self.live[s] for s in slot_list):
-            raise ValueError(f"refill_past: slot(s) {[s for s in slot_list if self.live[s]]} are live")
+            raise ValueError(f"{name}: slot(s) {[s for s in slot_list if self.live[s]]} are live")
         lens = [int(e.shape[0]) for e in embeds_list]
-        if min(lens) < 1 or min(pasts) < 0 or max(p + n_ for p, n_ in zip(pasts, lens)) > eng.max_seq:
+        if pasts is None:
+            if min(lens) < 1 or max(lens) > eng.max_seq:
+                raise ValueError(f"sequence lengths {lens} outside 1..max_seq {eng.max_seq}")
+        elif min(lens) < 1 or min(pasts) < 0 or max(p + n_ for p, n_ in zip(pasts, lens)) > eng.max_seq:
             raise ValueError(f"pasts {pasts} + sequence lengths {lens} outside 1..max_seq {eng.max_seq}")
         total, n = sum(lens), len(lens)
-        with eng.phase() as st:
+        with eng.phase():
             rows = torch.cat([e.to(device=eng.device, dtype=eng.dtype) for e in embeds_list], dim=0).contiguous()
             logits = torch.empty(n if last_only else total, eng.cfg.vocab_size, dtype=torch.float32, device=eng.device)
-            eng._flush_handoff_checks("prefill")
-            d0 = bd.slot_desc[0]
-            ws = eng._workspace("prefill", self.lib.teo_llama_prefill_workspace_bytes(C.byref(d0), total))
-            L.check(self.lib.teo_llama_prefill_slots_past(C.byref(d0), _p(rows), (C.c_int * n)(*lens), (C.c_int * n)(*pasts),
-                                                          (C.c_int * n)(*slot_list), n, bd.k_cache.stride(1), 1 if last_only else 0, _p(logits),
-                                                          _p(ws), ws.numel(), st, None), "teo_llama_prefill_slots_past")
-            sid = C.c_void_p(eng.stream.cuda_stream)
-            eng._check_handoffs("prefill", lambda f: self.lib.teo_llama_prefill_workspace_status(C.byref(d0), total, _p(ws), ws.numel(), C.byref(f), sid),
-                                "teo_llama_prefill_slots_past")
-        for s, p, n_ in zip(slot_list, pasts, lens):
+            d0, stride, last = C.byref(bd.slot_desc[0]), bd.k_cache.stride(1), 1 if last_only else 0
+            c_lens, c_slots = (C.c_int * n)(*lens), (C.c_int * n)(*slot_list)
+            if pasts is None:
+                run_prefill(eng, bd.slot_desc[0], total, "teo_llama_prefill_slots",
+                            lambda ws, st: lib.teo_llama_prefill_slots(d0, _p(rows), c_lens, c_slots, n, stride, last, _p(logits), _p(ws),
+                                                                       ws.numel(), st, None))
+            else:
+                c_pasts = (C.c_int * n)(*pasts)
+                run_prefill(eng, bd.slot_desc[0], total, "teo_llama_prefill_slots_past",
+                            lambda ws, st: lib.teo_llama_prefill_slots_past(d0, _p(rows), c_lens, c_pasts, c_slots, n, stride, last, _p(logits),
+                                                                            _p(ws), ws.numel(), st, None))
+        for s, p, n_ in zip(slot_list, pasts or [0] * n, lens):
             bd.cache_len[s] = p + n_
-            self.held[s] = None
+            self.held[s] = None                  # what the slot held is overwritten; the scheduler records what it holds now
         bd._armed = False
         self._stats["prefill_passes"] += 1
         return logits
@@ -260,7 +222,7 @@ class StreamDecoder:
             bd.d_count[slot] = 0
             bd.d_stop[slot] = 0
             self.d_limit[slot] = limit
-            bd.d_rng[slot] = torch.tensor([int(seed) & (2 ** 63 - 1), int(draws_done)], dtype=torch.int64, device=eng.device)
+            bd.d_rng[slot] = torch.tensor([int(seed) & SEED_MASK, int(draws_done)], dtype=torch.int64, device=eng.device)
             L.check(self.lib.teo_llama_decode_stream_arm(C.byref(bd.desc), C.byref(self.state), slot, _p(ws), ws.numel(), st),
                     "teo_llama_decode_stream_arm")
         self.live[slot] = True
@@ -279,16 +241,17 @@ class StreamDecoder:
             if gd is not None:
                 # the guided step (include/teo_hip_guide.h) and a graph of its own beside the plain one
                 g_ = C.byref(gd)
-                replay_or_step(self, "_guided_graph", "_guided_key", guide_graph_key(gd, ws), n, use_graph, st,
-                               lambda out: L.check(self.lib.teo_llama_decode_stream_graph_create_guided(d, s_, g_, _p(ws), ws.numel(), st, out),
-                                                   "teo_llama_decode_stream_graph_create_guided"),
-                               lambda: L.check(self.lib.teo_llama_decode_stream_step_guided(d, s_, g_, _p(ws), ws.numel(), st),
-                                               "teo_llama_decode_stream_step_guided"))
+                self.replay_or_step(eng.stream, guide_graph_key(gd, ws), n, use_graph,
+                                    lambda out: L.check(self.lib.teo_llama_decode_stream_graph_create_guided(d, s_, g_, _p(ws), ws.numel(), st, out),
+                                                        "teo_llama_decode_stream_graph_create_guided"),
+                                    lambda: L.check(self.lib.teo_llama_decode_stream_step_guided(d, s_, g_, _p(ws), ws.numel(), st),
+                                                    "teo_llama_decode_stream_step_guided"), guided=True)
             else:
-                replay_or_step(self, "_graph", "_graph_ws", ws.data_ptr(), n, use_graph, st,
-                               lambda out: L.check(self.lib.teo_llama_decode_stream_graph_create(d, s_, _p(ws), ws.numel(), st, out),
-                                                   "teo_llama_decode_stream_graph_create"),
-                               lambda: L.check(self.lib.teo_llama_decode_stream_step(d, s_, _p(ws), ws.numel(), st), "teo_llama_decode_stream_step"))
+                self.replay_or_step(eng.stream, ws.data_ptr(), n, use_graph,
+                                    lambda out: L.check(self.lib.teo_llama_decode_stream_graph_create(d, s_, _p(ws), ws.numel(), st, out),
+                                                        "teo_llama_decode_stream_graph_create"),
+                                    lambda: L.check(self.lib.teo_llama_decode_stream_step(d, s_, _p(ws), ws.numel(), st),
+                                                    "teo_llama_decode_stream_step"))
         self._stats["steps"] += n
         self._stats["slot_steps"] += n * self.B
 
@@ -332,12 +295,6 @@ class StreamDecoder:
 
     def stats(self):
         return dict(self._stats)
-
-    def __del__(self):
-        try:
-            self._drop_graph()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 def reusable_prefix(ids, record, min_prefix_rows=64):
