@@ -269,6 +269,24 @@ _SIGS_GUIDE = {
                                                               C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
 }
 EXPORTS_GUIDE = tuple(_SIGS_GUIDE.keys())
+
+
+# include/teo_hip_share.h: shared-prefix decode attention -- forked cache rows read once per group of slots, a fifth header of the same library
+class Share(C.Structure):
+    _fields_ = [("d_lead", C.c_void_p), ("d_rows", C.c_void_p)]
+
+
+_SIGS_SHARE = {
+    "teo_share_sizeof": (C.c_size_t, []),
+    "teo_attn_decode_shared": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_int, C.c_longlong, C.c_longlong,
+                                                                             C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "teo_attn_decode_chunk": (C.c_int, [C.c_int] * 5 + [C.c_void_p]),
+    "teo_llama_decode_stream_step_shared": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeStreamState), C.POINTER(Share), C.POINTER(Guide),
+                                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+    "teo_llama_decode_stream_graph_create_shared": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeStreamState), C.POINTER(Share),
+                                                              C.POINTER(Guide), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+}
+EXPORTS_SHARE = tuple(_SIGS_SHARE.keys())
 _lib = None
 
 
@@ -289,7 +307,8 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:
         raise TeoLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_PREFIX.items()) + list(_SIGS_SCORE.items()) + list(_SIGS_GUIDE.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_PREFIX.items()) + list(_SIGS_SCORE.items()) + list(_SIGS_GUIDE.items()) \
+            + list(_SIGS_SHARE.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -307,6 +326,8 @@ def load():
             raise TeoLibraryError(f"struct layout mismatch: {name} is {want} bytes in {LIB_PATH}, {C.sizeof(cls)} in this binding; rebuild")
     if lib.teo_guide_sizeof() != C.sizeof(Guide):
         raise TeoLibraryError(f"struct layout mismatch: teo_guide is {lib.teo_guide_sizeof()} bytes in {LIB_PATH}, {C.sizeof(Guide)} in this binding; rebuild")
+    if lib.teo_share_sizeof() != C.sizeof(Share):
+        raise TeoLibraryError(f"struct layout mismatch: teo_share is {lib.teo_share_sizeof()} bytes in {LIB_PATH}, {C.sizeof(Share)} in this binding; rebuild")
     _lib = lib
     return lib
 

@@ -9,6 +9,8 @@
 //  attn_verify_*           : R <= 16 new rows of ONE conversation at consecutive positions (speculative verify): the decode kernel's
 //                            arithmetic with the row loop inside the workgroup -- the cache is streamed once for all rows; bit-identical
 //                            to attn_decode(batch = R) on staggered copies of the conversation.
+//  attn_decode_shared      : the batched split step over slots that were forked from the same cache rows: a forked chunk is loaded once per
+//                            group of slots, from the leader's cache, for every member's query row; bit-identical to attn_decode(batch).
 #include "common.h"
 #include "ops.h"
 
@@ -1110,6 +1112,274 @@ int attn_verify(const void* qkv, void* kc, void* vc, void* vtc, const float* rop
 #undef TEO_VER
     note_kernel("attn_verify");
     TEO_LAUNCH_CHECK("attn_verify");
+    return TEO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// shared-prefix decode (include/teo_hip_share.h): the batched split step over slots of which some were forked from another slot's rows
+// (teo_kv_fork) -- rows [0, d_rows[b]) of slot b are byte for byte those of slot d_lead[b].  The contract is bit-identity with
+// attn_decode(batch, rope) on the same operands, so the kernel is attn_decode_partial_kernel<ROPE>'s arithmetic with a loop over slots
+// inside the workgroup, as attn_verify_partial_kernel has one over rows:
+//   * grid (heads, nsplit, batch) with the chunk attn_decode(batch) forms its records with (the whole-context form's where it would
+//     take the step: its records are the split form's at that chunk);
+//   * a chunk c is SHARED for slot b when b is live, d_lead[b] != b and (c + 1) * chunk <= d_rows[b]: every key of it is one of the
+//     copied rows, none is clamped, none is the new token's.  The workgroup (h, c, b) returns before its first K / V request; the
+//     workgroup (h, c, leader) loads the chunk ONCE from the leader's cache and forms the record of every live member it is shared
+//     for -- the member's q rotated at the member's own position -- beside the leader's own record when the leader is live;
+//   * every other (chunk, slot) is the plain path: loads clamped to the slot's position, the new token's rotated key / value taken
+//     from registers and appended by the workgroup of key `pos`.  Only the workgroup's own slot is ever written;
+//   * per record: the decode kernel's score expression, chunk max / exp / sum, per-wave partial PV sums added in its order; the
+//     records are merged by attn_decode_combine_kernel.
+// Nothing is indexed with a table value: d_lead is only compared, d_rows only bounds a chunk that is also clamped to the cache, so a
+// table that breaks the caller's promises gives wrong numbers, never an access outside the operands.
+// ------------------------------------------------------------------------------------------------
+template <typename T, int LPR, int DEC_CHUNK>
+__global__ __launch_bounds__(256) void attn_decode_shared_kernel(const int* __restrict__ d_pos, T* __restrict__ kc, T* __restrict__ vc,
+                                                                 const T* __restrict__ q, int S_max, int heads, int kv_heads, int nsplit,
+                                                                 T* __restrict__ vtc, const float* __restrict__ cs,
+                                                                 const float* __restrict__ sn, float* __restrict__ part, float scale,
+                                                                 AttnBatch bt, const int* __restrict__ d_lead, const int* __restrict__ d_rows) {
+    constexpr int VE = Cvt16<T>::N;
+    constexpr int HD = LPR * VE;
+    constexpr int RPI = 64 / LPR;                       // rows (keys) per wave-wide load instruction
+    constexpr int KPW = DEC_CHUNK / 4;                  // keys per wave
+    constexpr int NI = KPW / RPI;                       // load instructions per wave per operand
+    constexpr int MAXB = TEO_MAX_DECODE_BATCH;
+    __shared__ float sc[DEC_CHUNK];
+    __shared__ float pstrip[4][DEC_CHUNK];
+    __shared__ float obuf[4][HD];
+    __shared__ uint4 qrot[MAXB][LPR], knew_s[LPR], vnew_s[LPR];
+    const int h = blockIdx.x, sp = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int batch = min(bt.batch, MAXB);
+    const int c0 = sp * DEC_CHUNK;
+    const int pos = d_pos[b], lead_b = d_lead[b], rows_b = d_rows[b];      // (parked: pos < 0)
+    const bool leads = lead_b == b;
+    const bool own = pos >= 0 && c0 <= pos;             // this slot has keys in the chunk: its record is formed here ...
+    if (!leads && own && c0 + DEC_CHUNK <= rows_b) return;         // ... unless the chunk is shared: the leader's workgroup forms it
+    // the slots whose record this workgroup forms (uniform: scalar loads of three small tables, no branch between them)
+    unsigned todo = own ? 1u << b : 0u;
+    if (leads) {
+        for (int m = 0; m < batch; ++m) {
+            const int lm = d_lead[m], pm = d_pos[m], rm = d_rows[m];
+            todo |= (unsigned)((m != b) & (lm == b) & (pm >= c0) & (c0 + DEC_CHUNK <= rm)) << m;
+        }
+    }
+    if (!own) {                                         // nothing of this slot here: neutral partial
+        float* out = part + (((long long)b * heads + h) * nsplit + sp) * (HD + 2);
+        if (tid == 0) { out[0] = -INFINITY; out[1] = 0.f; }
+        for (int d = tid; d < HD; d += 256) out[2 + d] = 0.f;
+        if (todo == 0) return;
+    }
+    const int sub = lane % LPR, grp = lane / LPR;
+    const int gq = heads / kv_heads;
+    const int hk = (heads == kv_heads) ? h : h / gq;
+    kc += (long long)b * bt.cache_stride;
+    vc += (long long)b * bt.cache_stride;
+    if (vtc) vtc += (long long)b * bt.cache_stride;
+    const T* kb = kc + (long long)hk * S_max * HD + sub * VE;
+    const T* vb = vc + (long long)hk * S_max * HD + sub * VE;
+    const int kw0 = c0 + wid * KPW;                     // first key of this wave
+    // the plain kernel's clamp for the slot's own record (row pos is not written yet: its loads are replaced below).  A chunk shared for
+    // a member lies in front of the leader's position (the leader appends behind the rows it was forked at): nothing of it is clamped
+    const int jmax = own ? pos : S_max - 1;
+    uint4 kr[NI], vr[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) kr[i] = ld_kv(kb + (long long)min(kw0 + i * RPI + grp, jmax) * HD);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) vr[i] = ld_kv(vb + (long long)min(kw0 + i * RPI + grp, jmax) * HD);
+    // ---- rotated q of every slot in `todo`, each at its own position, and the rotated k / the v of this slot's new token, once per
+    // workgroup in LDS.  The loop is attn_verify_partial_kernel's, expression for expression: how the compiler contracts
+    // own * c + sgn * oth * s (which of the two products it fuses) follows the code around it, and that loop's choices are the decode
+    // kernels' (the bit tests of both pin it)
+    for (int idx = tid; idx < batch * LPR; idx += 256) {
+        const int r = idx / LPR, s_ = idx % LPR;
+        if (!((todo >> r) & 1u)) continue;
+        const int p_ = d_pos[r];
+        const T* row = q + (long long)r * bt.q_stride;
+        constexpr int HL = LPR / 2;
+        const int psub = s_ ^ HL, ci = (s_ % HL) * VE;
+        const float sgn = (s_ < HL) ? -1.f : 1.f;
+        float cf[VE], sf[VE];
+#pragma unroll
+        for (int e = 0; e < VE; e += 4) {
+            const float4 c4 = *reinterpret_cast<const float4*>(cs + (long long)p_ * (HD / 2) + ci + e);
+            const float4 s4 = *reinterpret_cast<const float4*>(sn + (long long)p_ * (HD / 2) + ci + e);
+            cf[e] = c4.x; cf[e + 1] = c4.y; cf[e + 2] = c4.z; cf[e + 3] = c4.w;
+            sf[e] = s4.x; sf[e + 1] = s4.y; sf[e + 2] = s4.z; sf[e + 3] = s4.w;
+        }
+        float own_[VE], oth[VE], rot[VE];
+        Cvt16<T>::cvt(*reinterpret_cast<const uint4*>(row + h * HD + s_ * VE), own_);
+        Cvt16<T>::cvt(*reinterpret_cast<const uint4*>(row + h * HD + psub * VE), oth);
+#pragma unroll
+        for (int e = 0; e < VE; ++e) rot[e] = Elem<T>::round(own_[e] * cf[e] + sgn * oth[e] * sf[e]);
+        qrot[r][s_] = Cvt16<T>::pack(rot);              // exact: the values are already rounded to T
+        if (own && r == b) {
+            const T* kraw = row + (long long)(heads + hk) * HD;
+            Cvt16<T>::cvt(*reinterpret_cast<const uint4*>(kraw + s_ * VE), own_);
+            Cvt16<T>::cvt(*reinterpret_cast<const uint4*>(kraw + psub * VE), oth);
+#pragma unroll
+            for (int e = 0; e < VE; ++e) rot[e] = Elem<T>::round(own_[e] * cf[e] + sgn * oth[e] * sf[e]);
+            knew_s[s_] = Cvt16<T>::pack(rot);
+            vnew_s[s_] = *reinterpret_cast<const uint4*>(row + (long long)(heads + kv_heads + hk) * HD + s_ * VE);
+        }
+    }
+    __syncthreads();
+    // ---- the slot's own new token in registers (every lane its 16-byte slice), as the plain kernel holds it; KV append by the lane
+    // group that owns key `pos`, one q head per kv head -- this workgroup's own slot, no other
+    float knew[VE], vnew[VE];
+#pragma unroll
+    for (int e = 0; e < VE; ++e) { knew[e] = 0.f; vnew[e] = 0.f; }
+    if (own) {
+        const uint4 kpk = knew_s[sub], vpk = vnew_s[sub];
+        Cvt16<T>::cvt(kpk, knew);
+        Cvt16<T>::cvt(vpk, vnew);
+        if (h % gq == 0 && pos >= kw0 && pos < kw0 + KPW && (pos - kw0) % RPI == grp) {
+            *reinterpret_cast<uint4*>(kc + ((long long)hk * S_max + pos) * HD + sub * VE) = kpk;
+            *reinterpret_cast<uint4*>(vc + ((long long)hk * S_max + pos) * HD + sub * VE) = vpk;
+            if (vtc) {
+                const T* pe = reinterpret_cast<const T*>(&vpk);
+#pragma unroll
+                for (int e = 0; e < VE; ++e) vtc[((long long)hk * HD + sub * VE + e) * S_max + pos] = pe[e];
+            }
+        }
+    }
+    constexpr bool DOT2 = sizeof(T) == 2;
+    constexpr int SPL = (DEC_CHUNK + 63) / 64;
+    for (int m = 0; m < batch; ++m) {
+        if (!((todo >> m) & 1u)) continue;              // (uniform)
+        const bool mine = m == b;
+        // a member's chunk is whole and in front of its position: no key of it is masked or new
+        const int kv_len = mine ? pos + 1 : c0 + DEC_CHUNK;
+        const int mpos = mine ? pos : -1;
+        const uint4 qpk = qrot[m][sub];
+        float qf[VE];
+        Cvt16<T>::cvt(qpk, qf);
+        // ---- scores
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int j = kw0 + i * RPI + grp;
+            uint4 kraw = kr[i];
+            float kf[VE];
+            if (!DOT2) Cvt16<T>::cvt(kr[i], kf);
+            if (j == mpos) {                            // the new token's key: not in the cache yet
+                if (DOT2) kraw = Cvt16<T>::pack(knew);
+#pragma unroll
+                for (int e = 0; e < VE; ++e) kf[e] = knew[e];
+            }
+            float s = 0.f;
+            if (DOT2) {
+                s = attn_dot2(kraw.x, qpk.x, s); s = attn_dot2(kraw.y, qpk.y, s);
+                s = attn_dot2(kraw.z, qpk.z, s); s = attn_dot2(kraw.w, qpk.w, s);
+            } else {
+#pragma unroll
+                for (int e = 0; e < VE; ++e) s = fmaf(qf[e], kf[e], s);
+            }
+            s = group_sum<LPR>(s);
+            if (sub == 0) sc[j - c0] = (j < kv_len) ? s * scale : -INFINITY;
+        }
+        __syncthreads();
+        // ---- chunk max / exp / sum (the decode kernel's expressions)
+        float sv[SPL];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < SPL; ++i) {
+            sv[i] = (DEC_CHUNK >= 64 || lane + 64 * i < DEC_CHUNK) ? sc[(lane + 64 * i) % DEC_CHUNK] : -INFINITY;
+            mx = fmaxf(mx, sv[i]);
+        }
+        mx = wave_max(mx);
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < SPL; ++i) { sv[i] = expf(sv[i] - mx); sum += sv[i]; }      // -inf -> 0
+        sum = wave_sum(sum);
+#pragma unroll
+        for (int i = 0; i < SPL; ++i)
+            if (DEC_CHUNK >= 64 || lane + 64 * i < DEC_CHUNK) pstrip[wid][lane + 64 * i] = Elem<T>::round(sv[i]);
+        // ---- PV on this wave's keys
+        float acc[VE];
+#pragma unroll
+        for (int e = 0; e < VE; ++e) acc[e] = 0.f;
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const float p = pstrip[wid][wid * KPW + i * RPI + grp];      // 0 for keys >= kv_len
+            float vf[VE];
+            Cvt16<T>::cvt(vr[i], vf);
+            // own record: key pos and the clamped keys behind it take the new token's value (0 x an unwritten row is not 0 when it is NaN)
+            if (mine && kw0 + i * RPI + grp >= pos) {
+#pragma unroll
+                for (int e = 0; e < VE; ++e) vf[e] = vnew[e];
+            }
+#pragma unroll
+            for (int e = 0; e < VE; ++e) acc[e] = fmaf(p, vf[e], acc[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < VE; ++e) acc[e] = cross_group_sum<LPR>(acc[e]);
+        if (grp == 0) {
+#pragma unroll
+            for (int e = 0; e < VE; ++e) obuf[wid][sub * VE + e] = acc[e];
+        }
+        __syncthreads();
+        float* out = part + (((long long)m * heads + h) * nsplit + sp) * (HD + 2);
+        for (int d = tid; d < HD; d += 256) out[2 + d] = obuf[0][d] + obuf[1][d] + obuf[2][d] + obuf[3][d];
+        if (tid == 0) { out[0] = mx; out[1] = sum; }
+    }
+}
+
+template <typename T, int LPR>
+static void attn_decode_shared_launch(const void* q, void* kc, void* vc, void* vtc, const float* cs, const float* sn, void* o, float* part,
+                                      const int* d_pos, int S_max, int heads, int kv_heads, int hd, float scale, int nsplit, int chunk,
+                                      AttnBatch bt, const int* d_lead, const int* d_rows, hipStream_t st) {
+    dim3 grid(heads, nsplit, bt.batch);
+#define TEO_SPART(CH)                                                                                                  \
+    TEO_KLAUNCH((attn_decode_shared_kernel<T, LPR, CH>), grid, 256, 0, st, d_pos, (T*)kc, (T*)vc, (const T*)q, S_max, heads, kv_heads, \
+                nsplit, (T*)vtc, cs, sn, part, scale, bt, d_lead, d_rows)
+    if constexpr (32 / 4 >= 64 / LPR) {
+        if (chunk == 32) { TEO_SPART(32); } else if (chunk == 64) { TEO_SPART(64); } else if (chunk == 256) { TEO_SPART(256); } else { TEO_SPART(128); }
+    } else if constexpr (64 / 4 >= 64 / LPR) {
+        if (chunk == 64) { TEO_SPART(64); } else if (chunk == 256) { TEO_SPART(256); } else { TEO_SPART(128); }
+    } else {
+        if (chunk == 256) { TEO_SPART(256); } else { TEO_SPART(128); }
+    }
+#undef TEO_SPART
+    prof_bump(1);
+    TEO_KLAUNCH((attn_decode_combine_kernel<T>), dim3(heads, bt.batch), 512, 0, st, d_pos, part, (T*)o, __builtin_ctz((unsigned)hd), nsplit,
+                __builtin_ctz((unsigned)chunk), bt.o_stride);
+    prof_bump(-1);
+}
+
+// keys per record of the step attn_decode(batch) runs at this shape (0: a shape it does not take): the host mirror of the share table
+// counts shared rows in whole chunks of it
+int attn_decode_record_chunk(int batch, int heads, int hd, int S_max, int dtype) {
+    const AttnDecodePlan pl = attn_decode_plan(batch, heads, hd, S_max, dtype);
+    if (!pl.ok) return 0;
+    return pl.whole ? pl.cw : pl.chunk;
+}
+
+// attn_decode(rope) over slots that share leading cache rows: d_lead / d_rows [bt.batch] (include/teo_hip_share.h)
+int attn_decode_shared(const void* q, void* kc, void* vc, void* vtc, const float* rope_cos, const float* rope_sin, void* o, float* part,
+                       const int* d_pos, int S_max, int heads, int kv_heads, int hd, float scale, int dtype, hipStream_t st, AttnBatch bt,
+                       const int* d_lead, const int* d_rows) {
+    const AttnDecodePlan pl = attn_decode_plan(bt.batch, heads, hd, S_max, dtype);
+    if (!pl.ok) {
+        set_error("attn_decode_shared: unsupported head_dim %d / max_seq %d", hd, S_max);
+        return TEO_ERR_UNSUPPORTED;
+    }
+    // the records attn_decode(batch) forms: the whole-context form's chunk where it would take the step
+    const int chunk = pl.whole ? pl.cw : pl.chunk;
+    const int nsplit = cdiv(S_max, chunk);
+#define TEO_SHR(TT, LL) attn_decode_shared_launch<TT, LL>(q, kc, vc, vtc, rope_cos, rope_sin, o, part, d_pos, S_max, heads, kv_heads, hd, scale, nsplit, chunk, bt, d_lead, d_rows, st)
+    if (dtype == TEO_F32) {
+        switch (pl.lpr) { case 2: TEO_SHR(float, 2); break; case 4: TEO_SHR(float, 4); break; case 8: TEO_SHR(float, 8); break;
+                          case 16: TEO_SHR(float, 16); break; default: TEO_SHR(float, 32); }
+    } else if (dtype == TEO_F16) {
+        switch (pl.lpr) { case 2: TEO_SHR(f16_t, 2); break; case 4: TEO_SHR(f16_t, 4); break; case 8: TEO_SHR(f16_t, 8); break;
+                          case 16: TEO_SHR(f16_t, 16); break; default: TEO_SHR(f16_t, 32); }
+    } else {
+        switch (pl.lpr) { case 2: TEO_SHR(bf16_t, 2); break; case 4: TEO_SHR(bf16_t, 4); break; case 8: TEO_SHR(bf16_t, 8); break;
+                          case 16: TEO_SHR(bf16_t, 16); break; default: TEO_SHR(bf16_t, 32); }
+    }
+#undef TEO_SHR
+    note_kernel("attn_decode_shared");
+    TEO_LAUNCH_CHECK("attn_decode_shared");
     return TEO_OK;
 }
 

@@ -32,7 +32,7 @@ static int guide_check(const teo_guide* g, const char* who) {
 }
 
 // what the steps add: the table is the model's width, the fallback token has an embedding row, the fallback can set d_stop
-static int guide_check_step(const teo_guide* g, const teo_llama_desc* d, const void* d_stop, const char* who) {
+int guide_check_step(const teo_guide* g, const teo_llama_desc* d, const void* d_stop, const char* who) {
     { const int rc = guide_check(g, who); if (rc != TEO_OK) return rc; }
     TEO_CHECK_ARG(g->vocab == d->vocab, "%s: the guide's vocab %d is not the model's %d", who, g->vocab, d->vocab);
     TEO_CHECK_ARG(g->fallback_token >= 0 && g->fallback_token < d->vocab, "%s: fallback_token %lld outside 0..%d", who, g->fallback_token,

@@ -26,6 +26,8 @@ int decode_stream_graph_create(const teo_llama_desc* d, const teo_decode_stream_
 // abi.hip: the argument checks of the plain entry points, for the guided ones
 int decode_state_check(const teo_llama_desc* d, const teo_decode_state* st, const char* who);
 int stream_state_check(const teo_llama_desc* d, const teo_decode_stream_state* st);
+// guide.hip: what a step checks of its guide (the table is the model's width, the fallback token has an embedding row, d_stop is there)
+int guide_check_step(const teo_guide* g, const teo_llama_desc* d, const void* d_stop, const char* who);
 
 #ifdef __HIPCC__
 // Row mask, called by a whole workgroup (any size): row[t] = -inf wherever next_row[t] == TEO_GUIDE_NONE; other floats are not written.

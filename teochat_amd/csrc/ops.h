@@ -36,6 +36,12 @@ int attn_decode(const void* q, void* kc, void* vc, void* vtc, const float* rope_
                 float* part, const int* d_pos, int S_max, int heads, int kv_heads, int hd, float scale, int dtype,
                 hipStream_t st, AttnBatch bt = AttnBatch());
 
+// attn_decode(rope) over slots that share leading cache rows (the share header: d_lead / d_rows [bt.batch]); bit-identical to it
+int attn_decode_shared(const void* q, void* kc, void* vc, void* vtc, const float* rope_cos, const float* rope_sin, void* o, float* part,
+                       const int* d_pos, int S_max, int heads, int kv_heads, int hd, float scale, int dtype, hipStream_t st, AttnBatch bt,
+                       const int* d_lead, const int* d_rows);
+int attn_decode_record_chunk(int batch, int heads, int hd, int S_max, int dtype);      // keys per record of attn_decode(batch); 0: unsupported
+
 // `rows` new rows of ONE conversation at positions d_pos[0] .. d_pos[0] + rows - 1 (speculative verify): RoPE, KV append and causal attention,
 // the cache streamed once; every row and every cache row bit-identical to attn_decode(batch = rows) on staggered copies (attention.hip)
 int attn_verify(const void* qkv, void* kc, void* vc, void* vtc, const float* rope_cos, const float* rope_sin, void* o, float* part,

@@ -6,6 +6,7 @@
 
 #include "runtime.h"
 #include "guide_dev.h"
+#include "share_dev.h"
 
 namespace teo {
 struct Carver {
@@ -627,8 +628,9 @@ static int decode_batch_layers(const teo_llama_desc* d, const BatchLoopOpts& o, 
 // d_limit == NULL: the batched step.  d_limit != NULL: the stream step (teo_decode_stream_state) -- the same launches with the
 // self-parking tail; the attention kernels skip parked conversations (d_pos < 0) by themselves.
 // g (optional, stream step only): the guided stream tail.
+// sh (optional, stream step only): the share table of include/teo_hip_share.h -- the attention launch reads forked rows once per group.
 static int decode_batch_step_impl(const teo_llama_desc* d, const teo_decode_batch_state* s, const int* d_limit, void* ws, size_t ws_bytes,
-                                  const char* who, hipStream_t st, const teo_guide* g = nullptr) {
+                                  const char* who, hipStream_t st, const teo_guide* g = nullptr, const teo_share* sh = nullptr) {
     const int B = s->batch;
     const DecodeBatchWs w = decode_batch_carve(d, B, ws, ws_bytes);
     if (w.total > ws_bytes) {
@@ -641,6 +643,9 @@ static int decode_batch_step_impl(const teo_llama_desc* d, const teo_decode_batc
     bt.batch = B; bt.q_stride = (H + 2 * Hk) * hd; bt.cache_stride = s->cache_stride; bt.o_stride = (long long)H * hd;
     // each conversation at its own position
     auto attend = [&](int l) {
+        if (sh)
+            return attn_decode_shared(w.qkv, d->k_cache[l], d->v_cache[l], d->vt_cache[l], d->rope_cos, d->rope_sin, w.attn, w.part, s->d_pos,
+                                      d->max_seq, H, Hk, hd, 1.0f / sqrtf((float)hd), dt, st, bt, sh->d_lead, sh->d_rows);
         return attn_decode(w.qkv, d->k_cache[l], d->v_cache[l], d->vt_cache[l], d->rope_cos, d->rope_sin, w.attn, w.part, s->d_pos,
                            d->max_seq, H, Hk, hd, 1.0f / sqrtf((float)hd), dt, st, bt);
     };
@@ -683,9 +688,15 @@ static teo_decode_batch_state stream_as_batch(const teo_decode_stream_state* s) 
 }
 
 int llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
-                             const teo_guide* g) {
+                             const teo_guide* g, const teo_share* sh) {
     const teo_decode_batch_state b = stream_as_batch(s);
-    return decode_batch_step_impl(d, &b, s->d_limit, ws, ws_bytes, g ? "teo_llama_decode_stream_step_guided" : "teo_llama_decode_stream_step", st, g);
+    const char* who = sh ? "teo_llama_decode_stream_step_shared" : (g ? "teo_llama_decode_stream_step_guided" : "teo_llama_decode_stream_step");
+    return decode_batch_step_impl(d, &b, s->d_limit, ws, ws_bytes, who, st, g, sh);
+}
+
+int llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
+                             const teo_guide* g) {
+    return llama_decode_stream_step(d, s, ws, ws_bytes, st, g, nullptr);
 }
 
 int llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -884,6 +895,11 @@ int decode_stream_graph_create(const teo_llama_desc* d, const teo_decode_stream_
 int decode_stream_graph_create(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
                                teo_graph** out, const teo_guide* g) {
     return capture_graph(st, [&]() { return llama_decode_stream_step(d, s, ws, ws_bytes, st, g); }, out);
+}
+
+int decode_stream_graph_create(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
+                               teo_graph** out, const teo_guide* g, const teo_share* sh) {
+    return capture_graph(st, [&]() { return llama_decode_stream_step(d, s, ws, ws_bytes, st, g, sh); }, out);
 }
 
 int llama_verify_step_profile(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, float* ms_out, int* count_out,

@@ -118,15 +118,16 @@ class StepGraphs:
         self._graph, self._graph_ws = None, None
         self._guided_graph, self._guided_key = None, None
 
-    def replay_or_step(self, stream, key, n, use_graph, create, step, guided=False):
+    def replay_or_step(self, stream, key, n, use_graph, create, step, guided=False, slot=None):
         """n decode steps on the engine's `stream`: plain launches (step()), or replays of the plain (or the guided) graph, captured again
         by create(out) whenever `key` is not the key of its capture.  The stream is drained behind the replays: replays still outstanding
-        when another command is enqueued run 8 % slower (TeoEngine._Phase.__exit__)."""
+        when another command is enqueued run 8 % slower (TeoEngine._Phase.__exit__).  slot: (graph attribute, key attribute) of a further
+        graph the owner keeps (and destroys in its _drop_graph) beside these two."""
         if not use_graph:
             for _ in range(n):
                 step()
             return
-        g_attr, k_attr = ("_guided_graph", "_guided_key") if guided else ("_graph", "_graph_ws")
+        g_attr, k_attr = slot if slot is not None else (("_guided_graph", "_guided_key") if guided else ("_graph", "_graph_ws"))
         if getattr(self, g_attr) is None or getattr(self, k_attr) != key:
             self._destroy_graph(g_attr)
             g = C.c_void_p()

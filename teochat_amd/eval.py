@@ -53,13 +53,14 @@ def output_path(dataset_name, model_path, out_name=None, out_dir=None, prompt_st
 def eval(dataset_name, model_path, model_base, load_8bit=False, load_4bit=False, cache_dir=None, data_cache_dir=None,
          out_name=None, out_dir=None, prompt_strategy=None, chronological_prefix=True, conv_mode="v1", device="cuda",
          force_rerun=False, temperature=0.2, max_new_tokens=256, dataset=None, model_bundle=None, batch_size=1,
-         continuous=False, prefix_cache=False, guide=None):
+         continuous=False, prefix_cache=False, guide=None, share_prefix=False):
     """Run (or re-use) the model's answers on one TEOChatlas evaluation split and print / return its task metrics.
     Extra keywords (not in the reference): `dataset` = examples to use instead of the hub download, `model_bundle` =
     (tokenizer, model, processor) already loaded, `batch_size` = examples answered per generation (1 = the reference's loop;
     up to 16 share every weight read of a decode step, inference.run_inference_batch), `continuous` = the whole split through one
     generate_stream over batch_size conversation slots that are refilled as answers finish (off: groups of batch_size examples),
     `prefix_cache` (with continuous) = examples about the same image sequence share its prefill (inference.run_inference_batch),
+    `share_prefix` (with prefix_cache) = the decode step reads the shared rows once per group of slots (same answers),
     `guide` = "boxes": every answer is generated under the automaton of guide.BOX_LIST_PATTERN over the tokenizer's vocabulary
     (guide.named_guide; batch_size 1 or continuous), so that it parses as a list of boxes."""
     print("Arguments passed to eval:")
@@ -92,7 +93,8 @@ def eval(dataset_name, model_path, model_base, load_8bit=False, load_4bit=False,
             extra["guide"] = named_guide(guide, tokenizer, vocab=getattr(getattr(model, "config", None), "vocab_size", None))
         outputs = run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronological_prefix, conv_mode,
                                 temperature, max_new_tokens, **({"batch_size": batch_size} if batch_size != 1 else {}),
-                                **({"continuous": True} if continuous else {}), **({"prefix_cache": True} if prefix_cache else {}), **extra)
+                                **({"continuous": True} if continuous else {}), **({"prefix_cache": True} if prefix_cache else {}),
+                                **({"share_prefix": True} if share_prefix else {}), **extra)
         print(f"Saving outputs to {out_path}")
         with open(out_path, "w") as f:
             json.dump(outputs, f, indent=4)
@@ -134,6 +136,8 @@ _CLI = (
     ("continuous", dict(action="store_true", default=argparse.SUPPRESS)),
     # not in the reference: with --continuous, examples with the same image paths share the prefill up to their last <image>
     ("prefix_cache", dict(action="store_true", default=argparse.SUPPRESS)),
+    # not in the reference: with --continuous --prefix_cache, the decode step reads the forked rows once per group of slots
+    ("share_prefix", dict(action="store_true", default=argparse.SUPPRESS)),
     # not in the reference: guided decoding (teochat_amd/guide.py) -- "boxes": answers are lists of [x1, y1, x2, y2]
     ("guide", dict(type=str, choices=["boxes"], default=argparse.SUPPRESS)),
 )

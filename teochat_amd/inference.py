@@ -98,7 +98,7 @@ def run_inference_options(model, processor, tokenizer, inp, image_paths, options
 
 def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, conv_mode="v1", timestamps_list=None,
                         prompt_strategy="interleave", chronological_prefix=True, temperature=0.2, max_new_tokens=256,
-                        do_sample=True, continuous=False, slots=None, prefix_cache=False, guides=None):
+                        do_sample=True, continuous=False, slots=None, prefix_cache=False, guides=None, share_prefix=False):
     """run_inference_single for up to 16 examples at once (not in the reference, whose loop is one example at a time,
     inference.py:100-113): the same prompt construction, frame order, tokenisation and stop keyword per example, then ONE
     batched generation -- every frame of every example through the tower together, one prefill per example, and a decode loop
@@ -117,15 +117,20 @@ def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, con
     An example that starts from another one's rows neither opens nor preprocesses its images.
 
     guides (with continuous=True only): one teochat_amd.guide.TokenGuide or None per example (any sequence with len() and []), handed to
-    generate_stream(guides=...)."""
+    generate_stream(guides=...).
+
+    share_prefix=True (with prefix_cache=True only): generate_stream(share_prefix=True) -- the decode step reads the rows examples were
+    forked from once per group of slots; the answers are the same."""
     B = len(inps)
+    if share_prefix and not prefix_cache:
+        raise ValueError("share_prefix needs prefix_cache=True (only forked rows are known to be shared)")
     if prefix_cache and not continuous:
         raise ValueError("prefix_cache needs continuous=True (prefix reuse lives in the stream decoder's slots)")
     if guides is not None and not continuous:
         raise ValueError("guides needs continuous=True (generate_stream takes one guide per request; the fixed-group batched step takes none)")
     if continuous:
         return _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, conv_mode, timestamps_list, prompt_strategy,
-                                     chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache, guides)
+                                     chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache, guides, share_prefix)
     if timestamps_list is None:
         timestamps_list = [[] for _ in range(B)]
     if len(image_paths_list) != B or len(timestamps_list) != B:
@@ -179,7 +184,8 @@ class _Prepared:
 
 
 def _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, conv_mode, timestamps_list, prompt_strategy,
-                          chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache=False, guides=None):
+                          chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache=False, guides=None,
+                          share_prefix=False):
     N = len(inps)
     if N == 0:
         return []
@@ -220,7 +226,8 @@ def _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, c
     with torch.inference_mode():
         outs = model.generate_stream(prepared.column(0), prepared.column(1), slots=slots, do_sample=do_sample, temperature=temperature,
                                      max_new_tokens=max_new_tokens, stopping_criteria=prepared.column(2),
-                                     **({"prefix_keys": Keys()} if prefix_cache else {}), **({"guides": guides} if guides is not None else {}))
+                                     **({"prefix_keys": Keys()} if prefix_cache else {}), **({"guides": guides} if guides is not None else {}),
+                                     **({"share_prefix": True} if share_prefix else {}))
     return [tokenizer.decode(o[n_prompt[i]:]).replace("</s>", "").strip() for i, o in enumerate(outs)]
 
 
@@ -251,7 +258,7 @@ def _record(example, response, dataset):
 
 
 def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronological_prefix, conv_mode, temperature,
-                  max_new_tokens, batch_size=1, continuous=False, prefix_cache=False, guide=None):
+                  max_new_tokens, batch_size=1, continuous=False, prefix_cache=False, guide=None, share_prefix=False):
     """Dataset loop with the bookkeeping the metrics need (inference.py:88-137): response / ground truth / task per example,
     the example's polygon when it has one, and the integer boxes quoted in the question and in the reference answer.
     batch_size (extra trailing keyword, default 1 = the reference's loop): answer that many consecutive examples per
@@ -260,6 +267,8 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
     conversation slots (run_inference_batch(continuous=True)); examples are read and prepared as slots free up.
     prefix_cache=True (with continuous=True): examples with the same image paths share the prefill of everything up to their last
     <image> (run_inference_batch(prefix_cache=True)); the records are the same.
+    share_prefix=True (with continuous=True and prefix_cache=True): the decode step reads the rows examples were forked from once per
+    group of slots (run_inference_batch(share_prefix=True)); the records are the same.
     guide (extra trailing keyword): a teochat_amd.guide.TokenGuide for every example, or a callable(example) -> TokenGuide or None.  With
     batch_size 1 it goes to run_inference_single(guide=...), with continuous=True to generate_stream(guides=...); groups of a fixed
     batch_size > 1 take no guide (ValueError)."""
@@ -267,6 +276,8 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
         raise ValueError(f"batch_size {batch_size}: 1..16 examples per generation")
     if prefix_cache and not continuous:
         raise ValueError("prefix_cache needs continuous=True")
+    if share_prefix and not prefix_cache:
+        raise ValueError("share_prefix needs prefix_cache=True")
     if guide is not None and not continuous and batch_size != 1:
         raise ValueError("guide needs batch_size=1 or continuous=True")
     guide_of = guide if callable(guide) else (lambda example: guide)
@@ -288,6 +299,7 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
                                         prompt_strategy=prompt_strategy, chronological_prefix=chronological_prefix, temperature=temperature,
                                         max_new_tokens=max_new_tokens, continuous=True, slots=int(batch_size),
                                         **({"prefix_cache": True} if prefix_cache else {}),
+                                        **({"share_prefix": True} if share_prefix else {}),
                                         **({"guides": Field(guide_of)} if guide is not None else {}))
         return [_record(dataset[i], r, dataset) for i, r in enumerate(responses)]
     if batch_size == 1:

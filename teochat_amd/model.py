@@ -889,7 +889,7 @@ class LlavaLlamaForCausalLM:
 
     def _generate_stream(self, input_ids_list, images_list=None, slots=8, max_new_tokens=20, do_sample=False, temperature=None,
                          top_k=None, top_p=None, stopping_criteria=None, eos_token_id="config", generator=None, chunk=16, prefix_keys=None,
-                         min_prefix_rows=64, guides=None):
+                         min_prefix_rows=64, guides=None, share_prefix=False):
         """Answer N requests (any N >= 1) over `slots` <= 16 conversation slots of the batched decode step: a slot whose request has
         finished parks -- the attention kernels skip it -- and is refilled with the next request, so a step's work follows the requests
         that are still being answered instead of the longest answer of a fixed group (teochat_amd/stream.py).
@@ -914,6 +914,12 @@ class LlavaLlamaForCausalLM:
         in two pieces is not bit for bit the prompt prefilled in one (the suffix's GEMMs and RoPE take the kernels of a short prefill), so
         answers may differ from the keyless run's the way two orderings of a sum differ (prefix reuse).
 
+        share_prefix=True (with prefix_keys only; ValueError otherwise): the decode step reads the rows a slot was forked from ONCE per
+        group of slots that hold them instead of once per slot (include/teo_hip_share.h; StreamDecoder.share_prefix).  The private
+        copies stay, and the shared step is bit for bit the plain one: the answers are exactly those of share_prefix=False.  The stats
+        gain shared_steps (steps that ran the shared form: only while a live slot shares at least one whole key chunk with its
+        leader) and shared_rows_skipped (cache rows those steps did not read, per layer and K / V operand).
+
         guides: one teochat_amd.guide.TokenGuide or None per request (any sequence with len() and []) turns guided decoding on.  The
         distinct guides (by identity) are concatenated into one GuideSet whose table is uploaded once; None is the automaton that allows
         everything.  A request's first token is selected from its prefill logits under its guide's start state, its slot then starts
@@ -927,6 +933,8 @@ class LlavaLlamaForCausalLM:
             raise ValueError("generate_stream: no requests")
         if not 1 <= slots <= L.MAX_DECODE_BATCH:
             raise ValueError(f"slots {slots} outside 1..{L.MAX_DECODE_BATCH}")
+        if share_prefix and prefix_keys is None:
+            raise ValueError("share_prefix needs prefix_keys (only forked rows are known to be shared)")
         if eos_token_id == "config":
             eos_token_id = self._config_eos()
         max_new = [int(max_new_tokens)] * N if isinstance(max_new_tokens, int) else [int(m) for m in max_new_tokens]
@@ -954,6 +962,7 @@ class LlavaLlamaForCausalLM:
             gset = GuideSet([guides[r] for r in range(N)], vocab=eng.cfg.vocab_size,
                             eos=eos_token_id if eos_token_id is not None else self._config_eos())
         dec.set_guide(gset)
+        dec.share_prefix(bool(share_prefix))
         ids_of, crits_of = {}, {}                 # the requests in flight (and, for ids, the finished ones: a few integers each)
         dev_stop = {"ids": None, "off": False}    # the device stop: one id sequence shared by every request admitted so far, or off
 
@@ -1092,7 +1101,10 @@ class LlavaLlamaForCausalLM:
         stats["requests"] = N
         if gset is not None:
             stats.update(guide_states=int(gset.n_states), guide_table_bytes=int(gset.table_bytes))
+        if share_prefix:
+            stats.update({k: int(dec.stats()[k]) for k in ("shared_steps", "shared_rows_skipped")})
         dec.set_guide(None)
+        dec.share_prefix(False)
         self.last_generation_stats = stats
         return outs
 

@@ -8,6 +8,7 @@ freed in a round (teo_llama_prefill_slots), one arm call per slot (teo_llama_dec
 slot's arithmetic is the batched step's, bit for bit.
 
   StreamDecoder  the device side: a BatchDecoder's caches, descriptors and weight copies + d_limit, the stream state and its graph
+  ShareTable     the host mirror of the share table (include/teo_hip_share.h): which slots hold byte-identical leading rows, by fork lineage
   run_stream     the scheduler loop over anything with StreamDecoder's methods (the host tests drive it with a fake)
 """
 import ctypes as C
@@ -25,6 +26,83 @@ SEED_STRIDE = 0x9E3779B97F4A7C15              # request i draws from the Philox 
 
 def request_seed(base_seed, i):
     return (int(base_seed) + SEED_STRIDE * int(i)) & SEED_MASK
+
+
+class ShareTable:
+    """Which slots hold byte-identical leading cache rows, known from fork lineage alone: lead[s] is the slot whose cache slot s shares
+    rows with (lead[s] == s: s leads), rows[s] how many leading rows of s equal the same rows of lead[s] (0 for a leader, and a member
+    whose claim shrinks to 0 leads itself again).  Invariants after every call: lead[lead[s]] == lead[s]; a claim is only ever made by
+    fork() and only ever shrinks afterwards; a leader's rows [0, max rows of its members) are never overwritten while it leads -- a
+    slot whose rows are about to be overwritten says so first (overwrite) and, where members read those rows, hands the lead to the
+    member that shares the most.  `dirty` is set by every change and cleared by whoever uploads the table."""
+
+    def __init__(self, slots):
+        self.n = int(slots)
+        self.reset()
+
+    def reset(self):
+        """every slot its own leader, nothing shared"""
+        self.lead = list(range(self.n))
+        self.rows = [0] * self.n
+        self.dirty = True
+
+    def members(self, s):
+        return [m for m in range(self.n) if m != s and self.lead[m] == s]
+
+    def _leave(self, s):
+        """slot s leaves its group: a member simply goes; a leader hands its members to the one that shares the most rows with it --
+        member m and that one both equal the old leader on their claimed rows, so they equal each other on the shorter claim"""
+        if self.lead[s] != s:
+            self.lead[s], self.rows[s] = s, 0
+        else:
+            mem = self.members(s)
+            if mem:
+                new = max(mem, key=lambda m: (self.rows[m], -m))
+                top = self.rows[new]
+                for m in mem:
+                    self.lead[m], self.rows[m] = new, min(self.rows[m], top)
+                self.lead[new], self.rows[new] = new, 0
+        self.dirty = True
+
+    def overwrite(self, s, past=0):
+        """rows [past, ...) of slot s are about to be rewritten (refill: past = 0; refill_past: its past).  A member keeps
+        min(rows, past); a leader whose members read rows at or behind `past` leaves its group first."""
+        s, past = int(s), max(int(past), 0)
+        if self.lead[s] != s:
+            if self.rows[s] > past:
+                self.rows[s] = past
+                self.dirty = True
+            if self.rows[s] == 0:
+                self._leave(s)
+        elif any(self.rows[m] > past for m in self.members(s)):
+            self._leave(s)
+
+    def fork(self, src, dst_list, rows):
+        """rows [0, rows) of src are copied into every slot of dst_list: each destination leaves its group (it is overwritten) and joins
+        src's -- under src's leader, or src itself when src leads -- with `rows`, clipped to what src shares with that leader"""
+        src, rows = int(src), int(rows)
+        for d in dst_list:
+            self._leave(int(d))
+        top = self.lead[src]
+        r = rows if top == src else min(rows, self.rows[src])
+        for d in dst_list:
+            if r > 0:
+                self.lead[int(d)], self.rows[int(d)] = top, r
+        self.dirty = True
+
+    def skipped(self, chunk, live):
+        """rows a shared step does not read: whole chunks of `chunk` keys inside the claim of every live member (live: one bool per slot)"""
+        chunk = int(chunk)
+        if chunk <= 0:
+            return 0
+        return sum(self.rows[s] // chunk * chunk for s in range(self.n) if self.lead[s] != s and live[s])
+
+    def check(self):
+        """the invariants the kernel's caller promises (for the tests)"""
+        for s in range(self.n):
+            top = self.lead[s]
+            assert 0 <= top < self.n and self.lead[top] == top, (s, self.lead)
+            assert self.rows[s] >= 0 and (top != s or self.rows[s] == 0) and (top == s or self.rows[s] > 0), (s, self.lead, self.rows)
 
 
 class StreamDecoder(StepGraphs):
@@ -59,6 +137,14 @@ class StreamDecoder(StepGraphs):
         # holds its address -- and the teo_guide of the set in force (set_guide), with a graph of its own beside the plain one
         self.d_guide_state = torch.zeros(slots, dtype=torch.int32, device=dev)
         self._guide, self._guide_obj = None, None
+        # shared-prefix decode (include/teo_hip_share.h): the share table, owned here for the decoder's life -- the shared graph holds
+        # the two addresses and reads the table at every replay -- its host mirror, and the shared step's graph beside the other two
+        self.d_share_lead = torch.arange(slots, dtype=torch.int32, device=dev)
+        self.d_share_rows = torch.zeros(slots, dtype=torch.int32, device=dev)
+        self.share = ShareTable(slots)
+        self._share = L.Share(self.d_share_lead.data_ptr(), self.d_share_rows.data_ptr())
+        self._share_on = False
+        self._shared_graph, self._shared_key = None, None
         # the step's workspace holds the slots' residual rows BETWEEN steps: this decoder's own, never a buffer another decoder writes
         self._ws = torch.empty(max(int(self.lib.teo_llama_decode_stream_workspace_bytes(C.byref(bd.desc), slots)), 256), dtype=torch.uint8, device=dev)
         # a knob (tune_set) or an option (set_options): the captured step keeps its capture's choices
@@ -86,7 +172,8 @@ class StreamDecoder(StepGraphs):
         self.pos = [-1] * self.B                 # host mirror of d_pos / d_out_count as of the last poll
         self.count = [0] * self.B
         self.held = [None] * self.B              # per slot: None or (key, prompt ids, embedded rows per id, rows written by PREFILL)
-        self._stats = dict(steps=0, slot_steps=0, live_slot_steps=0, prefill_passes=0, arms=0)
+        self._stats = dict(steps=0, slot_steps=0, live_slot_steps=0, prefill_passes=0, arms=0, shared_steps=0, shared_rows_skipped=0)
+        self.share.reset()
 
     def configure(self, stop_ids=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0):
         """The step's shared options: the device stop (an id sequence every live slot stops on, or None) and the sampler."""
@@ -130,6 +217,23 @@ class StreamDecoder(StepGraphs):
     def guide_states(self):
         with self.eng.phase():
             return self.d_guide_state.tolist()
+
+    # ------------------------------------------------------------------ shared-prefix decode
+    def share_prefix(self, on=True):
+        """Select the shared step (teo_llama_decode_stream_step_shared): steps() then reads the rows a live slot was forked from once per
+        group instead of once per slot -- while the table holds such a slot; otherwise it replays the plain (or guided) graph as before.
+        The table itself is always kept (fork / refill / refill_past / reset), whatever this switch says."""
+        self._share_on = bool(on)
+
+    def share_chunk(self):
+        """keys per split record of the step's attention at this decoder's shape, under the engine's knobs: claims count in whole chunks"""
+        cfg, bd = self.eng.cfg, self.bd
+        return int(self.lib.teo_attn_decode_chunk(self.B, int(bd.desc.heads), int(bd.desc.head_dim), int(bd.desc.max_seq), int(bd.desc.dtype),
+                                                  bd.desc.tune))
+
+    def _drop_graph(self):
+        StepGraphs._drop_graph(self)
+        self._destroy_graph("_shared_graph")
 
     # ------------------------------------------------------------------ refill + arm
     def refill(self, slot_list, embeds_list, last_only=True):
@@ -178,6 +282,7 @@ class StreamDecoder(StepGraphs):
                             lambda ws, st: lib.teo_llama_prefill_slots_past(d0, _p(rows), c_lens, c_pasts, c_slots, n, stride, last, _p(logits),
                                                                             _p(ws), ws.numel(), st, None))
         for s, p, n_ in zip(slot_list, pasts or [0] * n, lens):
+            self.share.overwrite(s, p)           # (the pass is enqueued; no step runs before steps() uploads the table)
             bd.cache_len[s] = p + n_
             self.held[s] = None                  # what the slot held is overwritten; the scheduler records what it holds now
         bd._armed = False
@@ -199,6 +304,7 @@ class StreamDecoder(StepGraphs):
         n = len(dst_list)
         with self.eng.phase() as st:
             L.check(self.lib.teo_kv_fork(C.byref(bd.desc), src, (C.c_int * n)(*dst_list), n, rows, bd.k_cache.stride(1), st), "teo_kv_fork")
+        self.share.fork(src, dst_list, rows)
         for s in dst_list:
             self.held[s] = None
         self._stats["forks"] = self._stats.get("forks", 0) + n
@@ -237,8 +343,28 @@ class StreamDecoder(StepGraphs):
         ws = self._workspace()
         d, s_ = C.byref(bd.desc), C.byref(self.state)
         gd = self._guide
+        skip = 0
+        if self._share_on:
+            chunk = self.share_chunk()
+            skip = self.share.skipped(chunk, self.live)
         with eng.phase() as st:
-            if gd is not None:
+            if skip:
+                # at least one live slot shares a whole chunk with its leader: the shared step, plain or guided tail.  The table is
+                # uploaded on the engine stream in front of the step whenever the mirror changed; the graph reads it from device memory
+                if self.share.dirty:
+                    self.d_share_lead.copy_(torch.tensor(self.share.lead, dtype=torch.int32))
+                    self.d_share_rows.copy_(torch.tensor(self.share.rows, dtype=torch.int32))
+                    self.share.dirty = False
+                g_ = C.byref(gd) if gd is not None else None
+                sh_ = C.byref(self._share)
+                self.replay_or_step(eng.stream, (ws.data_ptr(), guide_graph_key(gd, ws) if gd is not None else None), n, use_graph,
+                                    lambda out: L.check(self.lib.teo_llama_decode_stream_graph_create_shared(d, s_, sh_, g_, _p(ws), ws.numel(), st, out),
+                                                        "teo_llama_decode_stream_graph_create_shared"),
+                                    lambda: L.check(self.lib.teo_llama_decode_stream_step_shared(d, s_, sh_, g_, _p(ws), ws.numel(), st),
+                                                    "teo_llama_decode_stream_step_shared"), slot=("_shared_graph", "_shared_key"))
+                self._stats["shared_steps"] += n
+                self._stats["shared_rows_skipped"] += n * skip
+            elif gd is not None:
                 # the guided step (include/teo_hip_guide.h) and a graph of its own beside the plain one
                 g_ = C.byref(gd)
                 self.replay_or_step(eng.stream, guide_graph_key(gd, ws), n, use_graph,
