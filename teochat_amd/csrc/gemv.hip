@@ -174,16 +174,53 @@ __device__ __forceinline__ P13Img p13_img(const void* W, int N, int K) {
     const unsigned char* b = reinterpret_cast<const unsigned char*>(W);
     return {reinterpret_cast<const unsigned*>(b + l.rt), b + l.lo, b + l.nib, b + l.sgn, reinterpret_cast<const bf16_t*>(b + l.esc)};
 }
-template <bool NT, typename V>
-__device__ __forceinline__ V ldv(const void* p) {
-    return NT ? __builtin_nontemporal_load(reinterpret_cast<const V*>(p)) : *reinterpret_cast<const V*>(p);
+// The streams of ONE row of the image as buffer descriptors: the row's LO / NIB / SGN bases (64-bit, the same in every lane) live in
+// scalar registers, each with the row's own section bytes (K, K / 2, K / 8) as its extent, and a lane adds one 32-bit byte offset per
+// stream -- no 64-bit per-lane pointer per (row, stream) and no vector pointer add per step.  `row` must be wave-uniform; readfirstlane
+// makes that provable (a row derived from threadIdx.x / 64 is not), or every load would be wrapped in a waterfall loop.
+typedef __amdgpu_buffer_rsrc_t p13_rsrc;
+struct P13Row { p13_rsrc lo, nib, sgn; };
+__device__ __forceinline__ P13Row p13_row(const P13Img& img, int row, int K) {
+    // the row's SGN offset, 64-bit (an image may pass 4 GiB); NIB's is 4 x and LO's 8 x that (K % 8 == 0): one scalar multiply per row,
+    // not three -- this arithmetic stands between a row group's start and its first weight request
+    const long long q = (long long)__builtin_amdgcn_readfirstlane(row) * (K / 8);
+    auto rsrc = [](const unsigned char* p, int bytes) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p), 0, bytes, 0x00020000); };
+    return {rsrc(img.lo + q * 8, K), rsrc(img.nib + q * 4, K / 2), rsrc(img.sgn + q, K / 8)};
 }
-// the raw bytes of chunk c of a row: lo / nib / sgn are the ROW's section pointers
-template <bool NT>
-__device__ __forceinline__ uint4 p13_load(const unsigned char* lo, const unsigned char* nib, const unsigned char* sgn, long long c) {
+template <typename WT> using RowSrc = typename std::conditional<IsP13<WT>::v, P13Row, char>::type;      // (nothing for the other formats)
+// the raw bytes of chunk (s + C + l) of a row: l the lane's own chunk (a vector register), s the step's first chunk (wave-uniform), C a
+// constant of the unrolled step.  FULL (every lane's chunk is inside the row): s goes into the instruction's scalar offset and C into
+// its 12-bit immediate (what does not fit, into the scalar offset as well), so a step is loads and scalar adds only.  Otherwise (the
+// masked tail step) the whole index goes through the vector offset, the part the hardware range-checks against the descriptor's extent:
+// a chunk past the row returns zeros -- the {0, 0, 0, 0} the tail's select used to supply -- without exec masking, and reads nothing.
+// (in two parts, the 4 + 1 bytes of NIB and SGN and the 8 bytes of LO, for the callers that order a step's loads themselves)
+template <bool NT, bool FULL>
+__device__ __forceinline__ void p13_load_codes(uint4& w, const P13Row& row, int l, int s, int C) {
+    constexpr int AUX = NT ? 2 : 0;                                      // the nt bit: what __builtin_nontemporal_load sets on a global load
+    auto voff = [&](int b) { return FULL ? l * b + ((C * b) & 4095) : (l + s + C) * b; };
+    auto soff = [&](int b) { return FULL ? s * b + ((C * b) & ~4095) : 0; };
+    w.z = __builtin_amdgcn_raw_buffer_load_b32(row.nib, voff(4), soff(4), AUX);
+    w.w = __builtin_amdgcn_raw_buffer_load_b8(row.sgn, voff(1), soff(1), AUX);
+}
+template <bool NT, bool FULL>
+__device__ __forceinline__ void p13_load_lo(uint4& w, const P13Row& row, int l, int s, int C) {
     typedef unsigned v2u __attribute__((ext_vector_type(2)));
-    const v2u l = ldv<NT, v2u>(lo + c * 8);
-    return make_uint4(l.x, l.y, ldv<NT, unsigned>(nib + c * 4), (unsigned)ldv<NT, unsigned char>(sgn + c));
+    constexpr int AUX = NT ? 2 : 0;
+    const v2u lo = __builtin_amdgcn_raw_buffer_load_b64(row.lo, FULL ? l * 8 + ((C * 8) & 4095) : (l + s + C) * 8, FULL ? s * 8 + ((C * 8) & ~4095) : 0, AUX);
+    w.x = lo.x; w.y = lo.y;
+}
+template <bool NT, bool FULL>
+__device__ __forceinline__ uint4 p13_load(const P13Row& row, int l, int s, int C) {
+    uint4 w;
+    p13_load_codes<NT, FULL>(w, row, l, s, C);                           // NIB and SGN first: the rebuild starts on them
+    p13_load_lo<NT, FULL>(w, row, l, s, C);
+    return w;
+}
+// The lane's chunk, made opaque once per step.  Without it the loop-invariant sums l * b + C * b are hoisted out of the loop, one vector
+// register per (stream, chunk of the step), and reach the loads as registers; formed inside the step they fold into the immediates.
+__device__ __forceinline__ int p13_step_lane(int l) {
+    asm volatile("" : "+v"(l));
+    return l;
 }
 // raw {lo0, lo1, nib, sgn} -> PAIRS: the chunk's four bf16 pairs (v_dot2 operands); else {lo0, lo1, h0, h1} for Vec16<p13_t>::cvt
 template <bool PAIRS>
@@ -354,21 +391,27 @@ __device__ __forceinline__ void stage_x(const T* __restrict__ x, const T* __rest
 
 // one block of R rows x U chunks: loads and the dot-product update
 // (MXFP4: sx receives the chunks' e8m0 bytes from the scale rows srow -- one byte per lane, a wave's 64 in one request; unused otherwise)
-// (w13 image: rowp / srow / grow are the rows' LO / NIB / SGN pointers and w receives the raw bytes; grow is unused otherwise)
-template <typename WT, int R, int U, bool NT, bool FULL>
+// (w13 image: prow holds the rows' LO / NIB / SGN descriptors and w receives the raw bytes; the pointers are unused, as prow is otherwise)
+// BY_CHUNK (w13 image only) fixes the order of the step's loads, chunk by chunk: the codes of the R rows, then their LO bytes.  Left to
+// itself the scheduler clusters the buffer loads by stream -- every SGN byte of the step, every NIB dword, then LO, the 8 of every 13
+// bytes last.  Measured per kernel, 7B shapes, us per launch, parent / clustered / by chunk: qkv 16.41 / 14.57 / 14.62, gate/up 24.58 /
+// 24.45 / 24.65, lm_head 34.9 / 35.5 / 35.0 -- so only the plain row groups (the lm_head form) ask for it.  The empty asm is a memory
+// barrier to the compiler alone (no instruction): loads do not cross it.  The bits do not depend on any of this; what the loops look
+// like after a compiler change is what tools/gemv_isa.py prints (every step's 24 loads must stay ahead of its first vmcnt wait).
+template <typename WT, int R, int U, bool NT, bool FULL, bool BY_CHUNK = false>
 __device__ __forceinline__ void issue_block(uint4 (&w)[U][R], unsigned (&sx)[U][R], const WT* const (&rowp)[R],
-                                            const unsigned char* const (&srow)[R], const unsigned char* const (&grow)[R], int c0, int lane,
+                                            const unsigned char* const (&srow)[R], const RowSrc<WT> (&prow)[R], int c0, int lane,
                                             int nchunk) {
     constexpr int CH = CU<WT>::v;
     if constexpr (IsP13<WT>::v) {
+        const int l = p13_step_lane(lane);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int c = c0 + u * 64 + lane;
+            if (BY_CHUNK && u) asm volatile("" ::: "memory");
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (FULL) w[u][r] = p13_load<NT>(reinterpret_cast<const unsigned char*>(rowp[r]), srow[r], grow[r], c);
-                else w[u][r] = (c < nchunk) ? p13_load<NT>(reinterpret_cast<const unsigned char*>(rowp[r]), srow[r], grow[r], c) : make_uint4(0, 0, 0, 0);
-            }
+            for (int r = 0; r < R; ++r) p13_load_codes<NT, FULL>(w[u][r], prow[r], l, c0, u * 64);
+#pragma unroll
+            for (int r = 0; r < R; ++r) p13_load_lo<NT, FULL>(w[u][r], prow[r], l, c0, u * 64);
         }
         return;
     }
@@ -460,17 +503,18 @@ __device__ __forceinline__ float rows_escaped_row(const bf16_t* row, const float
     constexpr int STEP = 64 * U;
     const bf16_t* rowp[1] = {row};
     const unsigned char* none[1] = {nullptr};
+    const RowSrc<bf16_t> nosrc[1] = {};
     uint4 w[U][1];
     unsigned sx[U][1];
     float acc[1] = {0.f};
     const int cfull = (nchunk / STEP) * STEP;
     int c0 = 0;
     for (; c0 < cfull; c0 += STEP) {
-        issue_block<bf16_t, 1, U, NT, true>(w, sx, rowp, none, none, c0, lane, nchunk);
+        issue_block<bf16_t, 1, U, NT, true>(w, sx, rowp, none, nosrc, c0, lane, nchunk);
         consume_block<T, bf16_t, 1, U, true, XB16>(w, sx, xs, c0, lane, nchunk, acc);
     }
     if (c0 < nchunk) {
-        issue_block<bf16_t, 1, U, NT, false>(w, sx, rowp, none, none, c0, lane, nchunk);
+        issue_block<bf16_t, 1, U, NT, false>(w, sx, rowp, none, nosrc, c0, lane, nchunk);
         consume_block<T, bf16_t, 1, U, false, XB16>(w, sx, xs, c0, lane, nchunk, acc);
     }
     return acc[0];
@@ -489,6 +533,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const T* __restrict__ 
     constexpr int STEP = 64 * U;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int nchunk = K / VE;                    // 16-byte weight chunks per row
+    constexpr bool BYC = IsP13<WT>::v && !SWIGLU;   // the order of a step's image loads: see issue_block
     float* red = x_image_end<RowsImage16<T, WT>::v, VE>(xs, nchunk);
     const int nwaves = gridDim.x * GV_WAVES;
     const int ngroups = SWIGLU ? (N / 2 + (R / 2) - 1) / (R / 2) : (N + R - 1) / R;
@@ -506,15 +551,13 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const T* __restrict__ 
     const long long rowlen = K / WPer<WT>::v;     // WT units per row
     P13Img img = {};
     if constexpr (IsP13<WT>::v) img = p13_img(W, N, K);
-    // the pointers a block's loads start from: the weight row (w13 image: the row's LO bytes), the MXFP4 scale row (w13: the NIB row),
-    // and the w13 SGN row
-    auto row_ptrs = [&](long long row, const WT*& wp, const unsigned char*& sp, const unsigned char*& gp) {
+    // what a block's loads start from: the weight row and the MXFP4 scale row, or the descriptors of the w13 image's LO / NIB / SGN rows
+    auto row_ptrs = [&](long long row, const WT*& wp, const unsigned char*& sp, RowSrc<WT>& pr) {
         if constexpr (IsP13<WT>::v) {
-            wp = reinterpret_cast<const WT*>(img.lo + row * K); sp = img.nib + row * (K / 2); gp = img.sgn + row * (K / 8);
+            wp = nullptr; sp = nullptr; pr = p13_row(img, (int)row, K);
         } else {
             wp = W + row * rowlen;
             sp = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) + row * nchunk : nullptr;
-            gp = nullptr;
         }
     };
     int grp = blockIdx.x * GV_WAVES + wid;
@@ -535,17 +578,19 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const T* __restrict__ 
         if (PF) {
             const int gp = min(grp, ngroups - 1);
             const WT* rowp[R];
-            const unsigned char *srow[R], *grow[R];
+            const unsigned char* srow[R];
+            RowSrc<WT> grow[R];
 #pragma unroll
             for (int r = 0; r < R; ++r) row_ptrs(row_of(gp, r), rowp[r], srow[r], grow[r]);
-            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, grow, 0, lane, nchunk);
+            issue_block<WT, R, U, NT, true, BYC>(wa, sa, rowp, srow, grow, 0, lane, nchunk);
         }
     });
 
     bool have = PF;
     for (; grp < ngroups; grp += nwaves) {
         const WT* rowp[R];
-        const unsigned char *srow[R], *grow[R];
+        const unsigned char* srow[R];
+        RowSrc<WT> grow[R];
         long long rows[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -569,12 +614,12 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_kernel(const T* __restrict__ 
         }
         const int cfull = (nchunk / STEP) * STEP;          // steady state: no bounds checks, no exec masking
         for (; c0 < cfull; c0 += STEP) {
-            issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, grow, c0, lane, nchunk);
+            issue_block<WT, R, U, NT, true, BYC>(wa, sa, rowp, srow, grow, c0, lane, nchunk);
             rebuild_block<WT, R, U>(wa, rpm);
             consume_block<T, WT, R, U, true, RowsImage16<T, WT>::v>(wa, sa, xs, c0, lane, nchunk, acc);
         }
         if (c0 < nchunk) {
-            issue_block<WT, R, U, NT, false>(wa, sa, rowp, srow, grow, c0, lane, nchunk);
+            issue_block<WT, R, U, NT, false, BYC>(wa, sa, rowp, srow, grow, c0, lane, nchunk);
             rebuild_block<WT, R, U>(wa, rpm);
             consume_block<T, WT, R, U, false, RowsImage16<T, WT>::v>(wa, sa, xs, c0, lane, nchunk, acc);
         }
@@ -639,7 +684,7 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
     for (int r = 0; r < R; ++r) acc[r] = 0.f;
     const WT* wrow[R];
     const unsigned char* srow[R];                         // MXFP4: the rows' e8m0 bytes, one per chunk
-    const unsigned char* grow[R];                         // w13 image: wrow / srow / grow are the rows' LO / NIB / SGN bytes
+    RowSrc<WT> prow[R];                                   // w13 image: the descriptors of the rows' LO / NIB / SGN bytes
     // and its row table entries: requested here (scalar loads, all R before any is looked at), consumed behind each step's loads
     unsigned rt[R], rpm[R];
     P13Img img = {};
@@ -648,12 +693,12 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
     for (int r = 0; r < R; ++r) {
         const long long row = min(row0 + r, N - 1);
         if constexpr (IsP13<WT>::v) {
-            wrow[r] = reinterpret_cast<const WT*>(img.lo + row * K); srow[r] = img.nib + row * (K / 2); grow[r] = img.sgn + row * (K / 8);
+            wrow[r] = nullptr; srow[r] = nullptr; prow[r] = p13_row(img, (int)row, K);
             rt[r] = img.rt[row];
         } else {
             wrow[r] = W + row * (K / WPer<WT>::v);
             srow[r] = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) + row * nchunk : nullptr;
-            grow[r] = nullptr; rt[r] = 0u;
+            rt[r] = 0u;
         }
         rpm[r] = 0u;
     }
@@ -663,6 +708,8 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
         uint4 xr[U][XL];
         uint4 w[U][R];
         unsigned sx[U][R];
+        int tl = 0;                                       // w13 image: the thread's chunk of a 256-chunk round (wid * 64 + lane)
+        if constexpr (IsP13<WT>::v) tl = p13_step_lane(tid);
         if constexpr (IsMx<WT>::v) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -683,8 +730,8 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
             const int c = cb + u * 256 + wid * 64 + lane;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                if constexpr (IsP13<WT>::v)
-                    w[u][r] = (FULL || c < nchunk) ? p13_load<NT>(reinterpret_cast<const unsigned char*>(wrow[r]), srow[r], grow[r], c) : make_uint4(0, 0, 0, 0);
+                if constexpr (IsP13<WT>::v)            // (the tail step's chunks past the row: zeros from the range check, no exec masking)
+                    w[u][r] = p13_load<NT, FULL>(prow[r], tl, cb, u * 256);
                 else
                     w[u][r] = (FULL || c < nchunk) ? ld16<NT>(wrow[r] + (long long)c * CU<WT>::v) : make_uint4(0, 0, 0, 0);
             }
@@ -824,12 +871,12 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_qkv_rope_kernel(const WT* __r
     const unsigned char* sbase = IsMx<WT>::v ? reinterpret_cast<const unsigned char*>(wscale) : nullptr;
     P13Img img = {};
     if constexpr (IsP13<WT>::v) img = p13_img(W, (H + 2 * Hk) * hd, K);
-    // a row's load pointers (see gemv_kernel): weights / MXFP4 scales, or the w13 image's LO / NIB / SGN rows
-    auto row_ptrs = [&](long long row, const WT*& wp, const unsigned char*& sp, const unsigned char*& gp) {
+    // what a row's loads start from (see gemv_kernel): weights / MXFP4 scales, or the descriptors of the w13 image's LO / NIB / SGN rows
+    auto row_ptrs = [&](long long row, const WT*& wp, const unsigned char*& sp, RowSrc<WT>& pr) {
         if constexpr (IsP13<WT>::v) {
-            wp = reinterpret_cast<const WT*>(img.lo + row * K); sp = img.nib + row * (K / 2); gp = img.sgn + row * (K / 8);
+            wp = nullptr; sp = nullptr; pr = p13_row(img, (int)row, K);
         } else {
-            wp = W + row * rowlen; sp = sbase ? sbase + row * nchunk : nullptr; gp = nullptr;
+            wp = W + row * rowlen; sp = sbase ? sbase + row * nchunk : nullptr;
         }
     };
     const int grp0 = blockIdx.x * GV_WAVES + wid;
@@ -849,7 +896,8 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_qkv_rope_kernel(const WT* __r
             int head, i0;
             rows_of(min(grp0, ngroups - 1), rows, head, i0);
             const WT* rowp[R];
-            const unsigned char *srow[R], *grow[R];
+            const unsigned char* srow[R];
+            RowSrc<WT> grow[R];
 #pragma unroll
             for (int r = 0; r < R; ++r) row_ptrs(rows[r], rowp[r], srow[r], grow[r]);
             issue_block<WT, R, U, NT, true>(wa, sa, rowp, srow, grow, 0, lane, nchunk);
@@ -862,7 +910,8 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_qkv_rope_kernel(const WT* __r
         int head = 0, i0 = 0;
         const bool is_qk = rows_of(grp, rows, head, i0);
         const WT* rowp[R];
-        const unsigned char *srow[R], *grow[R];
+        const unsigned char* srow[R];
+        RowSrc<WT> grow[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) row_ptrs(rows[r], rowp[r], srow[r], grow[r]);
         // rotation coefficients of this pair: loaded before the weight stream so the epilogue never waits on memory.  No branch around
