@@ -16,7 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .decode_host import (SEED_MASK, PtrArrays, StepGraphs, _p, alloc_loop_state, arm_sampler, prefill_append, profile_steps, run_prefill,
+from .decode_host import (LINEAR_KINDS, SEED_MASK, PtrArrays, StepGraphs, _p, alloc_loop_state, arm_sampler, prefill_append, profile_steps, run_prefill,
                           sync_desc_options)
 from .engine import dequantize_mxfp4_blocks, reinterleave_gate_up, tile_weights, tile_weights_mxfp4
 
@@ -64,7 +64,7 @@ class BatchDecoder(StepGraphs, PtrArrays):
             q4, e4 = engine.llama_w4
             self.block8 = True                    # (intermediate_size % 128 == 0)
             tq, te = {}, {}
-            for k in ("qkv", "o", "gateup", "down"):
+            for k in LINEAR_KINDS:
                 tq[k], te[k] = [], []
                 for q, e in zip(q4[k], e4[k]):
                     if k == "gateup":             # rows re-interleaved to blocks of 8, codes and exponents alike
@@ -75,10 +75,8 @@ class BatchDecoder(StepGraphs, PtrArrays):
             head = tile_weights(engine.lm_head)
             self.tiled_w4 = (tq, te)
             self.tiled_w = (None, head)           # no 16-bit tiled copies of the layer matrices
-            d.qkv_w4, d.qkv_e4 = self._arr(tq["qkv"]), self._arr(te["qkv"])
-            d.o_w4, d.o_e4 = self._arr(tq["o"]), self._arr(te["o"])
-            d.gateup_w4, d.gateup_e4 = self._arr(tq["gateup"]), self._arr(te["gateup"])
-            d.down_w4, d.down_e4 = self._arr(tq["down"]), self._arr(te["down"])
+            self._bind_kinds(d, "_w4", tq)
+            self._bind_kinds(d, "_e4", te)
             d.lm_head = head.data_ptr()
         elif engine.mxfp4_only:
             # an mxfp4_only engine has no 16-bit layer matrices and this decoder cannot take the tiled 4-bit step (tiled=False): it owns
@@ -86,7 +84,7 @@ class BatchDecoder(StepGraphs, PtrArrays):
             q4, e4 = engine.llama_w4
             self.block8 = self.tiled and c.intermediate_size % 16 == 0
             tw = {}
-            for k in ("qkv", "o", "gateup", "down"):
+            for k in LINEAR_KINDS:
                 tw[k] = []
                 for q, e in zip(q4[k], e4[k]):
                     w = dequantize_mxfp4_blocks(q, e)
@@ -95,27 +93,23 @@ class BatchDecoder(StepGraphs, PtrArrays):
                     tw[k].append(w)
             head = tile_weights(engine.lm_head) if self.tiled else engine.lm_head
             self.tiled_w = (tw, head)
-            d.qkv_w, d.o_w = self._arr(tw["qkv"]), self._arr(tw["o"])
-            d.gateup_w, d.down_w = self._arr(tw["gateup"]), self._arr(tw["down"])
+            self._bind_kinds(d, "_w", tw)
             d.lm_head = head.data_ptr()
         elif self.tiled:
             src = engine.llama_w8[0] if fp8 else engine.llama_w
             # gate/up: pairs re-interleaved in blocks of 8 rows so a gate row and its up row share one 16-row tile
             self.block8 = c.intermediate_size % 16 == 0
             tw = {k: [tile_weights(reinterleave_gate_up(w, 8) if (k == "gateup" and self.block8) else w) for w in src[k]]
-                  for k in ("qkv", "o", "gateup", "down")}
+                  for k in LINEAR_KINDS}
             if fp8 and self.block8:
                 self.gateup_s8 = [reinterleave_gate_up(s_.view(-1, 1), 8).view(-1).contiguous() for s_ in engine.llama_w8[1]["gateup"]]
                 d.gateup_s = self._arr(self.gateup_s8)
             head = tile_weights(engine.lm_head8 if fp8 else engine.lm_head)
             self.tiled_w = (tw, head)
+            self._bind_kinds(d, "_w8" if fp8 else "_w", tw)
             if fp8:
-                d.qkv_w8, d.o_w8 = self._arr(tw["qkv"]), self._arr(tw["o"])
-                d.gateup_w8, d.down_w8 = self._arr(tw["gateup"]), self._arr(tw["down"])
                 d.lm_head8 = head.data_ptr()
             else:
-                d.qkv_w, d.o_w = self._arr(tw["qkv"]), self._arr(tw["o"])
-                d.gateup_w, d.down_w = self._arr(tw["gateup"]), self._arr(tw["down"])
                 d.lm_head = head.data_ptr()
         self.desc = d
         # the engine's per-engine options (TeoEngine.set_options) reach the copies made above: the slot descriptors' *_w4 arrays are

@@ -66,32 +66,48 @@ int decode_state_check(const teo_llama_desc* d, const teo_decode_state* st, cons
         TEO_CHECK_ARG(st->d_rng && st->temperature > 0.f, "%s: null d_rng or temperature %g", who, st->temperature);
         const int rc = sampler_check(d->vocab, st->top_k, st->top_p); if (rc != TEO_OK) return rc;
     }
-    return TEO_OK;
+    return llama_weights_check(d, {WeightUse::STEP, who});
 }
 
-// teo_llama_desc.prefill_w4 and the 16-bit layer pointers it makes optional: argument checks of every prefill entry (those of prefix.hip
-// and branches.hip too), before any launch
-int llama_prefill_check_weights(const teo_llama_desc* d) {
-    TEO_CHECK_ARG(!d->prefill_w4a8 || d->prefill_w4, "prefill: prefill_w4a8 is an option of prefill_w4 = 1");
-    if (!d->prefill_w4) {
-        TEO_CHECK_ARG(d->qkv_w && d->o_w && d->gateup_w && d->down_w,
-                      "prefill: the 16-bit qkv / o / gateup / down matrices are missing (a 4-bit-only descriptor needs prefill_w4 = 1)");
-        return TEO_OK;
+// Is the descriptor a legal carrier of the weights `use` reads?  Every entry point that takes a LLaMA descriptor runs this before its
+// first launch (runtime.h).  A use reads the MXFP4 copies when its option says so -- teo_llama_desc.prefill_w4, the batched state's
+// w_mxfp4 -- and the single step whenever any of them is set; otherwise it ignores them.  A use that reads neither them nor fp8 copies
+// reads the 16-bit matrices, which a 4-bit-only descriptor leaves NULL.  All TEO_ERR_ARG conditions come before the TEO_ERR_UNSUPPORTED ones.
+int llama_weights_check(const teo_llama_desc* d, const WeightUse& use) {
+    const char* who = use.who;
+    const int Hq = d->heads * d->head_dim;
+    bool all16 = true, any8 = d->lm_head8 != nullptr, any4 = false, all4 = true, any13 = d->lm_head_p13 != nullptr;
+    for (int k = 0; k < LIN_KINDS; ++k) {
+        const LinearForms f = linear_forms(d, (LinearKind)k);
+        all16 = all16 && f.w16; any8 = any8 || f.w8; any4 = any4 || f.w4 || f.e4; all4 = all4 && f.w4 && f.e4; any13 = any13 || f.p13;
     }
-    TEO_CHECK_ARG(d->qkv_w4 && d->qkv_e4 && d->o_w4 && d->o_e4 && d->gateup_w4 && d->gateup_e4 && d->down_w4 && d->down_e4,
-                  "prefill: prefill_w4 needs all of qkv/o/gateup/down _w4 and _e4");
-    TEO_CHECK_ARG(!d->qkv_w8 && !d->o_w8 && !d->gateup_w8 && !d->down_w8 && !d->lm_head8,
-                  "prefill: a descriptor carries fp8 (w8) or MXFP4 (w4) weights, not both");
-    TEO_CHECK_ARG(d->dtype == TEO_BF16, "prefill: prefill_w4 needs bf16 activations");
-    TEO_CHECK_ARG(!d->prefill_fp8, "prefill: prefill_w4 and prefill_fp8 exclude each other");
-    if (d->hidden % 128 != 0 || d->inter % 128 != 0 || (d->heads * d->head_dim) % 128 != 0) {
-        set_error("prefill: prefill_w4 needs hidden %d, heads * head_dim %d and inter %d to be multiples of 128", d->hidden,
-                  d->heads * d->head_dim, d->inter);
+    const bool prefill = use.kind == WeightUse::PREFILL, step = use.kind == WeightUse::STEP;
+    const bool w4 = prefill ? d->prefill_w4 != 0 : (step ? any4 : use.w_mxfp4);
+    const char* w4_opt = prefill ? "prefill_w4" : (step ? "the MXFP4 copies" : "w_mxfp4");
+    if (prefill) TEO_CHECK_ARG(!d->prefill_w4a8 || d->prefill_w4, "%s: prefill_w4a8 is an option of prefill_w4 = 1", who);
+    if (w4) {
+        TEO_CHECK_ARG(all4, "%s: %s needs all of qkv/o/gateup/down _w4 and _e4", who, w4_opt);
+        TEO_CHECK_ARG(!any8, "%s: a descriptor carries fp8 (w8) or MXFP4 (w4) weights, not both", who);
+        TEO_CHECK_ARG(d->dtype == TEO_BF16, "%s: %s needs bf16 activations", who, w4_opt);
+        TEO_CHECK_ARG(prefill || step || use.w_tiled, "%s: w_mxfp4 reads the TEO_GEMM_WTILED layout (w_tiled = 1)", who);
+        TEO_CHECK_ARG(!prefill || !d->prefill_fp8, "%s: prefill_w4 and prefill_fp8 exclude each other", who);
+    } else if (prefill || decode_weight_format(d, false) == GV_W_NATIVE) {
+        TEO_CHECK_ARG(all16, "%s: the 16-bit qkv / o / gateup / down matrices are missing (a 4-bit-only descriptor needs %s)", who,
+                      prefill ? "prefill_w4 = 1" : (step ? "all of its _w4 / _e4 arrays" : "w_mxfp4 = 1"));
+    }
+    if (step && any13) {      // w13 images of the bf16 matrices, which only the single step reads
+        TEO_CHECK_ARG(!any4 && !any8, "%s: a descriptor carries w13 images or fp8 (w8) / MXFP4 (w4) decode weights, not both", who);
+        TEO_CHECK_ARG(d->dtype == TEO_BF16, "%s: w13 images need bf16 activations", who);
+        TEO_CHECK_ARG(d->hidden % 8 == 0 && Hq % 8 == 0 && d->inter % 8 == 0,
+                      "%s: w13 images need hidden, heads * head_dim and inter to be multiples of 8", who);
+    }
+    if (w4 && !step && (d->hidden % 128 != 0 || d->inter % 128 != 0 || Hq % 128 != 0)) {
+        set_error("%s: %s needs hidden %d, heads * head_dim %d and inter %d to be multiples of 128", who, w4_opt, d->hidden, Hq, d->inter);
         return TEO_ERR_UNSUPPORTED;
     }
-    if (d->prefill_w4a8 && (d->hidden > 12288 || d->inter > 12288 || d->heads * d->head_dim > 12288)) {
-        set_error("prefill: prefill_w4a8 quantises rows of at most 12288 elements (hidden %d, heads * head_dim %d, inter %d)", d->hidden,
-                  d->heads * d->head_dim, d->inter);
+    if (w4 && prefill && d->prefill_w4a8 && (d->hidden > 12288 || d->inter > 12288 || Hq > 12288)) {
+        set_error("%s: prefill_w4a8 quantises rows of at most 12288 elements (hidden %d, heads * head_dim %d, inter %d)", who, d->hidden, Hq,
+                  d->inter);
         return TEO_ERR_UNSUPPORTED;
     }
     return TEO_OK;
@@ -551,10 +567,10 @@ int teo_llama_decode_begin(const teo_llama_desc* d, const teo_decode_state* st, 
 int teo_llama_decode_graph_create(const teo_llama_desc* d, const teo_decode_state* st, void* ws, size_t wsb,
                                   teo_stream_t s, teo_graph** out) {
     ENTER();
-    NEED(d, "desc"); NEED(st, "state"); NEED(ws, "workspace"); NEED(out, "out"); NEED_DT(d->dtype);
+    { const int rc = decode_state_check(d, st, __func__); if (rc != TEO_OK) return rc; }
+    NEED(ws, "workspace"); NEED(out, "out");
     TuneScope tune_scope(d->tune);
     TEO_CHECK_ARG(s != nullptr, "teo_llama_decode_graph_create: needs a non-default stream to capture on");
-    if (st->do_sample) { const int rc = sampler_check(d->vocab, st->top_k, st->top_p); if (rc != TEO_OK) return rc; }
     return decode_graph_create(d, st, ws, wsb, ST(s), out);
 }
 
@@ -570,24 +586,7 @@ static int check_batch_state(const teo_llama_desc* d, const teo_decode_batch_sta
         NEED(st->d_rng, "d_rng"); TEO_CHECK_ARG(st->temperature > 0.f, "decode batch: temperature %g", st->temperature);
         const int rc = sampler_check(d->vocab, st->top_k, st->top_p); if (rc != TEO_OK) return rc;
     }
-    if (st->w_mxfp4) {                                    // MXFP4 layer matrices (tiled): checked before any launch
-        TEO_CHECK_ARG(d->qkv_w4 && d->qkv_e4 && d->o_w4 && d->o_e4 && d->gateup_w4 && d->gateup_e4 && d->down_w4 && d->down_e4,
-                      "decode batch: w_mxfp4 needs all of qkv/o/gateup/down _w4 and _e4");
-        TEO_CHECK_ARG(st->w_tiled, "decode batch: w_mxfp4 reads the TEO_GEMM_WTILED layout (w_tiled = 1)");
-        TEO_CHECK_ARG(!d->qkv_w8 && !d->o_w8 && !d->gateup_w8 && !d->down_w8 && !d->lm_head8,
-                      "decode batch: a descriptor carries fp8 (w8) or MXFP4 (w4) decode weights, not both");
-        TEO_CHECK_ARG(d->dtype == TEO_BF16, "decode batch: MXFP4 weights need bf16 activations");
-        if (d->hidden % 128 != 0 || d->inter % 128 != 0 || (d->heads * d->head_dim) % 128 != 0) {
-            set_error("decode batch: w_mxfp4 needs hidden %d, heads * head_dim %d and inter %d to be multiples of 128", d->hidden,
-                      d->heads * d->head_dim, d->inter);
-            return TEO_ERR_UNSUPPORTED;
-        }
-    }
-    // a 4-bit-only descriptor (NULL 16-bit layer matrices, teo_llama_desc.prefill_w4) cannot run the 16-bit step
-    if (!st->w_mxfp4 && !d->qkv_w8)
-        TEO_CHECK_ARG(d->qkv_w && d->o_w && d->gateup_w && d->down_w,
-                      "decode batch: the 16-bit qkv / o / gateup / down matrices are missing (a 4-bit-only descriptor needs w_mxfp4 = 1)");
-    return TEO_OK;
+    return llama_weights_check(d, {WeightUse::BATCH, "decode batch", st->w_tiled != 0, st->w_mxfp4 != 0});
 }
 
 size_t teo_llama_decode_batch_workspace_bytes(const teo_llama_desc* d, int batch) {
@@ -630,19 +629,9 @@ int teo_llama_decode_batch_graph_create(const teo_llama_desc* d, const teo_decod
 }
 
 // ---- stream decode: the batched step over slots that park themselves ----
-static teo_decode_batch_state stream_batch_view(const teo_decode_stream_state* st) {
-    teo_decode_batch_state b;
-    memset(&b, 0, sizeof(b));
-    b.batch = st->batch; b.out_stride = st->out_stride; b.cache_stride = st->cache_stride;
-    b.w_tiled = st->w_tiled; b.gateup_block8 = st->gateup_block8; b.w_mxfp4 = st->w_mxfp4;
-    b.d_token = st->d_token; b.d_pos = st->d_pos; b.d_out_tokens = st->d_out_tokens; b.d_out_count = st->d_out_count; b.d_stop = st->d_stop;
-    b.d_stop_ids = st->d_stop_ids; b.n_stop_ids = st->n_stop_ids; b.d_logits = st->d_logits;
-    b.do_sample = st->do_sample; b.top_k = st->top_k; b.temperature = st->temperature; b.d_rng = st->d_rng; b.top_p = st->top_p;
-    return b;
-}
 static int check_stream_state(const teo_llama_desc* d, const teo_decode_stream_state* st) {
     NEED(d, "desc"); NEED(st, "state"); NEED(st->d_limit, "d_limit");
-    const teo_decode_batch_state b = stream_batch_view(st);         // the rest is the batched step's contract
+    const teo_decode_batch_state b = stream_as_batch(st);           // the rest is the batched step's contract
     return check_batch_state(d, &b);
 }
 
@@ -688,12 +677,10 @@ static int check_verify_state(const teo_llama_desc* d, const teo_verify_state* s
     TEO_CHECK_ARG(d->max_seq >= st->rows, "verify: max_seq %d below rows %d", d->max_seq, st->rows);
     // the rest is the batched step's contract on the same descriptor: sampler, MXFP4 / tiled weights, 4-bit-only descriptors
     teo_decode_batch_state b;
-    memset(&b, 0, sizeof(b));
+    copy_loop_state(b, *st);
     b.batch = st->rows; b.out_stride = st->max_new; b.cache_stride = 1;
     b.w_tiled = st->w_tiled; b.gateup_block8 = st->gateup_block8; b.w_mxfp4 = st->w_mxfp4;
-    b.d_token = st->d_rows; b.d_pos = st->d_pos; b.d_out_tokens = st->d_out_tokens; b.d_out_count = st->d_out_count; b.d_stop = st->d_stop;
-    b.d_logits = st->d_logits; b.do_sample = st->do_sample; b.top_k = st->top_k; b.temperature = st->temperature; b.d_rng = st->d_rng;
-    b.top_p = st->top_p;
+    b.d_token = st->d_rows;                                 // the rows the step embeds (d_token mirrors d_rows[0])
     return check_batch_state(d, &b);
 }
 

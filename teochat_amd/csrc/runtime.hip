@@ -180,8 +180,10 @@ int vit_workspace_status(const teo_vit_desc* d, int T, void* ws, size_t ws_bytes
 // ignored: the pass runs the 16-bit GEMMs
 static bool prefill_uses_fp8(const teo_llama_desc* d) {
     const int Hq = d->heads * d->head_dim;
-    return d->prefill_fp8 && d->dtype == TEO_BF16 && d->qkv_w8 && d->o_w8 && d->gateup_w8 && d->down_w8 && d->hidden % 128 == 0 &&
-           d->inter % 128 == 0 && Hq % 128 == 0 && d->inter <= 12288 && d->hidden <= 12288;
+    bool copies = true;
+    for (int k = 0; k < LIN_KINDS; ++k) copies = copies && linear_forms(d, (LinearKind)k).w8;
+    return d->prefill_fp8 && d->dtype == TEO_BF16 && copies && d->hidden % 128 == 0 && d->inter % 128 == 0 && Hq % 128 == 0 &&
+           d->inter <= 12288 && d->hidden <= 12288;
 }
 
 // One decoder layer on the residual stream w.h over the S rows of a pass; `attend` runs RoPE / KV append / attention on w.qkv -> w.attn.
@@ -195,39 +197,58 @@ enum PrefillMode { PF_W16, PF_W4, PF_FP8, PF_W4A8 };
 static PrefillMode prefill_mode(const teo_llama_desc* d) {
     return prefill_uses_fp8(d) ? PF_FP8 : (d->prefill_w4 ? (d->prefill_w4a8 ? PF_W4A8 : PF_W4) : PF_W16);
 }
-struct LinearForms {        // the per-layer arrays of one Linear layer in every weight format (those its mode does not use may be null)
-    const void* const* w16; const void* const* w8; const float* const* s8; const void* const* w4; const uint8_t* const* e4;
-};
-#define TEO_LINEAR_FORMS(n) LinearForms{d->n##_w, d->n##_w8, d->n##_s, d->n##_w4, d->n##_e4}
+
+// The descriptor's weight formats (runtime.h): the accessor, and what one launch of layer l takes in the format `wf` a walk runs in.  The
+// three walks -- prefill_layer, llama_decode_step, decode_batch_layers -- each decide `wf` once and otherwise only pick.
+LinearForms linear_forms(const teo_llama_desc* d, LinearKind kind) {
+    switch (kind) {
+    case LIN_QKV: return {d->qkv_w, d->qkv_w8, d->qkv_s, d->qkv_w4, d->qkv_e4, d->qkv_p13};
+    case LIN_O: return {d->o_w, d->o_w8, d->o_s, d->o_w4, d->o_e4, d->o_p13};
+    case LIN_GATEUP: return {d->gateup_w, d->gateup_w8, d->gateup_s, d->gateup_w4, d->gateup_e4, d->gateup_p13};
+    default: return {d->down_w, d->down_w8, d->down_s, d->down_w4, d->down_e4, d->down_p13};
+    }
+}
+// the GEMVs and the skinny GEMM name the three stored formats alike, so one picker serves both
+static_assert((int)GV_W_NATIVE == (int)SK_W_16 && (int)GV_W_FP8 == (int)SK_W_FP8 && (int)GV_W_MXFP4 == (int)SK_W_MXFP4, "weight format codes");
+struct LinearPick { const void* w; const void* s; int fmt; };     // weights; fp8 row scales / MXFP4 block exponents / null; format code
+// images: the single-conversation step's w13 image goes in place of the layer's 16-bit matrix where the descriptor has one
+static LinearPick pick_linear(const LinearForms& f, int wf, int l, bool images = false) {
+    if (wf == GV_W_MXFP4) return {f.w4[l], f.e4[l], wf};
+    if (wf == GV_W_FP8) return {f.w8[l], f.s8[l], wf};
+    if (images && f.p13 && f.p13[l]) return {f.p13[l], nullptr, GV_W_P13};
+    return {f.w16[l], nullptr, wf};
+}
 
 template <typename F>
 static int prefill_layer(const teo_llama_desc* d, const PrefillWs& w, PrefillMode mode, int l, int S, F attend, hipStream_t st) {
     const int dt = d->dtype, D = d->hidden, Hq = d->heads * d->head_dim, QKV = Hq + 2 * d->kv_heads * d->head_dim, Fi = d->inter;
     const bool a8 = mode == PF_FP8 || mode == PF_W4A8;
+    const int wf = mode == PF_FP8 ? GV_W_FP8 : (mode == PF_W16 ? GV_W_NATIVE : GV_W_MXFP4);
     // out[S, N] = x[S, K] . W^T (+ res); x is w.q8 / w.qs in the a8 modes.  The stream-K workspace goes to every 16-bit GEMM, to the fp8
     // GEMM of o and down only and to no MXFP4 GEMM: the planners choose by it
-    auto matmul = [&](const void* x, const LinearForms& f, const void* res, void* out, int N, int K, int ldc, unsigned flags) -> int {
+    auto matmul = [&](const void* x, LinearKind kind, const void* res, void* out, int N, int K, int ldc, unsigned flags) -> int {
+        const LinearPick p = pick_linear(linear_forms(d, kind), wf, l);
         switch (mode) {
-        case PF_FP8: return gemm_fp8(w.q8, w.qs, f.w8[l], f.s8[l], res, out, S, N, K, K, ldc, flags, dt, st, res ? w.sk : nullptr);
-        case PF_W4A8: return gemm_w4a8(w.q8, w.qs, f.w4[l], f.e4[l], res, out, S, N, K, K, ldc, flags, dt, st);
-        case PF_W4: return gemm_w4(x, f.w4[l], f.e4[l], res, out, S, N, K, K, ldc, flags, dt, st);
-        default: return gemm(x, f.w16[l], nullptr, res, out, S, N, K, K, ldc, TEO_ACT_NONE, flags, dt, dt, st, w.sk);
+        case PF_FP8: return gemm_fp8(w.q8, w.qs, p.w, (const float*)p.s, res, out, S, N, K, K, ldc, flags, dt, st, res ? w.sk : nullptr);
+        case PF_W4A8: return gemm_w4a8(w.q8, w.qs, p.w, p.s, res, out, S, N, K, K, ldc, flags, dt, st);
+        case PF_W4: return gemm_w4(x, p.w, p.s, res, out, S, N, K, K, ldc, flags, dt, st);
+        default: return gemm(x, p.w, nullptr, res, out, S, N, K, K, ldc, TEO_ACT_NONE, flags, dt, dt, st, w.sk);
         }
     };
-    auto project_normed = [&](const void* norm_w, const LinearForms& f, void* out, int N, int ldc, unsigned flags) -> int {   // out = Linear(RMSNorm(w.h))
+    auto project_normed = [&](const void* norm_w, LinearKind kind, void* out, int N, int ldc, unsigned flags) -> int {   // out = Linear(RMSNorm(w.h))
         if (a8) TEO_TRY(quant_rows_fp8(w.h, norm_w, w.q8, w.qs, S, D, D, d->eps, st));
         else TEO_TRY(rmsnorm(w.h, norm_w, w.n, S, D, d->eps, dt, st));
-        return matmul(w.n, f, nullptr, out, N, D, ldc, flags);
+        return matmul(w.n, kind, nullptr, out, N, D, ldc, flags);
     };
-    auto project_residual = [&](const void* x, const LinearForms& f, int K) -> int {                                             // w.h += Linear(x)
+    auto project_residual = [&](const void* x, LinearKind kind, int K) -> int {                                             // w.h += Linear(x)
         if (a8) TEO_TRY(quant_rows_fp8(x, nullptr, w.q8, w.qs, S, K, K, d->eps, st));
-        return matmul(x, f, w.h, w.h, D, K, D, 0);
+        return matmul(x, kind, w.h, w.h, D, K, D, 0);
     };
-    TEO_TRY(project_normed(d->in_norm_w[l], TEO_LINEAR_FORMS(qkv), w.qkv, QKV, QKV, 0));
+    TEO_TRY(project_normed(d->in_norm_w[l], LIN_QKV, w.qkv, QKV, QKV, 0));
     TEO_TRY(attend());
-    TEO_TRY(project_residual(w.attn, TEO_LINEAR_FORMS(o), Hq));
-    TEO_TRY(project_normed(d->post_norm_w[l], TEO_LINEAR_FORMS(gateup), w.act, 2 * Fi, Fi, TEO_GEMM_SWIGLU16));
-    return project_residual(w.act, TEO_LINEAR_FORMS(down), Fi);
+    TEO_TRY(project_residual(w.attn, LIN_O, Hq));
+    TEO_TRY(project_normed(d->post_norm_w[l], LIN_GATEUP, w.act, 2 * Fi, Fi, TEO_GEMM_SWIGLU16));
+    return project_residual(w.act, LIN_DOWN, Fi);
 }
 
 // hidden_states (optional, `output_hidden_states` of the kept forward signature, llava_llama.py:56-69): [layers + 1][S][hidden] in the model
@@ -388,23 +409,6 @@ size_t llama_decode_workspace_bytes(const teo_llama_desc* d) { return decode_car
 
 // g (optional, include/teo_hip_guide.h): the guided tail instead of the plain one; every launch in front of it is the same
 int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st, const teo_guide* g) {
-    // MXFP4 copies: all eight per-layer arrays or none, never beside the fp8 copies, bf16 activations (checked before any launch)
-    const bool w4 = d->qkv_w4 != nullptr;
-    if (w4 || d->qkv_e4 || d->o_w4 || d->o_e4 || d->gateup_w4 || d->gateup_e4 || d->down_w4 || d->down_e4) {
-        TEO_CHECK_ARG(d->qkv_w4 && d->qkv_e4 && d->o_w4 && d->o_e4 && d->gateup_w4 && d->gateup_e4 && d->down_w4 && d->down_e4,
-                      "teo_llama_decode_step: the MXFP4 copies need all of qkv/o/gateup/down _w4 and _e4");
-        TEO_CHECK_ARG(!d->qkv_w8 && !d->o_w8 && !d->gateup_w8 && !d->down_w8 && !d->lm_head8,
-                      "teo_llama_decode_step: a descriptor carries fp8 (w8) or MXFP4 (w4) decode weights, not both");
-        TEO_CHECK_ARG(d->dtype == TEO_BF16, "teo_llama_decode_step: MXFP4 weights need bf16 activations");
-    }
-    // w13 images of the bf16 matrices: never beside the fp8 / MXFP4 copies, bf16 only (checked before any launch)
-    if (d->qkv_p13 || d->o_p13 || d->gateup_p13 || d->down_p13 || d->lm_head_p13) {
-        TEO_CHECK_ARG(!w4 && !d->qkv_w8 && !d->o_w8 && !d->gateup_w8 && !d->down_w8 && !d->lm_head8,
-                      "teo_llama_decode_step: a descriptor carries w13 images or fp8 (w8) / MXFP4 (w4) decode weights, not both");
-        TEO_CHECK_ARG(d->dtype == TEO_BF16, "teo_llama_decode_step: w13 images need bf16 activations");
-        TEO_CHECK_ARG(d->hidden % 8 == 0 && (d->heads * d->head_dim) % 8 == 0 && d->inter % 8 == 0,
-                      "teo_llama_decode_step: w13 images need hidden, heads * head_dim and inter to be multiples of 8");
-    }
     const DecodeWs w = decode_carve(d, ws, ws_bytes);
     if (w.total > ws_bytes) {
         set_error("teo_llama_decode_step: workspace %zu < %zu", ws_bytes, w.total);
@@ -414,44 +418,34 @@ int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* 
     const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim, F = d->inter;
     const int QKV = (H + 2 * Hk) * hd;
     // w.h holds the embedding of *s->d_token: written by the previous step's tail (or by teo_llama_decode_begin)
-    const bool w8 = d->qkv_w8 != nullptr;              // decode streams the fp8 or MXFP4 copies when they are present
-    const int wf = w4 ? GV_W_MXFP4 : (w8 ? GV_W_FP8 : GV_W_NATIVE);
-    // (a w13 image, where the layer has one, goes in place of the 16-bit matrix: fmt() tells the GEMV which of the two lin() returned)
-    auto p13 = [&](const void* const* im, int l) -> const void* { return (!w4 && !w8 && im) ? im[l] : nullptr; };
-    auto lin = [&](const void* const* w16, const void* const* q8, const void* const* q4, const void* const* im, int l) {
-        return w4 ? q4[l] : (w8 ? q8[l] : (p13(im, l) ? p13(im, l) : w16[l]));
-    };
-    auto fmt = [&](const void* const* im, int l) { return p13(im, l) ? (int)GV_W_P13 : wf; };
-    auto scl = [&](const float* const* s8, const uint8_t* const* e4, int l) -> const void* { return w4 ? (const void*)e4[l] : (w8 ? (const void*)s8[l] : nullptr); };
+    // decode streams the MXFP4 or fp8 copies when they are present, else per layer the w13 image or the 16-bit matrix
+    const int wf = decode_weight_format(d, linear_forms(d, LIN_QKV).w4 != nullptr);
     for (int l = 0; l < d->layers; ++l) {
+        const LinearPick qkv = pick_linear(linear_forms(d, LIN_QKV), wf, l, true), o = pick_linear(linear_forms(d, LIN_O), wf, l, true);
+        const LinearPick gu = pick_linear(linear_forms(d, LIN_GATEUP), wf, l, true), dn = pick_linear(linear_forms(d, LIN_DOWN), wf, l, true);
         if (d->rope_in_attn) {
             // rmsnorm + QKV projection (plain weight stream); RoPE + KV append ride inside the attention kernel
             // (position read from s->d_pos on the device)
             prof_class(TEO_PROF_QKV);
-            TEO_TRY(gemv_w(w.h, lin(d->qkv_w, d->qkv_w8, d->qkv_w4, d->qkv_p13, l), scl(d->qkv_s, d->qkv_e4, l), fmt(d->qkv_p13, l), d->in_norm_w[l],
-                           nullptr, w.qkv, QKV, D, d->eps, 0, dt, dt, st));
+            TEO_TRY(gemv_w(w.h, qkv.w, qkv.s, qkv.fmt, d->in_norm_w[l], nullptr, w.qkv, QKV, D, d->eps, 0, dt, dt, st));
             prof_class(TEO_PROF_ATTN);
             TEO_TRY(attn_decode(w.qkv, d->k_cache[l], d->v_cache[l], d->vt_cache[l], d->rope_cos, d->rope_sin, w.attn, w.part,
                                 s->d_pos, d->max_seq, H, Hk, hd, 1.0f / sqrtf((float)hd), dt, st));
         } else {
             // rmsnorm -> QKV projection -> RoPE -> KV append in the GEMV epilogue
             prof_class(TEO_PROF_QKV);
-            TEO_TRY(gemv_qkv_rope(w.h, lin(d->qkv_w, d->qkv_w8, d->qkv_w4, d->qkv_p13, l), scl(d->qkv_s, d->qkv_e4, l), fmt(d->qkv_p13, l), d->in_norm_w[l], w.qkv,
-                                  d->rope_cos, d->rope_sin, s->d_pos, d->k_cache[l], d->v_cache[l], d->vt_cache[l], d->max_seq,
-                                  H, Hk, hd, D, d->eps, dt, st));
+            TEO_TRY(gemv_qkv_rope(w.h, qkv.w, qkv.s, qkv.fmt, d->in_norm_w[l], w.qkv, d->rope_cos, d->rope_sin, s->d_pos, d->k_cache[l],
+                                  d->v_cache[l], d->vt_cache[l], d->max_seq, H, Hk, hd, D, d->eps, dt, st));
             prof_class(TEO_PROF_ATTN);
             TEO_TRY(attn_decode(w.qkv, d->k_cache[l], d->v_cache[l], nullptr, nullptr, nullptr, w.attn, w.part, s->d_pos,
                                 d->max_seq, H, Hk, hd, 1.0f / sqrtf((float)hd), dt, st));
         }
         prof_class(TEO_PROF_O);
-        TEO_TRY(gemv_w(w.attn, lin(d->o_w, d->o_w8, d->o_w4, d->o_p13, l), scl(d->o_s, d->o_e4, l), fmt(d->o_p13, l), nullptr, w.h, w.h, D, H * hd, d->eps,
-                       0, dt, dt, st));
+        TEO_TRY(gemv_w(w.attn, o.w, o.s, o.fmt, nullptr, w.h, w.h, D, H * hd, d->eps, 0, dt, dt, st));
         prof_class(TEO_PROF_GATEUP);
-        TEO_TRY(gemv_w(w.h, lin(d->gateup_w, d->gateup_w8, d->gateup_w4, d->gateup_p13, l), scl(d->gateup_s, d->gateup_e4, l), fmt(d->gateup_p13, l), d->post_norm_w[l], nullptr,
-                       w.act, 2 * F, D, d->eps, TEO_GEMM_SWIGLU16, dt, dt, st));
+        TEO_TRY(gemv_w(w.h, gu.w, gu.s, gu.fmt, d->post_norm_w[l], nullptr, w.act, 2 * F, D, d->eps, TEO_GEMM_SWIGLU16, dt, dt, st));
         prof_class(TEO_PROF_DOWN);
-        TEO_TRY(gemv_w(w.act, lin(d->down_w, d->down_w8, d->down_w4, d->down_p13, l), scl(d->down_s, d->down_e4, l), fmt(d->down_p13, l), nullptr, w.h, w.h, D, F, d->eps,
-                       0, dt, dt, st));
+        TEO_TRY(gemv_w(w.act, dn.w, dn.s, dn.fmt, nullptr, w.h, w.h, D, F, d->eps, 0, dt, dt, st));
     }
     {
         const bool h8 = d->lm_head8 != nullptr;          // (the MXFP4 mode keeps a 16-bit lm_head)
@@ -505,7 +499,7 @@ size_t llama_decode_batch_workspace_bytes(const teo_llama_desc* d, int batch) {
 // Can every Linear layer of the step run on the MFMA skinny GEMM?  (bf16 activations, K multiples of the k-step.)
 static bool batch_uses_skinny(const teo_llama_desc* d, int B, bool w4 = false) {
     if (d->dtype != TEO_BF16 && d->dtype != TEO_F16) return false;
-    const int w8 = w4 ? SK_W_MXFP4 : (d->qkv_w8 != nullptr ? SK_W_FP8 : SK_W_16), h8 = d->lm_head8 != nullptr;
+    const int w8 = decode_weight_format(d, w4), h8 = d->lm_head8 != nullptr;
     if (d->dtype == TEO_F16 && (w8 || h8)) return false;   // fp8 weights go with bfloat16 activations
     const int D = d->hidden, H = d->heads, Hk = d->kv_heads, hd = d->head_dim, F = d->inter;
     const void* al = reinterpret_cast<const void*>(16);   // alignment of the real pointers is checked at launch
@@ -527,9 +521,7 @@ static int batch_linear_rows(int B, const void* x, int ldx, const void* W, const
 
 static teo_decode_state batch_as_state(const teo_decode_batch_state* s) {
     teo_decode_state t;
-    t.d_token = s->d_token; t.d_pos = s->d_pos; t.d_out_tokens = s->d_out_tokens; t.d_out_count = s->d_out_count;
-    t.d_stop = s->d_stop; t.d_stop_ids = s->d_stop_ids; t.n_stop_ids = s->n_stop_ids; t.d_logits = s->d_logits;
-    t.do_sample = s->do_sample; t.top_k = s->top_k; t.temperature = s->temperature; t.d_rng = s->d_rng; t.top_p = s->top_p;
+    copy_loop_state(t, *s);
     return t;
 }
 
@@ -557,12 +549,11 @@ static int decode_batch_layers(const teo_llama_desc* d, const BatchLoopOpts& o, 
     const int QKV = (H + 2 * Hk) * hd;
     // w4: the four layer matrices are the descriptor's tiled MXFP4 copies (teo_decode_batch_state.w_mxfp4; the C entry points have
     // checked that they are all there, tiled, bf16 and without fp8 copies); lm_head stays 16-bit
-    const bool w4 = o.w_mxfp4;
-    const bool w8 = d->qkv_w8 != nullptr, h8 = d->lm_head8 != nullptr;
-    const int wf = w4 ? SK_W_MXFP4 : (w8 ? SK_W_FP8 : SK_W_16);
+    const bool w4 = o.w_mxfp4, h8 = d->lm_head8 != nullptr;
+    const int wf = decode_weight_format(d, w4);
     const bool skinny = batch_uses_skinny(d, B, w4);
     if (!skinny && (o.w_tiled || o.gateup_block8 || w4)) {
-        set_error("%s: tiled weights need bf16 activations and K %% %d == 0", who, w4 ? 128 : (w8 ? 64 : 32));
+        set_error("%s: tiled weights need bf16 activations and K %% %d == 0", who, w4 ? 128 : (wf == SK_W_FP8 ? 64 : 32));
         return TEO_ERR_UNSUPPORTED;
     }
     const unsigned tl = o.w_tiled ? TEO_GEMM_WTILED : 0u;
@@ -572,20 +563,13 @@ static int decode_batch_layers(const teo_llama_desc* d, const BatchLoopOpts& o, 
     take.ssq_in = w.ssq; take.nparts = w.nparts; take.eps = d->eps;
     take.f16 = dt == TEO_F16;
     for (int l = 0; l < d->layers; ++l) {
-        const void* qkv_w = w4 ? d->qkv_w4[l] : (w8 ? d->qkv_w8[l] : d->qkv_w[l]);
-        const void* o_w = w4 ? d->o_w4[l] : (w8 ? d->o_w8[l] : d->o_w[l]);
-        const void* gu_w = w4 ? d->gateup_w4[l] : (w8 ? d->gateup_w8[l] : d->gateup_w[l]);
-        const void* dn_w = w4 ? d->down_w4[l] : (w8 ? d->down_w8[l] : d->down_w[l]);
-        // fp8: fp32 row scales; MXFP4: the tiled e8m0 block exponents
-        const void* qkv_s = w4 ? (const void*)d->qkv_e4[l] : (w8 ? (const void*)d->qkv_s[l] : nullptr);
-        const void* o_s = w4 ? (const void*)d->o_e4[l] : (w8 ? (const void*)d->o_s[l] : nullptr);
-        const void* gu_s = w4 ? (const void*)d->gateup_e4[l] : (w8 ? (const void*)d->gateup_s[l] : nullptr);
-        const void* dn_s = w4 ? (const void*)d->down_e4[l] : (w8 ? (const void*)d->down_s[l] : nullptr);
+        const LinearPick qkv = pick_linear(linear_forms(d, LIN_QKV), wf, l), ow = pick_linear(linear_forms(d, LIN_O), wf, l);
+        const LinearPick gu = pick_linear(linear_forms(d, LIN_GATEUP), wf, l), dn = pick_linear(linear_forms(d, LIN_DOWN), wf, l);
         prof_class(TEO_PROF_QKV);
         if (skinny) {
-            TEO_TRY(skinny_gemm(w.hg, qkv_w, qkv_s, wf, nullptr, 0.f, nullptr, w.qkv, B, QKV, D, D, QKV, tl, dt, st, take));
+            TEO_TRY(skinny_gemm(w.hg, qkv.w, qkv.s, wf, nullptr, 0.f, nullptr, w.qkv, B, QKV, D, D, QKV, tl, dt, st, take));
         } else {
-            TEO_TRY(batch_linear_rows(B, w.h, D, qkv_w, qkv_s, w8, d->in_norm_w[l], nullptr, w.qkv, QKV, QKV, D, d->eps, 0, dt, dt, st));
+            TEO_TRY(batch_linear_rows(B, w.h, D, qkv.w, qkv.s, wf, d->in_norm_w[l], nullptr, w.qkv, QKV, QKV, D, d->eps, 0, dt, dt, st));
         }
         // RoPE + KV append of the B new rows inside the attention kernel (w.qkv -> w.attn)
         prof_class(TEO_PROF_ATTN);
@@ -595,21 +579,21 @@ static int decode_batch_layers(const teo_llama_desc* d, const BatchLoopOpts& o, 
             give.f16 = dt == TEO_F16;
             give.next_g = (const unsigned short*)d->post_norm_w[l]; give.xg_out = (unsigned short*)w.hg; give.ssq_out = w.ssq;
             prof_class(TEO_PROF_O);
-            TEO_TRY(skinny_gemm(w.attn, o_w, o_s, wf, nullptr, 0.f, w.h, w.h, B, D, H * hd, H * hd, D, tl, dt, st, give));
+            TEO_TRY(skinny_gemm(w.attn, ow.w, ow.s, wf, nullptr, 0.f, w.h, w.h, B, D, H * hd, H * hd, D, tl, dt, st, give));
             prof_class(TEO_PROF_GATEUP);
-            TEO_TRY(skinny_gemm(w.hg, gu_w, gu_s, wf, nullptr, 0.f, nullptr, w.act, B, 2 * F, D, D, F,
+            TEO_TRY(skinny_gemm(w.hg, gu.w, gu.s, wf, nullptr, 0.f, nullptr, w.act, B, 2 * F, D, D, F,
                                 tl | (o.gateup_block8 ? TEO_GEMM_SWIGLU8 : TEO_GEMM_SWIGLU16), dt, st, take));
             give.next_g = (const unsigned short*)(l + 1 < d->layers ? d->in_norm_w[l + 1] : d->final_norm_w);
             prof_class(TEO_PROF_DOWN);
-            TEO_TRY(skinny_gemm(w.act, dn_w, dn_s, wf, nullptr, 0.f, w.h, w.h, B, D, F, F, D, tl, dt, st, give));
+            TEO_TRY(skinny_gemm(w.act, dn.w, dn.s, wf, nullptr, 0.f, w.h, w.h, B, D, F, F, D, tl, dt, st, give));
         } else {
             prof_class(TEO_PROF_O);
-            TEO_TRY(batch_linear_rows(B, w.attn, H * hd, o_w, o_s, w8, nullptr, w.h, w.h, D, D, H * hd, d->eps, 0, dt, dt, st));
+            TEO_TRY(batch_linear_rows(B, w.attn, H * hd, ow.w, ow.s, wf, nullptr, w.h, w.h, D, D, H * hd, d->eps, 0, dt, dt, st));
             prof_class(TEO_PROF_GATEUP);
-            TEO_TRY(batch_linear_rows(B, w.h, D, gu_w, gu_s, w8, d->post_norm_w[l], nullptr, w.act, F, 2 * F, D, d->eps,
+            TEO_TRY(batch_linear_rows(B, w.h, D, gu.w, gu.s, wf, d->post_norm_w[l], nullptr, w.act, F, 2 * F, D, d->eps,
                                       TEO_GEMM_SWIGLU16, dt, dt, st));
             prof_class(TEO_PROF_DOWN);
-            TEO_TRY(batch_linear_rows(B, w.act, F, dn_w, dn_s, w8, nullptr, w.h, w.h, D, D, F, d->eps, 0, dt, dt, st));
+            TEO_TRY(batch_linear_rows(B, w.act, F, dn.w, dn.s, wf, nullptr, w.h, w.h, D, D, F, d->eps, 0, dt, dt, st));
         }
     }
     const void* head_w = h8 ? d->lm_head8 : d->lm_head;
@@ -677,13 +661,11 @@ int llama_decode_batch_step(const teo_llama_desc* d, const teo_decode_batch_stat
 }
 
 // ---- stream step: the batched step over slots that park themselves (include/teo_hip.h teo_decode_stream_state)
-static teo_decode_batch_state stream_as_batch(const teo_decode_stream_state* s) {
+teo_decode_batch_state stream_as_batch(const teo_decode_stream_state* s) {
     teo_decode_batch_state b;
     b.batch = s->batch; b.out_stride = s->out_stride; b.cache_stride = s->cache_stride;
     b.w_tiled = s->w_tiled; b.gateup_block8 = s->gateup_block8; b.w_mxfp4 = s->w_mxfp4;
-    b.d_token = s->d_token; b.d_pos = s->d_pos; b.d_out_tokens = s->d_out_tokens; b.d_out_count = s->d_out_count; b.d_stop = s->d_stop;
-    b.d_stop_ids = s->d_stop_ids; b.n_stop_ids = s->n_stop_ids; b.d_logits = s->d_logits;
-    b.do_sample = s->do_sample; b.top_k = s->top_k; b.temperature = s->temperature; b.d_rng = s->d_rng; b.top_p = s->top_p;
+    copy_loop_state(b, *s);
     return b;
 }
 

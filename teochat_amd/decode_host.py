@@ -8,7 +8,7 @@ calls.  Each rule that is easy to copy wrongly is stated here and nowhere else:
                      replays, _drop_graph and the one __del__
   profile_steps      the per-class accumulator of the profiled steps
   alloc_loop_state   the eight device tensors of a decode loop and the state fields that point at them
-  PtrArrays          mixin: _arr, a pointer array kept alive beside its tensors
+  PtrArrays          mixin: _arr, a pointer array kept alive beside its tensors; _bind_kinds, one weight format's four arrays of LINEAR_KINDS
   HookList           set_options / tune_set callbacks held through a weak reference to their owner; sync_desc_options, the rule for which
                      descriptor copy receives which option
 
@@ -23,6 +23,7 @@ from . import _lib as L
 
 SEED_MASK = 2 ** 63 - 1            # d_rng is int64 on the host side: one mask for the first draw and every device loop
 MAX_STOP_IDS = 16                  # d_stop_ids holds the LAST 16 ids of a longer stop sequence
+LINEAR_KINDS = ("qkv", "o", "gateup", "down")     # the decoder's four Linear layers: the <kind>_* fields of teo_llama_desc, the keys of llama_w
 PROF_CLASSES = ("qkv_rope_gemv", "attn_decode_partial", "attn_decode_combine", "o_gemv", "gateup_gemv", "down_gemv", "lm_head_gemv",
                 "decode_tail")
 
@@ -38,6 +39,12 @@ class PtrArrays:
         arr, pp = L.ptr_array([t.data_ptr() for t in tensors])
         self._keep.append((arr, tensors))
         return pp
+
+    def _bind_kinds(self, desc, suffix, per_kind):
+        """desc.<kind><suffix> (teo_llama_desc: _w, _w8, _s, _w4, _e4, _p13) = the pointer array over per_kind[kind], for the four
+        Linear kinds; per_kind=None clears the four fields"""
+        for k in LINEAR_KINDS:
+            setattr(desc, k + suffix, None if per_kind is None else self._arr(per_kind[k]))
 
 
 # ---------------------------------------------------------------------- prefill

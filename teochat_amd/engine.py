@@ -20,7 +20,7 @@ import warnings
 import torch
 
 from . import _lib as L
-from .decode_host import (PROF_CLASSES, SEED_MASK, HookList, PtrArrays, StepGraphs, _p, alloc_loop_state, arm_sampler, profile_steps,
+from .decode_host import (LINEAR_KINDS, PROF_CLASSES, SEED_MASK, HookList, PtrArrays, StepGraphs, _p, alloc_loop_state, arm_sampler, profile_steps,
                           run_prefill, sync_desc_options)
 
 _ACT = {"quick_gelu": L.ACT_QUICK_GELU, "gelu": L.ACT_GELU_ERF}
@@ -438,7 +438,7 @@ class TeoEngine(StepGraphs, PtrArrays):
         self.max_pos = max(c.max_position_embeddings, self.max_seq)
         cs, sn = rope_tables(hd, c.rope_theta, self.max_pos)
         self.rope_cos, self.rope_sin = cs.to(self.device), sn.to(self.device)
-        per = {k: [] for k in ("in_norm", "qkv", "o", "post_norm", "gateup", "down")}
+        per = {k: [] for k in ("in_norm", "post_norm") + LINEAR_KINDS}
         self.prefill_mxfp4_a8 = False             # set_options(prefill_mxfp4_a8=True): ... against e4m3 activations (teo_llama_desc.prefill_w4a8)
         self.prefill_mxfp4 = False                # set_options(prefill_mxfp4=True): prefill reads the MXFP4 arrays (teo_llama_desc.prefill_w4)
         fused = {"qkv": lambda p: torch.cat([sd[p + f"self_attn.{n}_proj.weight"] for n in "qkv"], dim=0),
@@ -471,45 +471,32 @@ class TeoEngine(StepGraphs, PtrArrays):
         for i in range(c.num_hidden_layers):
             p = f"model.layers.{i}."
             per["in_norm"].append(self._dev(sd[p + "input_layernorm.weight"]))
-            per["qkv"].append(self._dev(fused["qkv"](p)))
-            per["o"].append(self._dev(fused["o"](p)))
             per["post_norm"].append(self._dev(sd[p + "post_attention_layernorm.weight"]))
-            per["gateup"].append(self._dev(fused["gateup"](p)))
-            per["down"].append(self._dev(fused["down"](p)))
+            for k in LINEAR_KINDS:
+                per[k].append(self._dev(fused[k](p)))
+
+        def quantised(quantiser):
+            """every (already fused / interleaved) layer matrix through quantiser(w) -> (codes, scales, dq): ({kind: codes}, {kind: scales}).
+            The 16-bit tensor, which prefill, the tower and the batched step keep reading, is replaced by dq, the exact dequantisation, so
+            that every path sees the same weights"""
+            q, s = {k: [] for k in LINEAR_KINDS}, {k: [] for k in LINEAR_KINDS}
+            for k in LINEAR_KINDS:
+                for i, w in enumerate(per[k]):
+                    qi, si, per[k][i] = quantiser(w)
+                    q[k].append(qi)
+                    s[k].append(si)
+            return q, s
+
         self.llama_w = per
-        self.llama_w8 = None
-        if self.weight_format == "fp8":
-            # quantise the (already fused / interleaved) Linear weights row-wise; prefill keeps using the bf16 tensors,
-            # which are replaced by the exactly-dequantised values so both paths see identical weights
-            w8 = {k: [] for k in ("qkv", "o", "gateup", "down")}
-            s8 = {k: [] for k in ("qkv", "o", "gateup", "down")}
-            for k in w8:
-                for i in range(c.num_hidden_layers):
-                    q, s, dq = quantize_fp8_rows(per[k][i])
-                    per[k][i] = dq
-                    w8[k].append(q)
-                    s8[k].append(s)
-            q, s, dq = quantize_fp8_rows(self.lm_head)
-            self.lm_head, self.lm_head8, self.lm_head_s = dq, q, s
-            self.llama_w8 = (w8, s8)
-        self.llama_w4 = None
+        self.llama_w8 = self.llama_w4 = None
         self.batch_mxfp4 = False                  # set_options(batch_mxfp4=True): the batched step streams tiled MXFP4 copies too
-        if self.weight_format == "mxfp4":
-            # the same for the single-conversation decode step in MXFP4 (blocks of 32 along K); lm_head stays 16-bit, and prefill, the
-            # tower and the batched step read the bf16 tensors, replaced by the exact dequantisation
-            w4 = {k: [] for k in ("qkv", "o", "gateup", "down")}
-            e4 = {k: [] for k in ("qkv", "o", "gateup", "down")}
-            for k in w4:
-                for i in range(c.num_hidden_layers):
-                    q, e, dq = quantize_mxfp4_blocks(per[k][i])
-                    per[k][i] = dq
-                    w4[k].append(q)
-                    e4[k].append(e)
-            self.llama_w4 = (w4, e4)
+        if self.weight_format == "fp8":           # row-wise e4m3 for the decode steps, lm_head included
+            self.llama_w8 = quantised(quantize_fp8_rows)
+            self.lm_head8, self.lm_head_s, self.lm_head = quantize_fp8_rows(self.lm_head)
+        elif self.weight_format == "mxfp4":       # blocks of 32 along K for the single-conversation decode step; lm_head stays 16-bit
+            self.llama_w4 = quantised(quantize_mxfp4_blocks)
 
     # ------------------------------------------------------------------ w13 images of the decode weights
-    _P13_KINDS = ("qkv", "o", "gateup", "down")
-
     def _decode_pack_applies(self):
         c = self.cfg
         return (self.dtype == torch.bfloat16 and self.weight_format == "native" and not self.mxfp4_only
@@ -518,7 +505,7 @@ class TeoEngine(StepGraphs, PtrArrays):
     def _build_decode_pack(self):
         """Pack every decode matrix, one at a time (the packer's temporaries are freed between matrices).  Returns False, with one log
         line, when free device memory is below twice the images' total."""
-        mats = {k: self.llama_w[k] for k in self._P13_KINDS}
+        mats = {k: self.llama_w[k] for k in LINEAR_KINDS}
         mats["lm_head"] = [self.lm_head]
         total = sum(w13_sections(*w.shape)[1] for ws in mats.values() for w in ws)
         free = torch.cuda.mem_get_info(self.device)[0]
@@ -547,7 +534,7 @@ class TeoEngine(StepGraphs, PtrArrays):
                                                 self.device, total / 1e9)
             return False
         stats["image_bytes"] = nbytes
-        self._p13 = {"imgs": imgs, "arrs": {k: self._arr(imgs[k]) for k in self._P13_KINDS}}
+        self._p13 = {"imgs": imgs}
         self.decode_pack_stats = stats
         return True
 
@@ -555,13 +542,8 @@ class TeoEngine(StepGraphs, PtrArrays):
         d = self.llama_desc
         if on and self._p13 is None and not self._build_decode_pack():
             on = False
-        if on:
-            a = self._p13["arrs"]
-            d.qkv_p13, d.o_p13, d.gateup_p13, d.down_p13 = a["qkv"], a["o"], a["gateup"], a["down"]
-            d.lm_head_p13 = self._p13["imgs"]["lm_head"][0].data_ptr()
-        else:
-            d.qkv_p13 = d.o_p13 = d.gateup_p13 = d.down_p13 = None
-            d.lm_head_p13 = None
+        self._bind_kinds(d, "_p13", self._p13["imgs"] if on else None)
+        d.lm_head_p13 = self._p13["imgs"]["lm_head"][0].data_ptr() if on else None
         self.decode_pack = bool(on)
         self._drop_graph()                        # the pointers are baked into a captured decode step
 
@@ -581,26 +563,17 @@ class TeoEngine(StepGraphs, PtrArrays):
         d.in_norm_w = self._arr(self.llama_w["in_norm"])
         d.post_norm_w = self._arr(self.llama_w["post_norm"])
         if not self.mxfp4_only:                   # (mxfp4_only: the 16-bit layer pointers stay NULL; prefill_w4 below makes prefill not read them)
-            d.qkv_w = self._arr(self.llama_w["qkv"])
-            d.o_w = self._arr(self.llama_w["o"])
-            d.gateup_w = self._arr(self.llama_w["gateup"])
-            d.down_w = self._arr(self.llama_w["down"])
+            self._bind_kinds(d, "_w", self.llama_w)
         d.k_cache = self._arr([self.k_cache[i] for i in range(Lr)])
         d.v_cache = self._arr([self.v_cache[i] for i in range(Lr)])
         d.vt_cache = self._arr([self.vt_cache[i] for i in range(Lr)])
         if self.llama_w8 is not None:
-            w8, s8 = self.llama_w8
-            d.qkv_w8, d.qkv_s = self._arr(w8["qkv"]), self._arr(s8["qkv"])
-            d.o_w8, d.o_s = self._arr(w8["o"]), self._arr(s8["o"])
-            d.gateup_w8, d.gateup_s = self._arr(w8["gateup"]), self._arr(s8["gateup"])
-            d.down_w8, d.down_s = self._arr(w8["down"]), self._arr(s8["down"])
+            self._bind_kinds(d, "_w8", self.llama_w8[0])
+            self._bind_kinds(d, "_s", self.llama_w8[1])
             d.lm_head8, d.lm_head_s = self.lm_head8.data_ptr(), self.lm_head_s.data_ptr()
         if self.llama_w4 is not None:
-            w4, e4 = self.llama_w4
-            d.qkv_w4, d.qkv_e4 = self._arr(w4["qkv"]), self._arr(e4["qkv"])
-            d.o_w4, d.o_e4 = self._arr(w4["o"]), self._arr(e4["o"])
-            d.gateup_w4, d.gateup_e4 = self._arr(w4["gateup"]), self._arr(e4["gateup"])
-            d.down_w4, d.down_e4 = self._arr(w4["down"]), self._arr(e4["down"])
+            self._bind_kinds(d, "_w4", self.llama_w4[0])
+            self._bind_kinds(d, "_e4", self.llama_w4[1])
         d.prefill_w4 = 1 if self.prefill_mxfp4 else 0
         d.prefill_w4a8 = 1 if (self.prefill_mxfp4 and self.prefill_mxfp4_a8) else 0
         d.tune = self.tune.ptr
