@@ -703,13 +703,12 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
         rpm[r] = 0u;
     }
     // chunk index for (iteration, unroll u): c = cb + u*256 + wid*64 + lane
+    // (the w13 image has a loop of its own below: the same map, the same order of the sums)
     auto step = [&](int cb, auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
         uint4 xr[U][XL];
         uint4 w[U][R];
         unsigned sx[U][R];
-        int tl = 0;                                       // w13 image: the thread's chunk of a 256-chunk round (wid * 64 + lane)
-        if constexpr (IsP13<WT>::v) tl = p13_step_lane(tid);
         if constexpr (IsMx<WT>::v) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -729,31 +728,9 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
         for (int u = 0; u < U; ++u) {
             const int c = cb + u * 256 + wid * 64 + lane;
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if constexpr (IsP13<WT>::v)            // (the tail step's chunks past the row: zeros from the range check, no exec masking)
-                    w[u][r] = p13_load<NT, FULL>(prow[r], tl, cb, u * 256);
-                else
-                    w[u][r] = (FULL || c < nchunk) ? ld16<NT>(wrow[r] + (long long)c * CU<WT>::v) : make_uint4(0, 0, 0, 0);
-            }
+            for (int r = 0; r < R; ++r)
+                w[u][r] = (FULL || c < nchunk) ? ld16<NT>(wrow[r] + (long long)c * CU<WT>::v) : make_uint4(0, 0, 0, 0);
         }
-        if constexpr (IsP13<WT>::v) {
-            // the row bases, taken from the entries BEHIND the step's loads: the entries are scalar loads, whose wait (lgkmcnt(0)) the
-            // compiler otherwise places -- one per entry -- in front of the first weight request of a one-to-three-step kernel.  The
-            // empty asm is opaque and ordered against the loads, so the arithmetic on an entry cannot be scheduled above them; three
-            // scalar instructions per row and step.  (No sched_barrier: it also fixes the order of the step's loads -- LO first -- and the
-            // rebuild then starts later than with the small NIB / SGN loads in front: down projection 14.75 -> 14.96 us.)
-            // Nothing but the schedule holds this order and the bits are the same either way, so after a compiler change read it again:
-            //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-kernarg-preload-count=16 --cuda-device-only -S gemv.hip
-            // In gemv_splitk_kernel<bf16, bf16, p13_t, 2, 2, true> the first s_waitcnt lgkmcnt(0) behind the two s_load_dword of the
-            // entries must stand BEHIND the loop's 2 + 12 global_load (profiles/r17_gemv_stream_head.md, section 2).
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                unsigned t = rt[r];
-                asm volatile("" : "+s"(t));
-                rpm[r] = p13_rpm(t);
-            }
-        }
-        rebuild_block<WT, R, U, true>(w, rpm);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if constexpr (IsMx<WT>::v) {
@@ -772,9 +749,87 @@ __global__ __launch_bounds__(GV_THREADS) void gemv_splitk_kernel(const T* __rest
         }
     };
     const int cfull = (nchunk / (256 * U)) * (256 * U);       // steady state: every lane in range, no exec masking
-    int cb = 0;
-    for (; cb < cfull; cb += 256 * U) step(cb, std::true_type{});
-    for (; cb < nchunk; cb += 256 * U) step(cb, std::false_type{});
+    if constexpr (!IsP13<WT>::v) {
+        int cb = 0;
+        for (; cb < cfull; cb += 256 * U) step(cb, std::true_type{});
+        for (; cb < nchunk; cb += 256 * U) step(cb, std::false_type{});
+    } else {
+        // w13 image: the step loop rotated.  A step is its loads (2 x 13 bytes per lane and chunk), then some 23 vector instructions of
+        // rebuild per chunk with nothing of the workgroup in flight -- and the eight workgroups of a CU start together, so they load
+        // together and rebuild together.  Here the raw bytes of step s + 1 are requested BEFORE the first wait of step s: two register
+        // sets, taken in turn by a loop of two steps per turn, so that no set is ever copied (a copy would have to wait for its loads).
+        // The x chunks of step s + 1 are requested behind step s's dot products and in front of step s + 2's weights: vmcnt counts in
+        // order, so a wait for them must not have newer weight loads in front.
+        // Every step -- full or the masked tail -- has ONE form: the whole chunk index goes through the vector offset, the part the
+        // descriptor range-checks, and x comes through a descriptor of its own (K elements), so a chunk past the row is zeros from both
+        // and reads nothing.  That costs three vector instructions per step against the scalar-offset form and buys a loop without a
+        // full / tail choice: behind a join of two paths the wait counts are those of the more careful side -- vmcnt(0) where one side
+        // requested nothing -- and that wait would take the next step's loads with it.  (For the same reason the lane's chunk is not made
+        // opaque per step as p13_step_lane does: an asm with a vector operand at the loop's head draws a vmcnt(0); with the step in the
+        // vector offset there is no loop-invariant sum to hoist.)
+        // Same chunk -> (wave, lane) map, same order of the sums (step after step, u inside a step): every bit is the plain loop's.
+        // tools/gemv_isa.py prints the result: the steady loop shows the next step's 12 loads ahead of the first vmcnt wait.
+        // (A row of one step -- the o projection -- runs the same code, loop not entered.  Keeping the plain step() beside this loop for
+        // such rows measured slower for both: o 5.8 -> 6.15 us, down 13.27 -> 13.44; profiles/r21_splitk_pipe.md, section 3.)
+        constexpr int S = 256 * U;
+        static_assert(XL == 1, "a w13 chunk is one 16-byte x load");
+        const p13_rsrc xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(x), 0, K * (int)sizeof(T), 0x00020000);
+        uint4 xr[U];
+        uint4 wa[U][R], wb[U][R];
+        auto loadx = [&](int cb) {
+            typedef unsigned v4u __attribute__((ext_vector_type(4)));
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const v4u v = __builtin_amdgcn_raw_buffer_load_b128(xsrc, (tid + cb + u * 256) * 16, 0, 0);
+                xr[u] = make_uint4(v.x, v.y, v.z, v.w);
+            }
+        };
+        auto issue = [&](uint4 (&w)[U][R], int cb) {      // tid: the thread's chunk of a 256-chunk round (wid * 64 + lane)
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int r = 0; r < R; ++r) w[u][r] = p13_load<NT, false>(prow[r], tid, cb, u * 256);
+        };
+        auto finish = [&](uint4 (&w)[U][R]) {
+            // the row bases, taken from the entries BEHIND the step's loads: the entries are scalar loads, whose wait (lgkmcnt(0)) the
+            // compiler otherwise places -- one per entry -- in front of the first weight request of a one-to-three-step kernel.  The
+            // empty asm is opaque and ordered against the loads, so the arithmetic on an entry cannot be scheduled above them; three
+            // scalar instructions per row and step.  (No sched_barrier: it also fixes the order of the step's loads -- LO first -- and the
+            // rebuild then starts later than with the small NIB / SGN loads in front: down projection 14.75 -> 14.96 us.)
+            // Nothing but the schedule holds this order and the bits are the same either way, so after a compiler change read it again:
+            //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-kernarg-preload-count=16 --cuda-device-only -S gemv.hip
+            // In gemv_splitk_kernel<bf16, bf16, p13_t, 2, 2, true> the first s_waitcnt lgkmcnt(0) behind the two s_load_dword of the
+            // entries must stand BEHIND the first step's 2 + 12 loads (profiles/r17_gemv_stream_head.md, section 2).
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                unsigned t = rt[r];
+                asm volatile("" : "+s"(t));
+                rpm[r] = p13_rpm(t);
+            }
+            rebuild_block<WT, R, U, true>(w, rpm);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int r = 0; r < R; ++r) acc[r] = dotb<WT>(w[u][r], &xr[u], acc[r]);
+        };
+        // One way into the loop and one way out, and nothing conditional inside: a step past the row is requested like any other (its
+        // range-checked loads are zeros and read nothing) and not summed, so a turn's second half needs no "is there a next step".
+        // (a loop with exits in the middle is rebuilt by the compiler around one shared latch, and the wait counts at its head are then
+        // those of paths that are never taken: vmcnt(0) in front of the next step's loads)
+        loadx(0);
+        issue(wa, 0);
+        int cb = 0;
+        while (cb + S < nchunk) {                         // wa: step cb, in flight; step cb + S exists
+            issue(wb, cb + S);
+            finish(wa);
+            loadx(cb + S);
+            issue(wa, cb + 2 * S);
+            finish(wb);
+            loadx(cb + 2 * S);
+            cb += 2 * S;
+        }
+        if (cb < nchunk) finish(wa);
+    }
     if constexpr (IsP13<WT>::v) {
         // an escaped row (rare; the four waves share their rows, so the whole workgroup takes the branch): its sum is taken again from
         // the raw row in ESC, with the chunk -> (wave, lane) map and the order of the bf16 kernel

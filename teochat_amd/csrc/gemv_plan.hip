@@ -115,7 +115,11 @@ GemvPlan plan_gemv(const GemvProblem& p, const teo_tune& t) {
         // projection) takes U = 1 -- with U = 2 half of the step's instructions are masked (5.39 -> 4.95 us alone, 5.24 -> 4.72 in
         // the step); 4 rows per workgroup are within noise alone and lose in the step (fp8 down 9.94 -> 10.53 us).  The chunk ->
         // (wave, lane) map and every lane's order of accumulation do not depend on R or U: all forms give the same bits (tested)
-        // (w13 image: the rebuild holds more registers per chunk in flight -- down projection, U = 6: 151 VGPRs, 16.9 us; U = 2: 15.0 us)
+        // (w13 image: the rebuild holds more registers per chunk in flight -- down projection, U = 6: 151 VGPRs, 16.9 us; U = 2: 15.0 us.
+        // Those are round 12's figures.  Since round 21 the image kernel holds TWO steps' raw bytes (gemv.hip, the rotated loop), so a
+        // larger U costs twice the registers: U = 2 59 VGPRs, 13.25 us; U = 3 82, 15.7 us; U = 6 187, 15.9 us -- before the rotation
+        // U = 3 was 58 VGPRs, 13.7 us and U = 6 95, 13.4 us.  The knob forms stay bit-identical and are not a tuning option for the image
+        // any more: profiles/r21_splitk_pipe.md)
         const bool p13 = p.wfmt == GV_W_P13;
         const int u = t.gemv_splitk_u > 0 ? t.gemv_splitk_u
                       : (nchunk <= 256 ? 1 : ((nchunk <= 512 || p13) ? 2 : (nchunk <= 1024 ? 4 : (nchunk <= 1536 ? 6 : 2))));
