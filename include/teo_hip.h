@@ -205,7 +205,10 @@ int teo_gemm_ws(const void* d_A, const void* d_W, const void* d_bias, const void
  * weight path on CDNA4 MFMA" for the prefill phase):
  *     C[m, n] = a_scale[m] * w_scale[n] * sum_k A8[m, k] * W8[n, k]  (+ residual[m, n]);  TEO_GEMM_SWIGLU16 as in teo_gemm.
  * A8 [M, lda] and W8 [N, K] hold OCP e4m3 bytes, a_scale [M] / w_scale [N] fp32; C / residual bf16 (or C fp32).  K % 128 == 0,
- * lda % 16 == 0, N % 4 == 0; TEO_ERR_UNSUPPORTED otherwise.  Same Linear layers as teo_gemm (tf LlamaAttention / LlamaMLP,
+ * lda % 16 == 0, N % 4 == 0; TEO_ERR_UNSUPPORTED otherwise.  Rounding: every product is exact; the sum over k is the instruction's --
+ * its 128-term internal sum is not an fp32 chain (up to 1.1e-5 of sum |a||w|) --, the scales and the residual are applied to it
+ * in fp32, and a bf16 C is that fp32 value rounded once, to nearest even (tests/test_half_ulp_gpu.py holds the bf16 output to half an ulp
+ * of the fp32 output form + residual; teo_gemm_w4a8 likewise).  Same Linear layers as teo_gemm (tf LlamaAttention / LlamaMLP,
  * reached from llava_llama.py:88-99) under a weight + activation quantisation the reference does not have (its 8-bit option is
  * bitsandbytes, eval.py:52-53): selectable, never the default.
  * teo_quant_rows_fp8: per-row (per-token) quantiser  q[m, :] = e4m3(f(x[m, :]) / s[m]),  s[m] = max|f(x[m, :])| / 448, with
