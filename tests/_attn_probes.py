@@ -11,8 +11,13 @@ kernel looked at (the one-hot idea of tests/test_mxfp4_a8_gpu.py, for key visibi
                dense  -- V[j, (j // div) % d] = 1: every key counts somewhere;
                window -- up to d chosen keys get a one-hot column each, all other V rows are 0: for any length.
 
+  mass       : q_i = a_i * sigma, k_j = ((t_j, C) / (d / 2)) * sigma on the two halves of the head, scale 1: score(i, j) = a_i * (t_j + C)
+               exactly in fp32 in any order of summation; V is a 0 / 1 class indicator.  out[i, c] = the softmax MASS of class c, held
+               to a bound derived from the number formats (mass_bound); the weights differ from key to key, which neither probe above
+               exercises.  Planted arithmetic faults (scale, log2(e), truncated P, a skipped rescale): flash_emulation, split_emulation.
+
 Everything here is torch on the CPU in fp32 holding values exact in the target dtype; expectations come from the boolean visibility
-mask alone (fp64 counts), never from a kernel."""
+mask alone (fp64 counts, fp64 softmax for the mass probe), never from a kernel."""
 import torch
 
 from tests._gpu import ulps_off          # exact ulps of a 16-bit format (plain torch; nothing there touches the GPU on import)
@@ -172,3 +177,202 @@ def plant_fault(vis, kind):
 
 
 FAULTS = ("diagonal_masked", "future_key_visible", "tile_first_key_masked", "chunk_last_key_masked", "ragged_tail_masked")
+
+
+# ---------------------------------------------------------------------------------------------- weight mass
+# Are the softmax weights right when they DIFFER from key to key?  Inputs exact in the kernel's type, scores exact in fp32 whatever the
+# order of summation, V a class indicator: the output is the softmax mass of a class of keys, and everything a correct kernel may add
+# to it is one rounding of P, one rounding of the output and a few fp32 roundings (mass_bound).
+MASS_MAGS = (0.25, 0.5, 0.75, 1.0)
+MASS_PROFILES = ("ramp", "saw", "spike")
+MASS_OFFSETS = {torch.bfloat16: (0.0, 512.0, -512.0), torch.float32: (0.0, 512.0, -512.0), torch.float16: (0.0, 64.0, -64.0)}
+MASS_U_P = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11, torch.float32: 0.0}        # the one rounding of P before the PV product
+MASS_TINY_P = {torch.bfloat16: 0.0, torch.float16: 2.0 ** -25, torch.float32: 0.0}            # half of fp16's smallest subnormal, per key
+MASS_SLACK_SHARE = 0.15           # 16-bit types: the fp32 slack may be at most this share of u_P * W, or the input is refused
+LOG2E = 1.4426950408889634
+
+
+def mass_sigma(d):
+    """A fixed vector of +-1 over the head dimension."""
+    e = torch.arange(d)
+    return torch.where(((e * 7) % 5) < 2, -1.0, 1.0)
+
+
+def mass_a(n, shift=0):
+    """[n] query amplitudes a_i from +-{0.25, 0.5, 0.75, 1}: the sign changes from one index to the next (an ascending and a descending
+    score profile in neighbouring rows of a wave), the magnitude every second index.  `shift` moves the pattern (heads, conversations)."""
+    i = torch.arange(n) + shift
+    mag = torch.tensor(MASS_MAGS)[(i // 2) % 4]
+    return torch.where(i % 2 == 0, mag, -mag)
+
+
+def mass_levels(profile, kv_len):
+    """[kv_len] key levels t_j, multiples of 0.25 with at most 8 significant bits (exact in bf16 after the division by d / 2).
+    ramp : the running maximum moves in every tile or chunk for a > 0 and never for a < 0;  saw : period 101, aligned to no tile or
+    chunk;  spike : one key at 64.0 three quarters of the way through the context -- a late jump of the maximum by more than 60."""
+    j = torch.arange(kv_len)
+    if profile == "ramp":
+        return ((j * 200) // kv_len).float() * 0.25
+    if profile == "saw":
+        return ((j * 37) % 101).float() * 0.25
+    if profile == "spike":
+        t = ((j * 37) % 17).float() * 0.25
+        t[(3 * kv_len) // 4] = 64.0
+        return t
+    raise ValueError(profile)
+
+
+def mass_qk(a, t, C, d, dt):
+    """a [..., Sq], t [Sk] -> q [..., Sq, d] = a sigma, k [Sk, d] = (t | C) / (d / 2) * sigma (fp32, exact in dt).  Every product of one
+    half is the same number and d / 2 is a power of two, so q_i . k_j = a_i (t_j + C) in fp32 for every order of summation: checked."""
+    half = d // 2
+    assert half >= 1 and half & (half - 1) == 0, "d / 2 must be a power of two"
+    sg = mass_sigma(d)
+    q = a.unsqueeze(-1) * sg
+    k = torch.cat([(t / half).view(-1, 1).expand(-1, half), torch.full((t.shape[0], half), C / half)], dim=1) * sg
+    assert_exact(q, dt), assert_exact(k, dt)
+    au = torch.unique(a)                               # a row of q is its amplitude times sigma: one row per distinct amplitude says it all
+    want = au.double().view(-1, 1) * (t.double() + C).view(1, -1)
+    for order in (torch.arange(d), torch.arange(d - 1, -1, -1), torch.arange(d).view(2, half).t().reshape(-1)):
+        s = torch.zeros(want.shape)
+        for e in order.tolist():                       # one fp32 addition per element, in three different orders
+            s = s + (au * sg[e]).view(-1, 1) * k[:, e].view(1, -1)
+        assert torch.equal(s.double(), want), "the scores are not exact in fp32"
+    return q, k
+
+
+def mass_v(kv_len, d, div):
+    """[kv_len, d] with V[j, (j // div) % d] = 1: dense_v without its count limit (mass_bound is relative to the mass)."""
+    j = torch.arange(kv_len)
+    v = torch.zeros(kv_len, d)
+    v[j, (j // div) % d] = 1.0
+    return v
+
+
+def mass_weights(a, t, vis):
+    """fp64 softmax over the visible keys of a_i * t_j: [..., Sq, Sk].  (The offset C shifts a whole row and drops out.)"""
+    s = a.double().unsqueeze(-1) * t.double()
+    s = s.masked_fill(~vis, float("-inf"))
+    assert vis.any(dim=-1).all(), "a row without a visible key has no softmax"
+    return torch.softmax(s, dim=-1)
+
+
+def mass_ref32(q, k, v, vis):
+    """The same formula on the CPU in fp32 (two passes, global maximum, no rounding of P): the yardstick of the fp32 slack."""
+    s = (q @ k.t()).masked_fill(~vis, float("-inf"))
+    p = torch.exp(s - s.max(dim=-1, keepdim=True).values)
+    return (p @ v) / p.sum(dim=-1, keepdim=True)
+
+
+def ulp_of(w, dt):
+    """Spacing of dt at |w| (fp64 in, fp64 out): 2^(e - mant_bits) for w in [2^(e-1), 2^e), floored at the smallest subnormal."""
+    mant, lowest = {torch.bfloat16: (8, -133), torch.float16: (11, -24)}[dt]
+    _, e = torch.frexp(w.abs().clamp_min(2.0 ** -140))
+    return torch.ldexp(torch.ones_like(w), (e - mant).clamp_min(lowest))
+
+
+def mass_bound(W, n_c, smax, rho, dt):
+    """Per output element, W the exact class mass [..., Sq, d], n_c [Sq, d] the visible keys of the class, smax [..., Sq] = max_j |s_ij|
+    over the visible keys (natural units), rho [..., Sq] the largest relative error of mass_ref32 over the row's nonzero columns:
+
+        |got - W| <= u_P W + tiny_P n_c + ulp_T(W) / 2 + slack,   slack = 2^-24 (16 + 4 log2(e) smax) W + 4 rho W
+
+    u_P W: P is rounded once to the storage type before the PV product (l comes from the unrounded P: nothing else of that order);
+    tiny_P n_c: a P below fp16's normal range loses at most half of the smallest subnormal, relative to a maximum no larger than the
+    final one; ulp_T / 2: the one rounding of the output; slack: rounding the scaled score, subtracting the maximum, exp / exp2, alpha
+    and 1 / l (first term) and the fp32 sums (second term, margin 4 as _halfulp.dot_slack).  fp32: u_P = tiny_P = 0, ulp_T = 2^-24 W.
+    16-bit types: slack <= 0.15 u_P W on every element, or the input is refused.  Nothing here is measured on a kernel."""
+    W = W.double()
+    slack = (2.0 ** -24 * (16.0 + 4.0 * LOG2E * smax.double()) + 4.0 * rho.double()).unsqueeze(-1) * W
+    if dt == torch.float32:
+        return 2.0 ** -25 * W + slack
+    u_p = MASS_U_P[dt]
+    share = float((slack / (u_p * W).clamp_min(1e-300)).max())
+    assert share <= MASS_SLACK_SHARE, f"fp32 slack is {share:.3f} of u_P * W (> {MASS_SLACK_SHARE}): the bound would not discriminate"
+    bound = u_p * W + MASS_TINY_P[dt] * n_c.double() + ulp_of(W, dt) / 2 + slack
+    return torch.where(W > 0, bound, torch.zeros_like(bound))           # no visible key in the column: exactly 0
+
+
+def mass_case(a, t, C, vis, v, dt):
+    """Everything a comparison needs for ONE K (profile t, offset C) and one V: (q, k, W, bound).  a [..., Sq], vis [Sq, Sk], v [Sk, d]."""
+    d = v.shape[1]
+    q, k = mass_qk(a, t, C, d, dt)
+    W = mass_weights(a, t, vis) @ v.double()
+    ref32 = mass_ref32(q, k, v, vis).double()
+    nz = W > 0
+    assert torch.equal(ref32 == 0, ~nz), "a column without a visible key must be exactly 0"
+    rho = torch.where(nz, (ref32 - W).abs() / W.clamp_min(1e-300), torch.zeros_like(W)).max(dim=-1).values
+    smax = (a.double().unsqueeze(-1) * (t.double() + C)).abs().masked_fill(~vis, 0.0).max(dim=-1).values
+    return q, k, W, mass_bound(W, vis.double() @ v.double(), smax, rho, dt)
+
+
+def mass_ratio(got, W, bound):
+    """(worst |got - W| / bound, share of the elements beyond it).  Where the bound is 0 (no visible key in the column) the output must be
+    exactly 0: anything else counts as infinitely far."""
+    err = (got.detach().cpu().double() - W).abs()
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err == 0, 0.0, float("inf")).double())
+    ratio = torch.where(torch.isnan(ratio), torch.full_like(ratio, float("inf")), ratio)
+    return float(ratio.max()), float((ratio > 1.0).double().mean())
+
+
+# ---- the kernels' arithmetic on the CPU, with switchable faults (host test: the probe's power; nothing here is a kernel)
+ARITH_FAULTS = ("scale_1pct", "log2e_1.44", "truncate_p", "skip_alpha", "wrong_chunk_max")
+
+
+def round_to(x, dt, truncate=False):
+    """fp32 -> dt -> fp32, to nearest or (the planted fault) towards zero."""
+    if dt == torch.float32:
+        return x
+    r = x.to(dt)
+    if truncate:
+        over = r.float().abs() > x.abs()
+        r = (r.view(torch.int16) - over.to(torch.int16)).view(dt)       # sign-magnitude: one step towards zero
+    return r.float()
+
+
+def flash_emulation(q, k, v, vis, scale, dt, fault=None, tile=64, fault_tile=1):
+    """The tile loop of csrc/flash.hip in fp32: sl2 = scale * log2(e), running maximum, alpha, P rounded to dt for the PV product, l from
+    the unrounded P, one rounding of the output.  q [R, d], k / v [Sk, .], vis [R, Sk] -> [R, dv] (fp32 holding dt values).
+    Faults: the softmax scale 1 % too large; log2(e) held as 1.44; P truncated; tile `fault_tile`'s alpha not applied to O."""
+    assert fault in (None,) + ARITH_FAULTS[:4]
+    f32 = torch.float32
+    sl2 = torch.tensor(scale, dtype=f32) * torch.tensor({"scale_1pct": 1.01 * LOG2E, "log2e_1.44": 1.44}.get(fault, LOG2E), dtype=f32)
+    R, Sk = vis.shape
+    m = torch.full((R, 1), float("-inf"))
+    l = torch.zeros(R, 1)
+    acc = torch.zeros(R, v.shape[1])
+    for ti, j0 in enumerate(range(0, Sk, tile)):
+        s = ((q @ k[j0:j0 + tile].t()) * sl2).masked_fill(~vis[:, j0:j0 + tile], float("-inf"))
+        m_new = torch.maximum(m, s.max(dim=1, keepdim=True).values)
+        m_use = torch.where(torch.isinf(m_new), torch.zeros_like(m_new), m_new)
+        alpha = torch.exp2(m - m_use)
+        p = torch.exp2(s - m_use)
+        l = l * alpha + p.sum(dim=1, keepdim=True)
+        if not (fault == "skip_alpha" and ti == fault_tile):
+            acc = acc * alpha
+        acc = acc + round_to(p, dt, truncate=fault == "truncate_p") @ v[j0:j0 + tile]
+        m = m_new
+    return round_to(acc * (1.0 / l), dt)
+
+
+def split_emulation(q, k, v, scale, dt, chunk, fault=None, fault_chunk=1):
+    """The decode kernels in fp32: per chunk of `chunk` keys exp relative to the CHUNK maximum, P rounded to dt, l from the unrounded P;
+    records (m, l, o) merged as attn_merge_records does (w = exp(m - M), sum o w / sum l w).  q [R, d], k / v [n, .]: every row sees every
+    key.  Faults: scale, log2(e) and truncation as above; chunk `fault_chunk`'s weight taken against its neighbour's maximum."""
+    assert fault in (None,) + ARITH_FAULTS[:3] + ARITH_FAULTS[4:]
+    n, R = k.shape[0], q.shape[0]
+    nc = -(-n // chunk)
+    s = (q @ k.t()) * torch.tensor(scale * (1.01 if fault == "scale_1pct" else 1.0), dtype=torch.float32)
+    s = torch.cat([s, torch.full((R, nc * chunk - n), float("-inf"))], dim=1).view(R, nc, chunk)
+    vp = torch.cat([v, torch.zeros(nc * chunk - n, v.shape[1])]).view(nc, chunk, -1)
+    mc = s.max(dim=2, keepdim=True).values
+    p = torch.exp2((s - mc) * torch.tensor(1.44, dtype=torch.float32)) if fault == "log2e_1.44" else torch.exp(s - mc)
+    lc = p.sum(dim=2)
+    oc = torch.einsum("rcj,cjd->rcd", round_to(p, dt, truncate=fault == "truncate_p"), vp)
+    mc = mc.squeeze(2)
+    M = mc.max(dim=1, keepdim=True).values
+    if fault == "wrong_chunk_max" and nc > fault_chunk:
+        mc = mc.clone()
+        mc[:, fault_chunk] = mc[:, fault_chunk - 1]
+    w = torch.exp(mc - M)
+    return round_to((oc * w.unsqueeze(2)).sum(dim=1) * (1.0 / (lc * w).sum(dim=1, keepdim=True)), dt)

@@ -1,6 +1,8 @@
 """The exact-data attention probes of tests/_attn_probes.py on the CPU oracle (no GPU): (a) every arithmetic mode of
 oracle.attention_core reproduces them as stated, (b) a fault planted in the visibility mask makes them fail -- the proof that
-tests/test_attention_exact_gpu.py has power --, (c) the Gaussian comparison the suite had before does not notice such a fault."""
+tests/test_attention_exact_gpu.py has power --, (c) the Gaussian comparison the suite had before does not notice such a fault,
+(d) the weight-mass probe of tests/test_attention_mass_gpu.py: CPU emulations of the kernels' arithmetic stay inside its derived bound,
+planted arithmetic faults leave it, and the Gaussian comparison passes three of them."""
 import pytest
 import torch
 
@@ -176,3 +178,123 @@ def test_gaussian_comparison_at_2299_keys_does_not_notice_a_dropped_key():
     assert not torch.equal(full, dropped)
     tol = 2.0 * (2.0 ** -7) * full.abs() + 4e-3
     assert ((dropped - full).abs() <= tol).all()
+
+
+# ---------------------------------------------------------------------------------------------- (d) the weight-mass probe
+# The inputs of tests/test_attention_mass_gpu.py through CPU emulations of the kernels' arithmetic (P.flash_emulation: the 64-key tile
+# loop of csrc/flash.hip; P.split_emulation: the decode chunks and attn_merge_records): the fault-free emulations stay inside the derived
+# bound on every case the GPU test runs (this is also where the slack condition of P.mass_bound is checked for every input), every
+# planted arithmetic fault leaves it, and the Gaussian comparison of tests/test_kernels_gpu.py passes three of those faults.
+BF, F16, F32 = torch.bfloat16, torch.float16, torch.float32
+MASS_PREFILL = [(130, 130, True), (100, 420, True), (333, 901, True), (257, 257, False)]
+MASS_BRANCH_PASTS = (5, 130)
+MASS_CTX = [1, 33, 64, 65, 129, 257, 513, 640]
+MASS_FORMS = [(BF, 64), (BF, 128), (F16, 64), (F16, 128), (F32, 16), (F32, 64)]
+
+
+def _mass_vis(shape):
+    if len(shape) == 1:                              # ("branches", past): the branch mask of tests/test_score_gpu.py
+        from tests.test_score_host import LENS, vis_of
+        return vis_of(shape[0], LENS)
+    return P.visible_mask(*shape)
+
+
+def _mass_prefill(dt, d, vis, profile, C, fault, heads=2):
+    """{div: (worst ratio, share beyond)} of the flash emulation on one K: `heads` amplitude patterns, V of both divs side by side"""
+    Sq, Sk = vis.shape
+    a = torch.stack([P.mass_a(Sq, h) for h in range(heads)])
+    t = P.mass_levels(profile, Sk)
+    cases = {div: P.mass_case(a, t, C, vis, P.mass_v(Sk, d, div), dt) for div in (1, 64)}
+    q, k = cases[1][:2]
+    v2 = torch.cat([P.mass_v(Sk, d, 1), P.mass_v(Sk, d, 64)], dim=1)
+    out = P.flash_emulation(q.reshape(-1, d), k, v2, vis.repeat(heads, 1), 1.0, dt, fault).view(heads, Sq, 2 * d)
+    return {div: P.mass_ratio(out[..., i * d:(i + 1) * d], W, bound) for i, (div, (_, _, W, bound)) in enumerate(cases.items())}
+
+
+def _mass_decode(dt, d, chunk, n, b, profile, C, fault, heads=8):
+    a = P.mass_a(heads, 9 * b).view(heads, 1)        # one query row per head; the sign changes from head to head and conversation to conversation
+    t = P.mass_levels(profile, n)
+    vis = torch.ones(1, n, dtype=torch.bool)
+    res = {}
+    for div in (1, chunk):
+        q, k, W, bound = P.mass_case(a, t, C, vis, P.mass_v(n, d, div), dt)
+        out = P.split_emulation(q.view(heads, d), k, P.mass_v(n, d, div), 1.0, dt, chunk, fault)
+        res[div] = P.mass_ratio(out.view(heads, 1, d), W, bound)
+    return res
+
+
+@pytest.mark.parametrize("dt,d", MASS_FORMS, ids=lambda x: str(x).replace("torch.", ""))
+def test_mass_fault_free_emulations_stay_inside_the_bound(dt, d):
+    worst = 0.0
+    for shape in MASS_PREFILL + [(past,) for past in MASS_BRANCH_PASTS]:
+        vis = _mass_vis(shape)
+        for profile in P.MASS_PROFILES:
+            for C in P.MASS_OFFSETS[dt]:
+                for div, (ratio, share) in _mass_prefill(dt, d, vis, profile, C, None).items():
+                    assert ratio <= 1.0 and share == 0.0, ("flash", shape, profile, C, div, ratio)
+                    worst = max(worst, ratio)
+    print(f"flash emulation {dt} d = {d}: worst |got - W| / bound {worst:.3f}")
+    worst = 0.0
+    for chunk in (32, 64, 128, 256):
+        for b, n in enumerate(MASS_CTX):
+            for profile in P.MASS_PROFILES:
+                for C in P.MASS_OFFSETS[dt]:
+                    for div, (ratio, share) in _mass_decode(dt, d, chunk, n, b, profile, C, None).items():
+                        assert ratio <= 1.0 and share == 0.0, ("split", chunk, n, profile, C, div, ratio)
+                        worst = max(worst, ratio)
+    print(f"split emulation {dt} d = {d}: worst |got - W| / bound {worst:.3f}")
+
+
+def test_mass_inputs_with_too_much_fp32_slack_are_refused():
+    """fp16 at the bf16 offset: 4 log2(e) * 562 fp32 ulps are 0.4 of u_P = 2^-11 -- the bound would stop discriminating"""
+    vis = P.visible_mask(130, 130, True)
+    with pytest.raises(AssertionError, match="would not discriminate"):
+        P.mass_case(P.mass_a(130), P.mass_levels("ramp", 130), 512.0, vis, P.mass_v(130, 64, 1), F16)
+    with pytest.raises(AssertionError, match="not exact"):                       # a level of 9 significant bits is not a bf16 number
+        P.mass_qk(P.mass_a(4), torch.tensor([0.25 * 257]), 0.0, 64, BF)
+
+
+def _mass_power(kind, dt, d, fault):
+    """largest share of elements beyond the bound per profile, over the offsets and class widths"""
+    best = {}
+    for profile in P.MASS_PROFILES:
+        shares = []
+        for C in P.MASS_OFFSETS[dt]:
+            if kind == "flash":
+                for Sq, Sk, causal in ((130, 130, True), (333, 901, True)):
+                    shares += [s for _, s in _mass_prefill(dt, d, P.visible_mask(Sq, Sk, causal), profile, C, fault).values()]
+            else:
+                for b, n in enumerate(MASS_CTX):
+                    if n > 128:                      # more than one chunk of 128 keys
+                        shares += [s for _, s in _mass_decode(dt, d, 128, n, b, profile, C, fault).values()]
+        best[profile] = max(shares)
+    return best
+
+
+@pytest.mark.parametrize("dt", [BF, F16], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("kind,fault", [("flash", f) for f in P.ARITH_FAULTS[:4]] + [("split", f) for f in P.ARITH_FAULTS[:3] + P.ARITH_FAULTS[4:]])
+def test_planted_arithmetic_fault_leaves_the_mass_bound(kind, fault, dt):
+    best = _mass_power(kind, dt, 128, fault)
+    print(f"{kind} emulation, {fault}, {dt}: largest share of elements beyond the bound per profile: "
+          + ", ".join(f"{p} {100 * s:.1f} %" for p, s in best.items()))
+    assert max(best.values()) >= 0.01, (kind, fault, best)
+
+
+@pytest.mark.parametrize("fault", P.ARITH_FAULTS[:3])
+@pytest.mark.parametrize("Sq,Sk", [(300, 300), (100, 420)])
+def test_gaussian_comparison_does_not_notice_the_arithmetic_fault(Sq, Sk, fault):
+    """The bar of test_attention_mfma_bf16 (atol = rtol = 1.5e-2 against the fp64 softmax) on its own kind of data -- N(0, 1), d = 128,
+    bf16, scale d^-0.5, causal: the flash emulation with the softmax scale 1 % off, with log2(e) = 1.44 or with a truncated P passes
+    it.  (A statement about the comparison; nothing here runs a kernel.)"""
+    d = 128
+    g = torch.Generator().manual_seed(1)
+    q, k, v = (torch.randn(n, d, generator=g).to(BF).float() for n in (Sq, Sk, Sk))
+    vis = P.visible_mask(Sq, Sk, True)
+    s = (q.double() @ k.double().t() * d ** -0.5).masked_fill(~vis, float("-inf"))
+    ref = (torch.softmax(s, dim=1) @ v.double()).float()
+    good = P.flash_emulation(q, k, v, vis, d ** -0.5, BF)
+    bad = P.flash_emulation(q, k, v, vis, d ** -0.5, BF, fault)
+    assert not torch.equal(bad, good)
+    torch.testing.assert_close(bad, ref, atol=1.5e-2, rtol=1.5e-2)
+    with pytest.raises(AssertionError):                                          # the fourth it does notice: a tile whose alpha is not applied
+        torch.testing.assert_close(P.flash_emulation(q, k, v, vis, d ** -0.5, BF, "skip_alpha"), ref, atol=1.5e-2, rtol=1.5e-2)
