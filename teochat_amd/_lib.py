@@ -287,6 +287,33 @@ _SIGS_SHARE = {
                                                               C.POINTER(Guide), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
 }
 EXPORTS_SHARE = tuple(_SIGS_SHARE.keys())
+
+
+# include/teo_hip_logprob.h: token log-probabilities recorded behind the decode steps, a sixth header of the same library
+class LogprobRec(C.Structure):
+    _fields_ = [("d_logprobs", C.c_void_p), ("stride", C.c_int), ("d_rec_count", C.c_void_p), ("top_k", C.c_int), ("d_top_ids", C.c_void_p),
+                ("d_top_logprobs", C.c_void_p)]
+
+
+LOGPROB_MAX_TOP = 8
+_SIGS_LOGPROB = {
+    "teo_logprob_rec_sizeof": (C.c_size_t, []),
+    "teo_logprob_rows": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "teo_logprob_record": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(LogprobRec), C.c_void_p]),
+    "teo_llama_decode_step_logp": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeState), C.POINTER(Guide), C.POINTER(LogprobRec), C.c_void_p,
+                                             C.c_size_t, C.c_void_p]),
+    "teo_llama_decode_graph_create_logp": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeState), C.POINTER(Guide), C.POINTER(LogprobRec),
+                                                     C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "teo_llama_decode_batch_step_logp": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeBatchState), C.POINTER(LogprobRec), C.c_void_p,
+                                                   C.c_size_t, C.c_void_p]),
+    "teo_llama_decode_batch_graph_create_logp": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeBatchState), C.POINTER(LogprobRec), C.c_void_p,
+                                                           C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "teo_llama_decode_stream_step_logp": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeStreamState), C.POINTER(Share), C.POINTER(Guide),
+                                                    C.POINTER(LogprobRec), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "teo_llama_decode_stream_graph_create_logp": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeStreamState), C.POINTER(Share), C.POINTER(Guide),
+                                                            C.POINTER(LogprobRec), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+}
+EXPORTS_LOGPROB = tuple(_SIGS_LOGPROB.keys())
 _lib = None
 
 
@@ -308,7 +335,7 @@ def load():
     except OSError as e:
         raise TeoLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_PREFIX.items()) + list(_SIGS_SCORE.items()) + list(_SIGS_GUIDE.items()) \
-            + list(_SIGS_SHARE.items()):
+            + list(_SIGS_SHARE.items()) + list(_SIGS_LOGPROB.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -328,6 +355,9 @@ def load():
         raise TeoLibraryError(f"struct layout mismatch: teo_guide is {lib.teo_guide_sizeof()} bytes in {LIB_PATH}, {C.sizeof(Guide)} in this binding; rebuild")
     if lib.teo_share_sizeof() != C.sizeof(Share):
         raise TeoLibraryError(f"struct layout mismatch: teo_share is {lib.teo_share_sizeof()} bytes in {LIB_PATH}, {C.sizeof(Share)} in this binding; rebuild")
+    if lib.teo_logprob_rec_sizeof() != C.sizeof(LogprobRec):
+        raise TeoLibraryError(f"struct layout mismatch: teo_logprob_rec is {lib.teo_logprob_rec_sizeof()} bytes in {LIB_PATH}, "
+                              f"{C.sizeof(LogprobRec)} in this binding; rebuild")
     _lib = lib
     return lib
 

@@ -16,12 +16,12 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .decode_host import (LINEAR_KINDS, SEED_MASK, PtrArrays, StepGraphs, _p, alloc_loop_state, arm_sampler, prefill_append, profile_steps, run_prefill,
-                          sync_desc_options)
+from .decode_host import (LINEAR_KINDS, SEED_MASK, LogprobRecorder, PtrArrays, StepGraphs, _p, alloc_loop_state, arm_sampler, logprob_graph_key,
+                          prefill_append, profile_steps, run_prefill, sync_desc_options)
 from .engine import dequantize_mxfp4_blocks, reinterleave_gate_up, tile_weights, tile_weights_mxfp4
 
 
-class BatchDecoder(StepGraphs, PtrArrays):
+class BatchDecoder(StepGraphs, PtrArrays, LogprobRecorder):
     def __init__(self, engine, batch, max_new=1024, tiled=True):
         if not 1 <= batch <= L.MAX_DECODE_BATCH:
             raise ValueError(f"batch {batch} outside 1..{L.MAX_DECODE_BATCH}")
@@ -183,6 +183,7 @@ class BatchDecoder(StepGraphs, PtrArrays):
             self.d_token.copy_(torch.tensor([int(t) for t in first_tokens], dtype=torch.int64))
             self.d_pos.copy_(torch.tensor(self.cache_len, dtype=torch.int32))
             self.d_count.zero_()
+            self.rec_sync()                       # (the recorder's count follows d_count wherever the host writes it)
             self.d_stop.zero_()
             seeds = list(seeds) if seeds is not None else [0] * self.B
             self.d_rng.copy_(torch.tensor([[int(sd) & SEED_MASK, int(draws_done)] for sd in seeds], dtype=torch.int64))
@@ -204,10 +205,20 @@ class BatchDecoder(StepGraphs, PtrArrays):
         ws = self._workspace()
         d, s_ = C.byref(self.desc), C.byref(self.state)
         with eng.phase() as st:
-            self.replay_or_step(eng.stream, ws.data_ptr(), n, use_graph,
-                                lambda out: L.check(self.lib.teo_llama_decode_batch_graph_create(d, s_, _p(ws), ws.numel(), st, out),
-                                                    "teo_llama_decode_batch_graph_create"),
-                                lambda: L.check(self.lib.teo_llama_decode_batch_step(d, s_, _p(ws), ws.numel(), st), "teo_llama_decode_batch_step"))
+            if self._rec is not None:
+                # the step with the recorder behind it (include/teo_hip_logprob.h), a graph of its own
+                r_ = C.byref(self._rec)
+                self.replay_or_step(eng.stream, logprob_graph_key(self._rec, ws.data_ptr()), n, use_graph,
+                                    lambda out: L.check(self.lib.teo_llama_decode_batch_graph_create_logp(d, s_, r_, _p(ws), ws.numel(), st, out),
+                                                        "teo_llama_decode_batch_graph_create_logp"),
+                                    lambda: L.check(self.lib.teo_llama_decode_batch_step_logp(d, s_, r_, _p(ws), ws.numel(), st),
+                                                    "teo_llama_decode_batch_step_logp"), slot=self.LOGP_SLOT)
+            else:
+                self.replay_or_step(eng.stream, ws.data_ptr(), n, use_graph,
+                                    lambda out: L.check(self.lib.teo_llama_decode_batch_graph_create(d, s_, _p(ws), ws.numel(), st, out),
+                                                        "teo_llama_decode_batch_graph_create"),
+                                    lambda: L.check(self.lib.teo_llama_decode_batch_step(d, s_, _p(ws), ws.numel(), st),
+                                                    "teo_llama_decode_batch_step"))
         self.cache_len = [x + n for x in self.cache_len]
         self._steps_done += n
 

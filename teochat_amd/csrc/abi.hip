@@ -851,4 +851,6 @@ int teo_gemm_skinny_w4(const void* x, const void* W4, const void* e8m0, const vo
 namespace teo {
 // the stream step's argument checks for the guided entry points (guide.hip)
 int stream_state_check(const teo_llama_desc* d, const teo_decode_stream_state* st) { return check_stream_state(d, st); }
+// the batched step's, for the entry point with the log-probability recorder (logprob.hip)
+int batch_state_check(const teo_llama_desc* d, const teo_decode_batch_state* st) { return check_batch_state(d, st); }
 }  // namespace teo

@@ -7,6 +7,7 @@
 #include "runtime.h"
 #include "guide_dev.h"
 #include "share_dev.h"
+#include "logprob_dev.h"
 
 namespace teo {
 struct Carver {
@@ -882,6 +883,31 @@ int decode_stream_graph_create(const teo_llama_desc* d, const teo_decode_stream_
 int decode_stream_graph_create(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
                                teo_graph** out, const teo_guide* g, const teo_share* sh) {
     return capture_graph(st, [&]() { return llama_decode_stream_step(d, s, ws, ws_bytes, st, g, sh); }, out);
+}
+
+// include/teo_hip_logprob.h: the step's launches, then the recorder over the state the tail left (one more kernel node per replay)
+int decode_graph_create_logp(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st, teo_graph** out,
+                             const teo_guide* g, const teo_logprob_rec* rec) {
+    return capture_graph(st, [&]() {
+        TEO_TRY(llama_decode_step(d, s, ws, ws_bytes, st, g));
+        return logprob_record(s->d_logits, d->vocab, 1, d->vocab, s->d_out_tokens, 1, s->d_out_count, rec, st);
+    }, out);
+}
+
+int decode_batch_graph_create_logp(const teo_llama_desc* d, const teo_decode_batch_state* s, void* ws, size_t ws_bytes, hipStream_t st,
+                                   teo_graph** out, const teo_logprob_rec* rec) {
+    return capture_graph(st, [&]() {
+        TEO_TRY(llama_decode_batch_step(d, s, ws, ws_bytes, st));
+        return logprob_record(s->d_logits, d->vocab, s->batch, d->vocab, s->d_out_tokens, s->out_stride, s->d_out_count, rec, st);
+    }, out);
+}
+
+int decode_stream_graph_create_logp(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
+                                    teo_graph** out, const teo_guide* g, const teo_share* sh, const teo_logprob_rec* rec) {
+    return capture_graph(st, [&]() {
+        TEO_TRY(llama_decode_stream_step(d, s, ws, ws_bytes, st, g, sh));
+        return logprob_record(s->d_logits, d->vocab, s->batch, d->vocab, s->d_out_tokens, s->out_stride, s->d_out_count, rec, st);
+    }, out);
 }
 
 int llama_verify_step_profile(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, float* ms_out, int* count_out,

@@ -8,6 +8,8 @@ calls.  Each rule that is easy to copy wrongly is stated here and nowhere else:
                      replays, _drop_graph and the one __del__
   profile_steps      the per-class accumulator of the profiled steps
   alloc_loop_state   the eight device tensors of a decode loop and the state fields that point at them
+  LogprobRecorder    mixin: the recorder's tensors beside alloc_loop_state's (include/teo_hip_logprob.h), allocated at first use, and the
+                     one rule that keeps d_rec_count equal to d_count wherever the host writes the latter
   PtrArrays          mixin: _arr, a pointer array kept alive beside its tensors; _bind_kinds, one weight format's four arrays of LINEAR_KINDS
   HookList           set_options / tune_set callbacks held through a weak reference to their owner; sync_desc_options, the rule for which
                      descriptor copy receives which option
@@ -98,6 +100,78 @@ def alloc_loop_state(owner, state, device, out_cap, logits_shape, rows=None):
     state.n_stop_ids, state.do_sample, state.top_k, state.temperature, state.top_p = 0, 0, 0, 1.0, 1.0
 
 
+class LogprobRecorder:
+    """mixin over `self.d_count` / `self.d_out` (alloc_loop_state): the recorder of include/teo_hip_logprob.h.  Off (`_rec` None) until
+    logprobs_begin; nothing is allocated before the first one."""
+    _rec = None
+    d_logprobs = d_rec_count = d_top_ids = d_top_logprobs = None
+
+    def logprobs_begin(self, top_k=0):
+        """Steps record from now on: d_logprobs [rows][out_cap] (NaN where nothing was recorded), d_rec_count, and with top_k > 0 the top
+        arrays [rows][out_cap][top_k].  The tensors are kept for the owner's life and replaced when top_k changes."""
+        top_k = int(top_k)
+        if not 0 <= top_k <= L.LOGPROB_MAX_TOP:
+            raise ValueError(f"top_logprobs {top_k} outside 0..{L.LOGPROB_MAX_TOP}")
+        if self.d_logprobs is None or self.d_top_ids.shape[-1] != top_k:
+            out, dev = self.d_out.reshape(self.d_count.numel(), -1), self.d_out.device
+            self.d_logprobs = torch.full(out.shape, float("nan"), dtype=torch.float32, device=dev)
+            self.d_rec_count = self.d_count.clone()
+            self.d_top_ids = torch.full((*out.shape, top_k), -1, dtype=torch.int64, device=dev)
+            self.d_top_logprobs = torch.full((*out.shape, top_k), float("nan"), dtype=torch.float32, device=dev)
+        r = L.LogprobRec()
+        r.d_logprobs, r.stride, r.d_rec_count, r.top_k = self.d_logprobs.data_ptr(), int(self.d_logprobs.shape[1]), self.d_rec_count.data_ptr(), top_k
+        r.d_top_ids, r.d_top_logprobs = (self.d_top_ids.data_ptr(), self.d_top_logprobs.data_ptr()) if top_k else (None, None)
+        self._rec = r
+        self.rec_sync()
+
+    def logprobs_end(self):
+        self._rec = None
+
+    def rec_sync(self, row=None):
+        """Call behind every host write of d_count (all rows, or `row`): d_rec_count takes the same value and the rows' entries go back
+        to NaN (top ids: -1).  Nothing to do before the first logprobs_begin."""
+        if self.d_rec_count is None:
+            return
+        if row is None:
+            self.d_rec_count.copy_(self.d_count)
+            rows = slice(None)
+        else:
+            self.d_rec_count[row] = self.d_count[row]
+            rows = row
+        self.d_logprobs[rows] = float("nan")
+        self.d_top_ids[rows] = -1
+        self.d_top_logprobs[rows] = float("nan")
+
+    def recorded(self, row, n):
+        """(logprobs [n], top ids [n, k] or None, top logprobs [n, k] or None) of the row's first n entries, on the host"""
+        k = int(self._rec.top_k)
+        lp = self.d_logprobs[row, :n].cpu()
+        return (lp, self.d_top_ids[row, :n].cpu(), self.d_top_logprobs[row, :n].cpu()) if k else (lp, None, None)
+
+
+def logprob_graph_key(rec, *rest):
+    """what a _logp graph holds by value: the teo_logprob_rec fields, then whatever the step beneath holds (`rest`)"""
+    return (rec.d_logprobs, rec.stride, rec.d_rec_count, rec.top_k, rec.d_top_ids, rec.d_top_logprobs) + tuple(rest)
+
+
+def logprob_rows(eng, logits, tokens, top_k=0):
+    """teo_logprob_rows over fp32 device logits [rows, V] (contiguous rows): (logprob [rows], top ids [rows, k], top logprobs [rows, k])
+    on the device -- the entry of a token the HOST selected (the first token of a call, from the prefill logits)."""
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or not logits.is_cuda:
+        raise ValueError("logprob_rows: fp32 device logits [rows, V] with contiguous rows")
+    rows, V, k = int(logits.shape[0]), int(logits.shape[1]), int(top_k)
+    lp = torch.empty(rows, dtype=torch.float32, device=eng.device)
+    ids = torch.empty(rows, k, dtype=torch.int64, device=eng.device)
+    tlp = torch.empty(rows, k, dtype=torch.float32, device=eng.device)
+    with eng.phase() as st:
+        tok = torch.as_tensor(tokens, dtype=torch.int64).reshape(-1).to(eng.device)
+        if tok.numel() != rows:
+            raise ValueError(f"logprob_rows: {rows} rows, {tok.numel()} tokens")
+        L.check(eng.lib.teo_logprob_rows(_p(logits), int(logits.stride(0)), rows, V, _p(tok), _p(lp), _p(ids) if k else None,
+                                         _p(tlp) if k else None, k, st), "teo_logprob_rows")
+    return lp, ids, tlp
+
+
 def arm_sampler(state, d_stop_ids, stop_ids, do_sample, temperature, top_k, top_p, extra=()):
     """Write the stop ids (the last MAX_STOP_IDS of them) and set the sampler fields of `state`, plus `extra` (field, value) pairs.
     All of these a captured step graph holds by value: returns True when any of them changed -- the caller drops its graphs.  The floats
@@ -118,12 +192,15 @@ def arm_sampler(state, d_stop_ids, stop_ids, do_sample, temperature, top_k, top_
 
 # ---------------------------------------------------------------------- step graphs
 class StepGraphs:
-    """mixin over `self.lib`: the captured plain step (`_graph`, None when there is none) and the guided step beside it, each with its key
-    -- everything its capture holds by value."""
+    """mixin over `self.lib`: the captured plain step (`_graph`, None when there is none), the guided step beside it and the step with the
+    log-probability recorder behind it (LOGP_SLOT, whatever its guide or share table), each with its key -- everything its capture holds
+    by value."""
+    LOGP_SLOT = ("_logp_graph", "_logp_key")
 
     def __init__(self):
         self._graph, self._graph_ws = None, None
         self._guided_graph, self._guided_key = None, None
+        self._logp_graph, self._logp_key = None, None
 
     def replay_or_step(self, stream, key, n, use_graph, create, step, guided=False, slot=None):
         """n decode steps on the engine's `stream`: plain launches (step()), or replays of the plain (or the guided) graph, captured again
@@ -152,6 +229,7 @@ class StepGraphs:
     def _drop_graph(self):
         self._destroy_graph("_graph")
         self._destroy_graph("_guided_graph")
+        self._destroy_graph("_logp_graph")
 
     def __del__(self):
         try:

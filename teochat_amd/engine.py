@@ -20,8 +20,8 @@ import warnings
 import torch
 
 from . import _lib as L
-from .decode_host import (LINEAR_KINDS, PROF_CLASSES, SEED_MASK, HookList, PtrArrays, StepGraphs, _p, alloc_loop_state, arm_sampler, profile_steps,
-                          run_prefill, sync_desc_options)
+from .decode_host import (LINEAR_KINDS, PROF_CLASSES, SEED_MASK, HookList, LogprobRecorder, PtrArrays, StepGraphs, _p, alloc_loop_state, arm_sampler,
+                          logprob_graph_key, profile_steps, run_prefill, sync_desc_options)
 
 _ACT = {"quick_gelu": L.ACT_QUICK_GELU, "gelu": L.ACT_GELU_ERF}
 VIT_PREFIX = "model.image_tower.image_tower."
@@ -281,7 +281,7 @@ def guide_graph_key(gd, ws):
     return (gd.d_next, gd.n_states, gd.vocab, gd.d_state, gd.fallback_token, ws.data_ptr())
 
 
-class TeoEngine(StepGraphs, PtrArrays):
+class TeoEngine(StepGraphs, PtrArrays, LogprobRecorder):
     def __init__(self, state_dict, config, dtype=torch.bfloat16, device="cuda:0", max_seq=None, weight_format=None, mxfp4_only=False,
                  decode_pack=True):
         self.lib = L.load()                       # raises TeoLibraryError when the HIP library is missing
@@ -847,6 +847,7 @@ class TeoEngine(StepGraphs, PtrArrays):
             self.d_token.fill_(int(first_token))
             self.d_pos.fill_(self.cache_len)
             self.d_count.zero_()
+            self.rec_sync()                       # (the recorder's count follows d_count wherever the host writes it)
             self.d_stop.zero_()
             self.d_rng[0] = int(seed) & SEED_MASK            # the same 63-bit seed teo_sample_topk gets for draw 0
             self.steps_since_begin = 0
@@ -1010,7 +1011,16 @@ class TeoEngine(StepGraphs, PtrArrays):
         d, s_ = C.byref(self.llama_desc), C.byref(self.decode_state)
         gd = self._guide
         with self.phase() as st:
-            if gd is not None:
+            if self._rec is not None:
+                # the step (plain or guided) with the recorder behind it (include/teo_hip_logprob.h), a graph of its own
+                g_, r_ = (C.byref(gd) if gd is not None else None), C.byref(self._rec)
+                self.replay_or_step(self.stream, logprob_graph_key(self._rec, guide_graph_key(gd, ws) if gd is not None else ws.data_ptr()), n,
+                                    use_graph,
+                                    lambda out: L.check(self.lib.teo_llama_decode_graph_create_logp(d, s_, g_, r_, _p(ws), ws.numel(), st, out),
+                                                        "teo_llama_decode_graph_create_logp"),
+                                    lambda: L.check(self.lib.teo_llama_decode_step_logp(d, s_, g_, r_, _p(ws), ws.numel(), st),
+                                                    "teo_llama_decode_step_logp"), slot=self.LOGP_SLOT)
+            elif gd is not None:
                 # the guided step (include/teo_hip_guide.h) and a graph of its own: the plain graph is left alone
                 g_ = C.byref(gd)
                 self.replay_or_step(self.stream, guide_graph_key(gd, ws), n, use_graph,

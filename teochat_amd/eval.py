@@ -53,7 +53,7 @@ def output_path(dataset_name, model_path, out_name=None, out_dir=None, prompt_st
 def eval(dataset_name, model_path, model_base, load_8bit=False, load_4bit=False, cache_dir=None, data_cache_dir=None,
          out_name=None, out_dir=None, prompt_strategy=None, chronological_prefix=True, conv_mode="v1", device="cuda",
          force_rerun=False, temperature=0.2, max_new_tokens=256, dataset=None, model_bundle=None, batch_size=1,
-         continuous=False, prefix_cache=False, guide=None, share_prefix=False):
+         continuous=False, prefix_cache=False, guide=None, share_prefix=False, logprobs=False):
     """Run (or re-use) the model's answers on one TEOChatlas evaluation split and print / return its task metrics.
     Extra keywords (not in the reference): `dataset` = examples to use instead of the hub download, `model_bundle` =
     (tokenizer, model, processor) already loaded, `batch_size` = examples answered per generation (1 = the reference's loop;
@@ -62,7 +62,8 @@ def eval(dataset_name, model_path, model_base, load_8bit=False, load_4bit=False,
     `prefix_cache` (with continuous) = examples about the same image sequence share its prefill (inference.run_inference_batch),
     `share_prefix` (with prefix_cache) = the decode step reads the shared rows once per group of slots (same answers),
     `guide` = "boxes": every answer is generated under the automaton of guide.BOX_LIST_PATTERN over the tokenizer's vocabulary
-    (guide.named_guide; batch_size 1 or continuous), so that it parses as a list of boxes."""
+    (guide.named_guide; batch_size 1 or continuous), so that it parses as a list of boxes,
+    `logprobs` = every record gains `confidence` and `box_confidences` (inference.run_inference(logprobs=True)); no metric reads them."""
     print("Arguments passed to eval:")
     for k, v in (("dataset_name", dataset_name), ("model_path", model_path), ("model_base", model_base), ("out_name", out_name),
                  ("out_dir", out_dir), ("prompt_strategy", prompt_strategy), ("chronological_prefix", chronological_prefix),
@@ -94,7 +95,7 @@ def eval(dataset_name, model_path, model_base, load_8bit=False, load_4bit=False,
         outputs = run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronological_prefix, conv_mode,
                                 temperature, max_new_tokens, **({"batch_size": batch_size} if batch_size != 1 else {}),
                                 **({"continuous": True} if continuous else {}), **({"prefix_cache": True} if prefix_cache else {}),
-                                **({"share_prefix": True} if share_prefix else {}), **extra)
+                                **({"share_prefix": True} if share_prefix else {}), **({"logprobs": True} if logprobs else {}), **extra)
         print(f"Saving outputs to {out_path}")
         with open(out_path, "w") as f:
             json.dump(outputs, f, indent=4)
@@ -140,6 +141,8 @@ _CLI = (
     ("share_prefix", dict(action="store_true", default=argparse.SUPPRESS)),
     # not in the reference: guided decoding (teochat_amd/guide.py) -- "boxes": answers are lists of [x1, y1, x2, y2]
     ("guide", dict(type=str, choices=["boxes"], default=argparse.SUPPRESS)),
+    # not in the reference: token log-probabilities (include/teo_hip_logprob.h) -- the records gain confidence and box_confidences
+    ("logprobs", dict(action="store_true", default=argparse.SUPPRESS)),
 )
 
 

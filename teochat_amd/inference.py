@@ -37,9 +37,11 @@ def build_prompt(inp, image_paths, conv_mode="v1", prompt_strategy="interleave",
 
 def run_inference_single(model, processor, tokenizer, inp, image_paths, conv_mode="v1", timestamps=[],
                          prompt_strategy="interleave", chronological_prefix=True, temperature=0.2, max_new_tokens=256,
-                         do_sample=True, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, guide=None):
+                         do_sample=True, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, guide=None, return_logprobs=False):
     """guide (extra trailing keyword): a teochat_amd.guide.TokenGuide over the tokenizer's vocabulary -- the answer is generated under it
-    (model.generate(guide=...)); None: the keyword is not passed on."""
+    (model.generate(guide=...)); None: the keyword is not passed on.
+    return_logprobs=True (extra trailing keyword): returns (text, {"logprobs": [...], "confidence": float, "box_confidences": [...]}) --
+    model.generate(logprobs=True) and teochat_amd/confidence.py over the generated tokens, the stop token included."""
     if len(timestamps) > 0:
         order = sorted(range(len(image_paths)), key=lambda i: datetime.strptime(timestamps[i], "%Y-%m-%d"))
         image_paths = [image_paths[i] for i in order]
@@ -57,9 +59,33 @@ def run_inference_single(model, processor, tokenizer, inp, image_paths, conv_mod
             spec["max_matching_ngram_size"] = max_matching_ngram_size
         if guide is not None:
             spec["guide"] = guide
+        if return_logprobs:
+            spec["logprobs"] = True
         output_ids = model.generate(input_ids=input_ids, images=frames, do_sample=do_sample, temperature=temperature,
                                     max_new_tokens=max_new_tokens, use_cache=True, stopping_criteria=[stopping], **spec)
+    if return_logprobs:
+        new = output_ids.sequences[0, input_ids.shape[1]:]
+        return _text(tokenizer, new), _confidence(model, tokenizer, new, output_ids.logprobs[0])
     return tokenizer.decode(output_ids[0, input_ids.shape[1]:]).replace("</s>", "").strip()
+
+
+def _text(tokenizer, new_ids):
+    return tokenizer.decode(new_ids).replace("</s>", "").strip()
+
+
+def _confidence(model, tokenizer, new_ids, logprobs):
+    """confidence.confidence_record of one answer; the tokenizer's pieces are computed once per (model, tokenizer)"""
+    from .confidence import confidence_record
+    from .guide import pieces_of
+    cached = getattr(model, "_pieces_cache", None)
+    if cached is None or cached[0] is not tokenizer:
+        cached = (tokenizer, pieces_of(tokenizer, vocab=getattr(getattr(model, "config", None), "vocab_size", None)))
+        try:
+            model._pieces_cache = cached
+        except AttributeError:
+            pass
+    n = int(new_ids.numel())
+    return confidence_record(cached[1], new_ids, logprobs[:n])
 
 
 def option_token_ids(tokenizer, option):
@@ -98,7 +124,7 @@ def run_inference_options(model, processor, tokenizer, inp, image_paths, options
 
 def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, conv_mode="v1", timestamps_list=None,
                         prompt_strategy="interleave", chronological_prefix=True, temperature=0.2, max_new_tokens=256,
-                        do_sample=True, continuous=False, slots=None, prefix_cache=False, guides=None, share_prefix=False):
+                        do_sample=True, continuous=False, slots=None, prefix_cache=False, guides=None, share_prefix=False, logprobs=False):
     """run_inference_single for up to 16 examples at once (not in the reference, whose loop is one example at a time,
     inference.py:100-113): the same prompt construction, frame order, tokenisation and stop keyword per example, then ONE
     batched generation -- every frame of every example through the tower together, one prefill per example, and a decode loop
@@ -120,7 +146,10 @@ def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, con
     generate_stream(guides=...).
 
     share_prefix=True (with prefix_cache=True only): generate_stream(share_prefix=True) -- the decode step reads the rows examples were
-    forked from once per group of slots; the answers are the same."""
+    forked from once per group of slots; the answers are the same.
+
+    logprobs=True: every entry of the returned list is (text, confidence record) as run_inference_single(return_logprobs=True) returns
+    them (generate_batch / generate_stream with logprobs=True)."""
     B = len(inps)
     if share_prefix and not prefix_cache:
         raise ValueError("share_prefix needs prefix_cache=True (only forked rows are known to be shared)")
@@ -130,7 +159,8 @@ def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, con
         raise ValueError("guides needs continuous=True (generate_stream takes one guide per request; the fixed-group batched step takes none)")
     if continuous:
         return _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, conv_mode, timestamps_list, prompt_strategy,
-                                     chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache, guides, share_prefix)
+                                     chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache, guides, share_prefix,
+                                     logprobs)
     if timestamps_list is None:
         timestamps_list = [[] for _ in range(B)]
     if len(image_paths_list) != B or len(timestamps_list) != B:
@@ -149,7 +179,9 @@ def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, con
         crits.append([KeywordsStoppingCriteria([stop_str], tokenizer, input_ids)])
     with torch.inference_mode():
         outs = model.generate_batch(ids_list, frames_list, do_sample=do_sample, temperature=temperature,
-                                    max_new_tokens=max_new_tokens, stopping_criteria=crits)
+                                    max_new_tokens=max_new_tokens, stopping_criteria=crits, **({"logprobs": True} if logprobs else {}))
+    if logprobs:
+        return [(_text(tokenizer, o[0][n:]), _confidence(model, tokenizer, o[0][n:], o[1])) for o, n in zip(outs, n_prompt)]
     return [tokenizer.decode(o[n:]).replace("</s>", "").strip() for o, n in zip(outs, n_prompt)]
 
 
@@ -185,7 +217,7 @@ class _Prepared:
 
 def _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, conv_mode, timestamps_list, prompt_strategy,
                           chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache=False, guides=None,
-                          share_prefix=False):
+                          share_prefix=False, logprobs=False):
     N = len(inps)
     if N == 0:
         return []
@@ -227,7 +259,9 @@ def _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, c
         outs = model.generate_stream(prepared.column(0), prepared.column(1), slots=slots, do_sample=do_sample, temperature=temperature,
                                      max_new_tokens=max_new_tokens, stopping_criteria=prepared.column(2),
                                      **({"prefix_keys": Keys()} if prefix_cache else {}), **({"guides": guides} if guides is not None else {}),
-                                     **({"share_prefix": True} if share_prefix else {}))
+                                     **({"share_prefix": True} if share_prefix else {}), **({"logprobs": True} if logprobs else {}))
+    if logprobs:
+        return [(_text(tokenizer, o[0][n_prompt[i]:]), _confidence(model, tokenizer, o[0][n_prompt[i]:], o[1])) for i, o in enumerate(outs)]
     return [tokenizer.decode(o[n_prompt[i]:]).replace("</s>", "").strip() for i, o in enumerate(outs)]
 
 
@@ -258,7 +292,7 @@ def _record(example, response, dataset):
 
 
 def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronological_prefix, conv_mode, temperature,
-                  max_new_tokens, batch_size=1, continuous=False, prefix_cache=False, guide=None, share_prefix=False):
+                  max_new_tokens, batch_size=1, continuous=False, prefix_cache=False, guide=None, share_prefix=False, logprobs=False):
     """Dataset loop with the bookkeeping the metrics need (inference.py:88-137): response / ground truth / task per example,
     the example's polygon when it has one, and the integer boxes quoted in the question and in the reference answer.
     batch_size (extra trailing keyword, default 1 = the reference's loop): answer that many consecutive examples per
@@ -271,7 +305,18 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
     group of slots (run_inference_batch(share_prefix=True)); the records are the same.
     guide (extra trailing keyword): a teochat_amd.guide.TokenGuide for every example, or a callable(example) -> TokenGuide or None.  With
     batch_size 1 it goes to run_inference_single(guide=...), with continuous=True to generate_stream(guides=...); groups of a fixed
-    batch_size > 1 take no guide (ValueError)."""
+    batch_size > 1 take no guide (ValueError).
+    logprobs=True (extra trailing keyword): every record gains `confidence` (exp of the mean token log-probability of the answer) and
+    `box_confidences` ([[box, score], ...] for the boxes of the response; teochat_amd/confidence.py), at batch_size 1, in groups and
+    continuous alike.  The metrics functions do not read the two keys."""
+    lp_kw = {"logprobs": True} if logprobs else {}
+
+    def record(example, response):
+        if not logprobs:
+            return _record(example, response, dataset)
+        rec = _record(example, response[0], dataset)
+        rec["confidence"], rec["box_confidences"] = response[1]["confidence"], response[1]["box_confidences"]
+        return rec
     if not 1 <= int(batch_size) <= 16:
         raise ValueError(f"batch_size {batch_size}: 1..16 examples per generation")
     if prefix_cache and not continuous:
@@ -300,15 +345,16 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
                                         max_new_tokens=max_new_tokens, continuous=True, slots=int(batch_size),
                                         **({"prefix_cache": True} if prefix_cache else {}),
                                         **({"share_prefix": True} if share_prefix else {}),
-                                        **({"guides": Field(guide_of)} if guide is not None else {}))
-        return [_record(dataset[i], r, dataset) for i, r in enumerate(responses)]
+                                        **({"guides": Field(guide_of)} if guide is not None else {}), **lp_kw)
+        return [record(dataset[i], r) for i, r in enumerate(responses)]
     if batch_size == 1:
         for example in dataset:
             response = run_inference_single(model, processor, tokenizer, example["conversations"][0]["value"], example["video"],
                                             conv_mode=conv_mode, timestamps=example["timestamp"], prompt_strategy=prompt_strategy,
                                             chronological_prefix=chronological_prefix, temperature=temperature,
-                                            max_new_tokens=max_new_tokens, **({"guide": guide_of(example)} if guide is not None else {}))
-            outputs.append(_record(example, response, dataset))
+                                            max_new_tokens=max_new_tokens, **({"guide": guide_of(example)} if guide is not None else {}),
+                                            **({"return_logprobs": True} if logprobs else {}))
+            outputs.append(record(example, response))
         return outputs
     group = []
 
@@ -319,8 +365,8 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
                                         [e["video"] for e in group], conv_mode=conv_mode,
                                         timestamps_list=[e["timestamp"] for e in group], prompt_strategy=prompt_strategy,
                                         chronological_prefix=chronological_prefix, temperature=temperature,
-                                        max_new_tokens=max_new_tokens)
-        outputs.extend(_record(e, r, dataset) for e, r in zip(group, responses))
+                                        max_new_tokens=max_new_tokens, **lp_kw)
+        outputs.extend(record(e, r) for e, r in zip(group, responses))
         group.clear()
 
     for example in dataset:

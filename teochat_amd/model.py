@@ -31,6 +31,42 @@ class CausalLMOutputWithPast(dict):
         return tuple(v for v in (self.loss, self.logits, self.past_key_values, self.hidden_states, self.attentions) if v is not None)
 
 
+class GenerateOutput(dict):
+    """What generate(logprobs=True) returns (attribute + key access): `sequences` is exactly what generate() returns without the keyword;
+    `logprobs` fp32 [B, n_new] holds log softmax(logits)[token] of every new token (NaN behind a row's end); `top_token_ids` /
+    `top_logprobs` [B, n_new, k] the k most likely tokens of each step, or None with top_logprobs=0."""
+
+    def __init__(self, sequences=None, logprobs=None, top_token_ids=None, top_logprobs=None):
+        super().__init__(sequences=sequences, logprobs=logprobs, top_token_ids=top_token_ids, top_logprobs=top_logprobs)
+        self.__dict__ = self
+
+
+def check_logprob_args(logprobs, top_logprobs, prompt_lookup_num_tokens=None):
+    """the keyword rules of generate() / generate_batch() / generate_stream(); returns top_logprobs as an int"""
+    k = int(top_logprobs or 0)
+    if not 0 <= k <= L.LOGPROB_MAX_TOP:
+        raise ValueError(f"top_logprobs {k} outside 0..{L.LOGPROB_MAX_TOP}")
+    if k and not logprobs:
+        raise ValueError("top_logprobs needs logprobs=True")
+    if logprobs and prompt_lookup_num_tokens:
+        raise ValueError("logprobs=True is not combined with prompt_lookup_num_tokens (the speculative verify step records no log-probabilities)")
+    return k
+
+
+def _pack_logprobs(entries, k):
+    """[(logprobs [n_b], top ids [n_b, k] or None, top logprobs or None)] -> padded [B, n], [B, n, k], [B, n, k] (NaN / -1 behind a row's end)"""
+    n = max(int(e[0].numel()) for e in entries)
+    lp = torch.full((len(entries), n), float("nan"), dtype=torch.float32)
+    ids = torch.full((len(entries), n, k), -1, dtype=torch.int64) if k else None
+    tlp = torch.full((len(entries), n, k), float("nan"), dtype=torch.float32) if k else None
+    for b, e in enumerate(entries):
+        m = int(e[0].numel())
+        lp[b, :m] = e[0]
+        if k:
+            ids[b, :m], tlp[b, :m] = e[1], e[2]
+    return lp, ids, tlp
+
+
 class TeoKVCache:
     """Handle to the engine's device KV cache (one sequence).  `[-1][-1].shape[-2]` reports the cached length so that
     code written against the legacy tuple cache (llava_arch.py:156) keeps working."""
@@ -501,15 +537,18 @@ class LlavaLlamaForCausalLM:
     def generate(self, *args, **kwargs):
         # one engine phase around the whole call: tower, projector, splice, prefill and the decode chunks run back to back on the
         # engine stream with a single hand-over to the caller's stream at the end (no stream edges between the pieces)
+        check_logprob_args(kwargs.get("logprobs"), kwargs.get("top_logprobs"), kwargs.get("prompt_lookup_num_tokens"))
         with self.engine.phase():
             try:
                 return self._generate(*args, **kwargs)
             finally:
-                self.engine.guide_end()           # a guide arms the engine's steps for this call only
+                self.engine.guide_end()           # a guide and the recorder arm the engine's steps for this call only
+                self.engine.logprobs_end()
 
     def _generate(self, input_ids=None, images=None, do_sample=None, temperature=None, top_k=None, top_p=None,
                   max_new_tokens=20, use_cache=True, stopping_criteria=None, eos_token_id="config", attention_mask=None,
-                  generator=None, chunk=16, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, prefix_key=None, guide=None, **kwargs):
+                  generator=None, chunk=16, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, prefix_key=None, guide=None, logprobs=False,
+                  top_logprobs=0, **kwargs):
         """Greedy or sampled (temperature / top-k, device sampler) decoding of ONE sequence; the loop is device-resident
         and replayed from a hipGraph.
 
@@ -535,6 +574,13 @@ class LlavaLlamaForCausalLM:
         answer in the middle of the pattern.  Works with prefix_key (nothing in the prefix path reads the guide).
         `last_generation_stats` gains guide_states and guide_table_bytes.
 
+        logprobs=True (not with prompt_lookup_num_tokens), top_logprobs=k (0..8): returns a GenerateOutput instead of the ids tensor --
+        `sequences` is that tensor, `logprobs` [B, n_new] the natural-log probability the model gave each new token, the stop token
+        included, `top_token_ids` / `top_logprobs` [B, n_new, k] the k most likely tokens of each step (None with k = 0).  The value is
+        log softmax(logits)[token]: temperature, top_k and top_p do not enter.  One more launch behind each decode step records it on the
+        device (include/teo_hip_logprob.h); the first token's entry comes from the prefill logits.  Under a guide the row is the masked
+        one, so the value is the probability AMONG THE TOKENS THE GUIDE ALLOWED.  With the keyword unset nothing changes.
+
         Returns int64 [1, n_prompt + n_generated]; the prompt part still contains the -200 sentinels, as with the
         reference (eval/inference.py:75 slices at input_ids.shape[1]).  `eos_token_id=None` disables EOS stopping.
         """
@@ -546,6 +592,7 @@ class LlavaLlamaForCausalLM:
         top_p = getattr(gc, "top_p", 1.0) if top_p is None else top_p
         self.last_generation_stats = None
         K = int(prompt_lookup_num_tokens or 0)
+        top_n = check_logprob_args(logprobs, top_logprobs, K)
         if K and prefix_key is not None:
             raise ValueError("prefix_key is not combined with prompt_lookup_num_tokens")
         record, self._prefix_record = getattr(self, "_prefix_record", None), None          # any generate() call forgets it
@@ -568,7 +615,10 @@ class LlavaLlamaForCausalLM:
                 raise ValueError("batched generate(): `images` must be a list with one entry (frame list) per conversation")
             outs = self.generate_batch(rows, images, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
                                        max_new_tokens=max_new_tokens, stopping_criteria=stopping_criteria,
-                                       eos_token_id=eos_token_id, generator=generator, chunk=chunk)
+                                       eos_token_id=eos_token_id, generator=generator, chunk=chunk, logprobs=logprobs, top_logprobs=top_n)
+            entries = None
+            if logprobs:
+                outs, entries = [o[0] for o in outs], [o[1:] for o in outs]
             # what GenerationMixin.generate returns: the input rows exactly as given (left or right padding included) followed
             # by the new tokens of each row; rows that stopped early are filled up with pad_token_id
             pad = getattr(self.config, "pad_token_id", None)
@@ -578,12 +628,16 @@ class LlavaLlamaForCausalLM:
             tail = torch.full((B, n_new), pad, dtype=input_ids.dtype, device=input_ids.device)
             for b, t in enumerate(news):
                 tail[b, :t.numel()] = t.to(tail.device)
-            return torch.cat([input_ids, tail], dim=1)
+            seqs = torch.cat([input_ids, tail], dim=1)
+            return GenerateOutput(seqs, *_pack_logprobs(entries, top_n)) if logprobs else seqs
         eng = self.engine
         if eos_token_id == "config":
             eos_token_id = self._config_eos()
         crits = list(stopping_criteria or [])
         if max_new_tokens <= 0:
+            if logprobs:
+                z = torch.zeros(1, 0, top_n)
+                return GenerateOutput(input_ids, torch.zeros(1, 0), z.to(torch.int64) if top_n else None, z if top_n else None)
             return input_ids
         # ---- prefill
         ids_t, reuse = tuple(input_ids[0].tolist()), (0, 0)
@@ -642,9 +696,27 @@ class LlavaLlamaForCausalLM:
         else:
             k, seed, tp = 0, 0, 1.0
             first = self._argmax(logits[0])
+        first_lp = None
+        if logprobs:
+            # the first token's entry: the prefill row it was selected from (masked, under a guide), through the recorder's own body
+            from .decode_host import logprob_rows
+            first_lp = [t.cpu() for t in logprob_rows(eng, logits[:1].contiguous(), [first], top_n)]
+            eng.logprobs_begin(top_n)
         if guide is not None:
             eng.guide_advance([first])
         new_tokens = [first]
+
+        def finish(tokens):
+            seqs = self._finish(input_ids, tokens)
+            if not logprobs:
+                return seqs
+            lp, ids, tlp = first_lp
+            if len(tokens) > 1:
+                r = eng.recorded(0, len(tokens) - 1)
+                lp = torch.cat([lp, r[0]])
+                if top_n:
+                    ids, tlp = torch.cat([ids, r[1]]), torch.cat([tlp, r[2]])
+            return GenerateOutput(seqs, lp.view(1, -1), ids.unsqueeze(0) if top_n else None, tlp.unsqueeze(0) if top_n else None)
 
         def done(tokens):
             if eos_token_id is not None and tokens[-1] == eos_token_id:
@@ -655,7 +727,7 @@ class LlavaLlamaForCausalLM:
             return False
 
         if done(new_tokens) or max_new_tokens == 1:
-            return self._finish(input_ids, new_tokens)
+            return finish(new_tokens)
         # ---- decode: the whole loop (incl. the sampler) runs on the device, replayed from a hipGraph in chunks;
         # the host only looks at the tokens once per chunk to apply EOS / stopping criteria at the exact token.
         cands = [ids for c in crits for ids in getattr(c, "keyword_id_lists", []) if ids]
@@ -701,7 +773,7 @@ class LlavaLlamaForCausalLM:
                     break
             if stop_here:
                 break
-        return self._finish(input_ids, new_tokens)
+        return finish(new_tokens)
 
     # --- closed-set answers: log p(option | frames, question) of every option, the options packed into one pass over the weights
     @torch.no_grad()
@@ -778,22 +850,31 @@ class LlavaLlamaForCausalLM:
 
     @torch.no_grad()
     def generate_batch(self, *args, **kwargs):
+        check_logprob_args(kwargs.get("logprobs"), kwargs.get("top_logprobs"))
         with self.engine.phase():
             return self._generate_batch(*args, **kwargs)
 
     def _generate_batch(self, input_ids_list, images_list=None, do_sample=False, temperature=None, top_k=None, top_p=None,
-                        max_new_tokens=20, stopping_criteria=None, eos_token_id="config", generator=None, chunk=16):
+                        max_new_tokens=20, stopping_criteria=None, eos_token_id="config", generator=None, chunk=16, logprobs=False,
+                        top_logprobs=0):
         """Decode B conversations together (B <= 16).  input_ids_list: B 1-D id tensors (with -200 sentinels);
         images_list: per conversation what generate() takes as `images`.  stopping_criteria: None, or one list of
         criteria per conversation.  Returns B 1-D tensors prompt + generated, each cut at its own EOS / stop keyword.
 
         One multimodal preparation and ONE prefill pass over the concatenated rows of all conversations (per-sequence RoPE,
         KV append and causal attention); the decode loop is batched: per step every weight matrix is streamed once for all
-        conversations (teo_llama_decode_batch_step)."""
+        conversations (teo_llama_decode_batch_step).
+
+        logprobs=True, top_logprobs=k: every entry of the returned list is (ids, logprobs [n_new], top ids [n_new, k] or None, top
+        logprobs or None) instead of the ids tensor, as generate_stream(logprobs=True) returns them (see generate())."""
+        top_n = check_logprob_args(logprobs, top_logprobs)
         B = len(input_ids_list)
         if eos_token_id == "config":
             eos_token_id = self._config_eos()
         if max_new_tokens <= 0:
+            if logprobs:
+                z = torch.zeros(0, top_n)
+                return [(ids.clone(), torch.zeros(0), z.to(torch.int64) if top_n else None, z if top_n else None) for ids in input_ids_list]
             return [ids.clone() for ids in input_ids_list]
         gc = self.generation_config
         temperature = float(getattr(gc, "temperature", 1.0) or 1.0) if temperature is None else temperature
@@ -840,6 +921,11 @@ class LlavaLlamaForCausalLM:
                   for b in range(B)]
         new_tokens = [[t] for t in firsts]
         finished = [False] * B
+        first_lp = None
+        if logprobs:
+            from .decode_host import logprob_rows
+            first_lp = [t.cpu() for t in logprob_rows(eng, logits[:B].contiguous(), firsts, top_n)]
+            dec.logprobs_begin(top_n)
 
         def done(b):
             toks = new_tokens[b]
@@ -869,8 +955,21 @@ class LlavaLlamaForCausalLM:
                             finished[b] = True
                             break
                 remaining -= n
-        return [torch.cat([input_ids_list[b].view(-1), torch.tensor(new_tokens[b], dtype=input_ids_list[b].dtype,
+        outs = [torch.cat([input_ids_list[b].view(-1), torch.tensor(new_tokens[b], dtype=input_ids_list[b].dtype,
                                                                      device=input_ids_list[b].device)]) for b in range(B)]
+        if not logprobs:
+            return outs
+        res = []
+        for b in range(B):
+            lp, ids, tlp = first_lp[0][b:b + 1], first_lp[1][b:b + 1], first_lp[2][b:b + 1]
+            if len(new_tokens[b]) > 1:
+                r = dec.recorded(b, len(new_tokens[b]) - 1)
+                lp = torch.cat([lp, r[0]])
+                if top_n:
+                    ids, tlp = torch.cat([ids, r[1]]), torch.cat([tlp, r[2]])
+            res.append((outs[b], lp, ids if top_n else None, tlp if top_n else None))
+        dec.logprobs_end()
+        return res
 
     # --- continuous batching: the batched step over slots that park when they finish and are refilled from a queue of requests
     def stream_decoder(self, slots, max_new=1024):
@@ -884,12 +983,13 @@ class LlavaLlamaForCausalLM:
 
     @torch.no_grad()
     def generate_stream(self, *args, **kwargs):
+        check_logprob_args(kwargs.get("logprobs"), kwargs.get("top_logprobs"))
         with self.engine.phase():
             return self._generate_stream(*args, **kwargs)
 
     def _generate_stream(self, input_ids_list, images_list=None, slots=8, max_new_tokens=20, do_sample=False, temperature=None,
                          top_k=None, top_p=None, stopping_criteria=None, eos_token_id="config", generator=None, chunk=16, prefix_keys=None,
-                         min_prefix_rows=64, guides=None, share_prefix=False):
+                         min_prefix_rows=64, guides=None, share_prefix=False, logprobs=False, top_logprobs=0):
         """Answer N requests (any N >= 1) over `slots` <= 16 conversation slots of the batched decode step: a slot whose request has
         finished parks -- the attention kernels skip it -- and is refilled with the next request, so a step's work follows the requests
         that are still being answered instead of the longest answer of a fixed group (teochat_amd/stream.py).
@@ -925,8 +1025,14 @@ class LlavaLlamaForCausalLM:
         everything.  A request's first token is selected from its prefill logits under its guide's start state, its slot then starts
         from the successor; the step's tail masks, selects and moves every live slot's state (include/teo_hip_guide.h).  EOS stays the
         stop, the guide decides when it is allowed; max_new_tokens may cut an answer mid-pattern.  The stats gain guide_states and
-        guide_table_bytes."""
+        guide_table_bytes.
+
+        logprobs=True, top_logprobs=k (0..8): returns per request (ids, logprobs [n_new], top ids [n_new, k] or None, top logprobs or None)
+        instead of the ids tensor; the values are generate()'s (log softmax of the row each token was selected from, the masked row under
+        a guide), recorded by one more launch behind each stream step, plain, guided or shared (include/teo_hip_logprob.h)."""
+        from .decode_host import logprob_rows
         from .stream import request_seed, run_stream
+        top_n = check_logprob_args(logprobs, top_logprobs)
         N = len(input_ids_list)
         slots = int(slots)
         if N < 1:
@@ -963,6 +1069,9 @@ class LlavaLlamaForCausalLM:
                             eos=eos_token_id if eos_token_id is not None else self._config_eos())
         dec.set_guide(gset)
         dec.share_prefix(bool(share_prefix))
+        if logprobs:
+            dec.logprobs_begin(top_n)
+        first_lp = {}                             # request -> its first token's entry (from the prefill logits)
         ids_of, crits_of = {}, {}                 # the requests in flight (and, for ids, the finished ones: a few integers each)
         dev_stop = {"ids": None, "off": False}    # the device stop: one id sequence shared by every request admitted so far, or off
 
@@ -1029,6 +1138,10 @@ class LlavaLlamaForCausalLM:
                 seed = request_seed(base_seed, r)
                 first = eng.sample(logits[b], temperature, k, seed, 0, top_p=tp) if do_sample else self._argmax(logits[b])
                 out.append((first, min(max_new[r] - 1, eng.max_seq - lens[b]), seed))
+            if logprobs:
+                got = [t.cpu() for t in logprob_rows(eng, logits[:len(reqs)].contiguous(), [f[0] for f in out], top_n)]
+                for b, r in enumerate(reqs):
+                    first_lp[r] = tuple(t[b:b + 1] for t in got)
             if gset is not None:
                 eng.guide_advance([f[0] for f in out], g0)
                 dec.set_guide_states(slot_list, st0)
@@ -1078,18 +1191,20 @@ class LlavaLlamaForCausalLM:
             return False
 
         todo = [r for r in range(N) if max_new[r] > 0]
+        step_lp = {}                              # request -> what the recorder holds for its step tokens, read when it finishes
+        fin = (lambda i, slot, n: step_lp.__setitem__(todo[i], dec.recorded(slot, n))) if logprobs else None
         if prefix_keys is not None and len(prefix_keys) != N:
             raise ValueError("prefix_keys must hold one key (or None) per request")
         if not todo:
             results, stats = [], None
         elif prefix_keys is None:
             results, stats = run_stream(dec, len(todo), slots, lambda reqs, sl: admit([todo[i] for i in reqs], sl),
-                                        lambda i, toks: host_done(todo[i], toks), chunk=chunk)
+                                        lambda i, toks: host_done(todo[i], toks), chunk=chunk, on_finish=fin)
         else:
             results, stats = run_stream(dec, len(todo), slots, None, lambda i, toks: host_done(todo[i], toks), chunk=chunk,
                                         keys=[prefix_keys[r] for r in todo], ids_of=lambda i: input_ids_list[todo[i]].view(-1).tolist(),
                                         admit_past=lambda items: admit_past([(todo[i], s, p, P) for i, s, p, P in items]),
-                                        min_prefix_rows=min_prefix_rows)
+                                        min_prefix_rows=min_prefix_rows, on_finish=fin)
         outs = []
         new_of = {todo[i]: toks for i, toks in enumerate(results)}
         for r in range(N):
@@ -1106,6 +1221,19 @@ class LlavaLlamaForCausalLM:
         dec.set_guide(None)
         dec.share_prefix(False)
         self.last_generation_stats = stats
+        if logprobs:
+            dec.logprobs_end()
+            z = torch.zeros(0, top_n)
+            res = []
+            for r in range(N):
+                lp, ids, tlp = first_lp.get(r, (torch.zeros(0), z.to(torch.int64), z))
+                if r in step_lp:
+                    more = step_lp[r]
+                    lp = torch.cat([lp, more[0]])
+                    if top_n:
+                        ids, tlp = torch.cat([ids, more[1]]), torch.cat([tlp, more[2]])
+                res.append((outs[r], lp, ids if top_n else None, tlp if top_n else None))
+            return res
         return outs
 
     def _config_eos(self):

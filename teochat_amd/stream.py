@@ -18,7 +18,7 @@ import torch
 
 from . import _lib as L
 from .batch import BatchDecoder
-from .decode_host import SEED_MASK, StepGraphs, _p, arm_sampler, run_prefill
+from .decode_host import SEED_MASK, StepGraphs, _p, arm_sampler, logprob_graph_key, run_prefill
 from .engine import guide_graph_key
 
 SEED_STRIDE = 0x9E3779B97F4A7C15              # request i draws from the Philox stream seeded (base + i * SEED_STRIDE) mod 2^63
@@ -159,6 +159,7 @@ class StreamDecoder(StepGraphs):
         with self.eng.phase():
             bd.d_pos.fill_(-1)
             bd.d_count.zero_()
+            bd.rec_sync()                         # (the recorder lives with d_count, in the BatchDecoder: its count follows every host write)
             bd.d_stop.fill_(1)
             bd.d_token.zero_()
             self.d_limit.fill_(1)
@@ -326,6 +327,7 @@ class StreamDecoder(StepGraphs):
             bd.d_token[slot] = int(first_token)
             bd.d_pos[slot] = pos
             bd.d_count[slot] = 0
+            bd.rec_sync(slot)
             bd.d_stop[slot] = 0
             self.d_limit[slot] = limit
             bd.d_rng[slot] = torch.tensor([int(seed) & SEED_MASK, int(draws_done)], dtype=torch.int64, device=eng.device)
@@ -347,8 +349,28 @@ class StreamDecoder(StepGraphs):
         if self._share_on:
             chunk = self.share_chunk()
             skip = self.share.skipped(chunk, self.live)
+        rec = bd._rec
         with eng.phase() as st:
-            if skip:
+            if rec is not None:
+                # whichever step the branches below would run -- plain, guided, shared -- with the recorder behind it
+                # (include/teo_hip_logprob.h): one entry point, one graph of its own whose key says which step it holds
+                if skip and self.share.dirty:
+                    self.d_share_lead.copy_(torch.tensor(self.share.lead, dtype=torch.int32))
+                    self.d_share_rows.copy_(torch.tensor(self.share.rows, dtype=torch.int32))
+                    self.share.dirty = False
+                g_ = C.byref(gd) if gd is not None else None
+                sh_ = C.byref(self._share) if skip else None
+                r_ = C.byref(rec)
+                key = logprob_graph_key(rec, ws.data_ptr(), guide_graph_key(gd, ws) if gd is not None else None, bool(skip))
+                self.replay_or_step(eng.stream, key, n, use_graph,
+                                    lambda out: L.check(self.lib.teo_llama_decode_stream_graph_create_logp(d, s_, sh_, g_, r_, _p(ws), ws.numel(), st, out),
+                                                        "teo_llama_decode_stream_graph_create_logp"),
+                                    lambda: L.check(self.lib.teo_llama_decode_stream_step_logp(d, s_, sh_, g_, r_, _p(ws), ws.numel(), st),
+                                                    "teo_llama_decode_stream_step_logp"), slot=self.LOGP_SLOT)
+                if skip:
+                    self._stats["shared_steps"] += n
+                    self._stats["shared_rows_skipped"] += n * skip
+            elif skip:
                 # at least one live slot shares a whole chunk with its leader: the shared step, plain or guided tail.  The table is
                 # uploaded on the engine stream in front of the step whenever the mirror changed; the graph reads it from device memory
                 if self.share.dirty:
@@ -397,6 +419,19 @@ class StreamDecoder(StepGraphs):
                     parked.append(s)
             self.pos[s], self.count[s] = pos[s], cnt[s]
         return parked
+
+    def logprobs_begin(self, top_k=0):
+        """steps() records every live slot's tokens from now on (the BatchDecoder's recorder: it lives with d_count)"""
+        self.bd.logprobs_begin(top_k)
+
+    def logprobs_end(self):
+        self.bd.logprobs_end()
+
+    def recorded(self, slot, n=None):
+        """what the recorder holds for the first n tokens slot `slot` has produced by steps (default: all, as of the last poll); read it
+        before the slot is armed again"""
+        with self.eng.phase():
+            return self.bd.recorded(slot, self.count[slot] if n is None else min(int(n), self.count[slot]))
 
     def tokens(self, slot, start=0):
         """The tokens slot `slot` has produced by steps (its first token excluded), from index `start`, as of the last poll."""
@@ -539,7 +574,8 @@ def _admit_prefix(dec, reqs, free, queue, slots, keys, ids_of, admit_past, min_p
     return [(r, slot_of[r]) + tuple(first[r]) for r in reqs]
 
 
-def run_stream(dec, n_requests, slots, admit, host_done, chunk=16, *, keys=None, ids_of=None, admit_past=None, min_prefix_rows=64):
+def run_stream(dec, n_requests, slots, admit, host_done, chunk=16, *, keys=None, ids_of=None, admit_past=None, min_prefix_rows=64,
+               on_finish=None):
     """The scheduler.  dec: refill / arm / steps / poll / tokens / park as StreamDecoder has them.
       admit(reqs, slot_list) -> per request (first_token, limit, seed): runs the tower over the requests' frames in one call, ONE
                                 dec.refill(slot_list, ...) pass and picks the first tokens; limit = steps the slot may run (<= 0: none)
@@ -554,7 +590,10 @@ def run_stream(dec, n_requests, slots, admit, host_done, chunk=16, *, keys=None,
                             ids = P rows are in the slot already (embed ids[p:] only, no frames).  ONE dec.refill_past pass; returns per
                             item (first_token, limit, seed, embedded rows per id or None, rows prefilled)
     dec additionally has held / refill_past / fork.  A round is at most two passes over the weights (_admit_prefix).  The stats gain
-    prefix_hits, prefix_rows_reused, forks, fork_rows, frames_skipped and prefill_rows."""
+    prefix_hits, prefix_rows_reused, forks, fork_rows, frames_skipped and prefill_rows.
+
+    on_finish(req, slot, n): called when a request that ran in `slot` is complete, n = the tokens it keeps from the slot's steps (its first
+    token aside), BEFORE the slot is handed to another request -- the moment to read anything else the slot's steps left on the device."""
     queue = deque(range(int(n_requests)))
     free = list(range(int(slots)))
     live = {}                                     # slot -> [request, tokens, limit]
@@ -605,6 +644,8 @@ def run_stream(dec, n_requests, slots, admit, host_done, chunk=16, *, keys=None,
                 dec.park(s)
             if fired or s in parked:
                 results[r] = toks
+                if on_finish is not None:
+                    on_finish(r, s, len(toks) - 1)
                 del live[s]
                 free.append(s)
         free.sort()
