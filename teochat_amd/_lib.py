@@ -314,6 +314,30 @@ _SIGS_LOGPROB = {
                                                             C.POINTER(LogprobRec), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
 }
 EXPORTS_LOGPROB = tuple(_SIGS_LOGPROB.keys())
+
+
+# include/teo_hip_rules.h: logit rules (repetition penalty and bans) in front of the decode steps' tails, a seventh header of the same library
+class LogitRules(C.Structure):
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram", C.c_int), ("min_new", C.c_int), ("vocab", C.c_int),
+                ("d_flags", C.c_void_p), ("d_hist", C.c_void_p), ("d_hist_len", C.c_void_p), ("hist_stride", C.c_int)]
+
+
+RULE_SEEN, RULE_BANNED, RULE_EOS = 1, 2, 4
+_SIGS_RULES = {
+    "teo_logit_rules_sizeof": (C.c_size_t, []),
+    "teo_logit_rules_seed": (C.c_int, [C.POINTER(LogitRules), C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "teo_logit_rules_apply": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.POINTER(LogitRules), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "teo_llama_decode_step_ruled": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeState), C.POINTER(Guide), C.POINTER(LogprobRec),
+                                              C.POINTER(LogitRules), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "teo_llama_decode_graph_create_ruled": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeState), C.POINTER(Guide), C.POINTER(LogprobRec),
+                                                      C.POINTER(LogitRules), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "teo_llama_decode_stream_step_ruled": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeStreamState), C.POINTER(Share), C.POINTER(Guide),
+                                                     C.POINTER(LogprobRec), C.POINTER(LogitRules), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "teo_llama_decode_stream_graph_create_ruled": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeStreamState), C.POINTER(Share), C.POINTER(Guide),
+                                                             C.POINTER(LogprobRec), C.POINTER(LogitRules), C.c_void_p, C.c_size_t, C.c_void_p,
+                                                             C.POINTER(C.c_void_p)]),
+}
+EXPORTS_RULES = tuple(_SIGS_RULES.keys())
 _lib = None
 
 
@@ -335,7 +359,7 @@ def load():
     except OSError as e:
         raise TeoLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_PREFIX.items()) + list(_SIGS_SCORE.items()) + list(_SIGS_GUIDE.items()) \
-            + list(_SIGS_SHARE.items()) + list(_SIGS_LOGPROB.items()):
+            + list(_SIGS_SHARE.items()) + list(_SIGS_LOGPROB.items()) + list(_SIGS_RULES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -358,6 +382,9 @@ def load():
     if lib.teo_logprob_rec_sizeof() != C.sizeof(LogprobRec):
         raise TeoLibraryError(f"struct layout mismatch: teo_logprob_rec is {lib.teo_logprob_rec_sizeof()} bytes in {LIB_PATH}, "
                               f"{C.sizeof(LogprobRec)} in this binding; rebuild")
+    if lib.teo_logit_rules_sizeof() != C.sizeof(LogitRules):
+        raise TeoLibraryError(f"struct layout mismatch: teo_logit_rules is {lib.teo_logit_rules_sizeof()} bytes in {LIB_PATH}, "
+                              f"{C.sizeof(LogitRules)} in this binding; rebuild")
     _lib = lib
     return lib
 

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(1024) void logprob_record_kernel(const float* __res
     if (threadIdx.x == 0) rec.d_rec_count[r] = n;
 }
 
-static int logprob_rec_check(const teo_logprob_rec* rec, const char* who) {
+int logprob_rec_check(const teo_logprob_rec* rec, const char* who) {          // (also the ruled steps', rules_dev.h)
     TEO_CHECK_ARG(rec != nullptr, "%s: null rec", who);
     TEO_CHECK_ARG(rec->top_k >= 0 && rec->top_k <= TEO_LOGPROB_MAX_TOP, "%s: top_k %d outside 0..%d", who, rec->top_k, TEO_LOGPROB_MAX_TOP);
     TEO_CHECK_ARG(rec->top_k == 0 || (rec->d_top_ids && rec->d_top_logprobs), "%s: null d_top_ids / d_top_logprobs with top_k %d", who,

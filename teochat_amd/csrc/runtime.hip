@@ -8,6 +8,7 @@
 #include "guide_dev.h"
 #include "share_dev.h"
 #include "logprob_dev.h"
+#include "rules_dev.h"
 
 namespace teo {
 struct Carver {
@@ -409,7 +410,9 @@ static DecodeWs decode_carve(const teo_llama_desc* d, void* ws, size_t cap) {
 size_t llama_decode_workspace_bytes(const teo_llama_desc* d) { return decode_carve(d, nullptr, 0).total; }
 
 // g (optional, include/teo_hip_guide.h): the guided tail instead of the plain one; every launch in front of it is the same
-int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st, const teo_guide* g) {
+// lr (optional, include/teo_hip_rules.h): one rules launch over d_logits between the lm_head and the tail
+int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st, const teo_guide* g,
+                      const teo_logit_rules* lr) {
     const DecodeWs w = decode_carve(d, ws, ws_bytes);
     if (w.total > ws_bytes) {
         set_error("teo_llama_decode_step: workspace %zu < %zu", ws_bytes, w.total);
@@ -457,8 +460,13 @@ int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* 
     }
     // argmax -> append/advance/stop test -> embedding row of the next token into w.h, one launch
     prof_class(TEO_PROF_TAIL);
+    if (lr) TEO_TRY(logit_rules_apply(s->d_logits, d->vocab, 1, lr, s->d_token, s->d_out_count, s->d_stop, nullptr, st));
     if (g) return decode_tail_guided(s->d_logits, s, g, d->embed, w.h, d->vocab, D, dt, st);
     return decode_tail(s->d_logits, s, d->embed, w.h, d->vocab, D, dt, st);
+}
+
+int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st, const teo_guide* g) {
+    return llama_decode_step(d, s, ws, ws_bytes, st, g, nullptr);
 }
 
 int llama_decode_step(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -614,8 +622,10 @@ static int decode_batch_layers(const teo_llama_desc* d, const BatchLoopOpts& o, 
 // self-parking tail; the attention kernels skip parked conversations (d_pos < 0) by themselves.
 // g (optional, stream step only): the guided stream tail.
 // sh (optional, stream step only): the share table of include/teo_hip_share.h -- the attention launch reads forked rows once per group.
+// lr (optional, stream step only): the rules of include/teo_hip_rules.h -- one launch over d_logits in front of the tail; parked slots skip.
 static int decode_batch_step_impl(const teo_llama_desc* d, const teo_decode_batch_state* s, const int* d_limit, void* ws, size_t ws_bytes,
-                                  const char* who, hipStream_t st, const teo_guide* g = nullptr, const teo_share* sh = nullptr) {
+                                  const char* who, hipStream_t st, const teo_guide* g = nullptr, const teo_share* sh = nullptr,
+                                  const teo_logit_rules* lr = nullptr) {
     const int B = s->batch;
     const DecodeBatchWs w = decode_batch_carve(d, B, ws, ws_bytes);
     if (w.total > ws_bytes) {
@@ -639,6 +649,7 @@ static int decode_batch_step_impl(const teo_llama_desc* d, const teo_decode_batc
     TEO_TRY(decode_batch_layers(d, o, w, s->d_logits, attend, &skinny, who, st));
     const teo_decode_state t = batch_as_state(s);
     prof_class(TEO_PROF_TAIL);
+    if (d_limit && lr) TEO_TRY(logit_rules_apply(s->d_logits, d->vocab, B, lr, s->d_token, s->d_out_count, nullptr, s->d_pos, st));
     if (d_limit && g) {
         if (skinny)
             return decode_stream_tail_guided(s->d_logits, &t, g, d_limit, d->embed, w.h, d->vocab, D, dt, st, B, s->out_stride, d->in_norm_w[0],
@@ -671,10 +682,16 @@ teo_decode_batch_state stream_as_batch(const teo_decode_stream_state* s) {
 }
 
 int llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
-                             const teo_guide* g, const teo_share* sh) {
+                             const teo_guide* g, const teo_share* sh, const teo_logit_rules* lr) {
     const teo_decode_batch_state b = stream_as_batch(s);
-    const char* who = sh ? "teo_llama_decode_stream_step_shared" : (g ? "teo_llama_decode_stream_step_guided" : "teo_llama_decode_stream_step");
-    return decode_batch_step_impl(d, &b, s->d_limit, ws, ws_bytes, who, st, g, sh);
+    const char* who = lr ? "teo_llama_decode_stream_step_ruled"
+                         : (sh ? "teo_llama_decode_stream_step_shared" : (g ? "teo_llama_decode_stream_step_guided" : "teo_llama_decode_stream_step"));
+    return decode_batch_step_impl(d, &b, s->d_limit, ws, ws_bytes, who, st, g, sh, lr);
+}
+
+int llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
+                             const teo_guide* g, const teo_share* sh) {
+    return llama_decode_stream_step(d, s, ws, ws_bytes, st, g, sh, nullptr);
 }
 
 int llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
@@ -906,6 +923,26 @@ int decode_stream_graph_create_logp(const teo_llama_desc* d, const teo_decode_st
                                     teo_graph** out, const teo_guide* g, const teo_share* sh, const teo_logprob_rec* rec) {
     return capture_graph(st, [&]() {
         TEO_TRY(llama_decode_stream_step(d, s, ws, ws_bytes, st, g, sh));
+        return logprob_record(s->d_logits, d->vocab, s->batch, d->vocab, s->d_out_tokens, s->out_stride, s->d_out_count, rec, st);
+    }, out);
+}
+
+// include/teo_hip_rules.h: the step with the rules launch in front of its tail, then the recorder when there is one
+int decode_graph_create_ruled(const teo_llama_desc* d, const teo_decode_state* s, void* ws, size_t ws_bytes, hipStream_t st, teo_graph** out,
+                              const teo_guide* g, const teo_logprob_rec* rec, const teo_logit_rules* lr) {
+    return capture_graph(st, [&]() {
+        TEO_TRY(llama_decode_step(d, s, ws, ws_bytes, st, g, lr));
+        if (!rec) return (int)TEO_OK;
+        return logprob_record(s->d_logits, d->vocab, 1, d->vocab, s->d_out_tokens, 1, s->d_out_count, rec, st);
+    }, out);
+}
+
+int decode_stream_graph_create_ruled(const teo_llama_desc* d, const teo_decode_stream_state* s, void* ws, size_t ws_bytes, hipStream_t st,
+                                     teo_graph** out, const teo_guide* g, const teo_share* sh, const teo_logprob_rec* rec,
+                                     const teo_logit_rules* lr) {
+    return capture_graph(st, [&]() {
+        TEO_TRY(llama_decode_stream_step(d, s, ws, ws_bytes, st, g, sh, lr));
+        if (!rec) return (int)TEO_OK;
         return logprob_record(s->d_logits, d->vocab, s->batch, d->vocab, s->d_out_tokens, s->out_stride, s->d_out_count, rec, st);
     }, out);
 }

@@ -10,6 +10,8 @@ calls.  Each rule that is easy to copy wrongly is stated here and nowhere else:
   alloc_loop_state   the eight device tensors of a decode loop and the state fields that point at them
   LogprobRecorder    mixin: the recorder's tensors beside alloc_loop_state's (include/teo_hip_logprob.h), allocated at first use, and the
                      one rule that keeps d_rec_count equal to d_count wherever the host writes the latter
+  LogitRules         mixin: the flags and history of the logit rules (include/teo_hip_rules.h), allocated at first use, the host-written flag
+                     bits, the seed of a row and the host-path form for a call's first token; check_rule_args, the keywords' refusals
   PtrArrays          mixin: _arr, a pointer array kept alive beside its tensors; _bind_kinds, one weight format's four arrays of LINEAR_KINDS
   HookList           set_options / tune_set callbacks held through a weak reference to their owner; sync_desc_options, the rule for which
                      descriptor copy receives which option
@@ -172,6 +174,110 @@ def logprob_rows(eng, logits, tokens, top_k=0):
     return lp, ids, tlp
 
 
+def check_rule_args(repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, suppress_tokens=None, vocab=None):
+    """The four rule keywords of generate() / generate_stream() as (penalty, n-gram size, min new tokens, sorted suppress ids), or None
+    when every one is neutral (None / 1.0 / 0 / []).  ValueError, with a sentence, for what include/teo_hip_rules.h cannot hold."""
+    p = 1.0 if repetition_penalty is None else float(repetition_penalty)
+    n = 0 if no_repeat_ngram_size is None else int(no_repeat_ngram_size)
+    m = 0 if min_new_tokens is None else int(min_new_tokens)
+    sup = sorted({int(t) for t in (suppress_tokens if suppress_tokens is not None else [])})
+    if not 0.0 < p < float("inf"):
+        raise ValueError(f"repetition_penalty {repetition_penalty} must be a positive number (1.0 leaves the logits alone)")
+    if n < 0:
+        raise ValueError(f"no_repeat_ngram_size {n} must be 0 (off) or a positive n-gram length")
+    if m < 0:
+        raise ValueError(f"min_new_tokens {m} must not be negative")
+    if sup and vocab is not None and (sup[0] < 0 or sup[-1] >= int(vocab)):
+        raise ValueError(f"suppress_tokens holds ids outside the vocabulary 0..{int(vocab) - 1}: {[t for t in sup if not 0 <= t < int(vocab)][:8]}")
+    if p == 1.0 and n == 0 and m == 0 and not sup:
+        return None
+    return p, n, m, sup
+
+
+def rule_args_ban(rules):
+    """whether check_rule_args' result removes tokens (anything but the penalty): what a guide is not combined with"""
+    return rules is not None and bool(rules[1] or rules[2] or rules[3])
+
+
+class LogitRules:
+    """mixin over `self.lib` and the engine (`self.eng`, or self): the state of include/teo_hip_rules.h for the owner's rows.  Off (`_rules`
+    None) until rules_begin with a rule that is not neutral; nothing is allocated before that."""
+    _rules = None
+    d_rule_flags = d_rule_hist = d_rule_hist_len = None
+
+    def rules_begin(self, rows, rules, eos_ids=()):
+        """Arm the owner's steps with `rules` (check_rule_args' result; None: rules_end) for a call: flags [rows][vocab] with bits 1
+        (suppressed) and 2 (the call's EOS ids, when min_new_tokens is set) written here, once; every row's history empty until
+        rules_seed.  The history is max_seq ids per row -- an id takes at least one cache row, so no prompt plus its new tokens is longer
+        -- which keeps the tensors, and a captured graph, across calls."""
+        if rules is None:
+            self._rules = None
+            return
+        eng = getattr(self, "eng", self)
+        p, n, m, sup = rules
+        V, rows, stride = int(eng.cfg.vocab_size), int(rows), int(eng.max_seq)
+        if sup and (sup[0] < 0 or sup[-1] >= V):
+            raise ValueError(f"suppress_tokens holds ids outside the vocabulary 0..{V - 1}")
+        with eng.phase():
+            if self.d_rule_flags is None or tuple(self.d_rule_flags.shape) != (rows, V) or int(self.d_rule_hist.shape[1]) != stride:
+                self.d_rule_flags = torch.zeros(rows, V, dtype=torch.uint8, device=eng.device)
+                self.d_rule_hist = torch.zeros(rows, stride, dtype=torch.int64, device=eng.device)
+                self.d_rule_hist_len = torch.zeros(rows, dtype=torch.int32, device=eng.device)
+            col = torch.zeros(V, dtype=torch.uint8)
+            if sup:
+                col[torch.tensor(sup, dtype=torch.long)] |= L.RULE_BANNED
+            eos = [int(e) for e in eos_ids if 0 <= int(e) < V]
+            if m and eos:
+                col[torch.tensor(eos, dtype=torch.long)] |= L.RULE_EOS
+            self.d_rule_flags.copy_(col.to(eng.device).unsqueeze(0).expand(rows, V))
+            self.d_rule_hist_len.zero_()
+        r = L.LogitRules()
+        r.repetition_penalty, r.no_repeat_ngram, r.min_new, r.vocab, r.hist_stride = p, n, m, V, stride
+        r.d_flags, r.d_hist, r.d_hist_len = self.d_rule_flags.data_ptr(), self.d_rule_hist.data_ptr(), self.d_rule_hist_len.data_ptr()
+        self._rules = r
+
+    def rules_end(self):
+        self._rules = None
+
+    def rules_seed(self, row, ids):
+        """Row `row` starts the sequence `ids` (the prompt as the caller passed it, sentinels included): teo_logit_rules_seed.  At begin,
+        and whenever a stream slot is armed or refilled -- the row inherits nothing from its earlier occupant."""
+        eng = getattr(self, "eng", self)
+        with eng.phase() as st:
+            t = torch.as_tensor(ids, dtype=torch.int64).reshape(-1).to(eng.device)
+            if t.numel() > self._rules.hist_stride:
+                raise ValueError(f"rules_seed: {t.numel()} ids exceed the history ({self._rules.hist_stride})")
+            L.check(self.lib.teo_logit_rules_seed(C.byref(self._rules), int(row), _p(t) if t.numel() else None, int(t.numel()), st),
+                    "teo_logit_rules_seed")
+
+    def rules_first(self, logits, row=0):
+        """The rules over ONE fp32 device row of prefill logits [V], in place, with the state of row `row`: the host-path form for a
+        call's first token (nothing is appended, no token has been selected yet) -- before the guide's mask and teo_logprob_rows."""
+        eng = getattr(self, "eng", self)
+        r = self._rules
+        if logits.dtype != torch.float32 or not logits.is_cuda or logits.dim() != 1 or logits.stride(0) != 1 or logits.numel() != r.vocab:
+            raise ValueError("rules_first: one contiguous fp32 device row [V]")
+        one, row = L.LogitRules(), int(row)
+        for name, _ in L.LogitRules._fields_:
+            setattr(one, name, getattr(r, name))
+        one.d_flags, one.d_hist, one.d_hist_len = r.d_flags + row * r.vocab, r.d_hist + row * r.hist_stride * 8, r.d_hist_len + row * 4
+        with eng.phase() as st:
+            L.check(self.lib.teo_logit_rules_apply(_p(logits), r.vocab, 1, C.byref(one), None, None, None, st), "teo_logit_rules_apply")
+
+    def rules_in_force(self):
+        """the rules for last_generation_stats"""
+        r = self._rules
+        if r is None:
+            return {}
+        return dict(repetition_penalty=float(r.repetition_penalty), no_repeat_ngram_size=int(r.no_repeat_ngram), min_new_tokens=int(r.min_new))
+
+
+def rules_graph_key(rules, *rest):
+    """what a _ruled graph holds by value: the teo_logit_rules fields, then whatever the step beneath holds (`rest`)"""
+    return (rules.repetition_penalty, rules.no_repeat_ngram, rules.min_new, rules.vocab, rules.d_flags, rules.d_hist, rules.d_hist_len,
+            rules.hist_stride) + tuple(rest)
+
+
 def arm_sampler(state, d_stop_ids, stop_ids, do_sample, temperature, top_k, top_p, extra=()):
     """Write the stop ids (the last MAX_STOP_IDS of them) and set the sampler fields of `state`, plus `extra` (field, value) pairs.
     All of these a captured step graph holds by value: returns True when any of them changed -- the caller drops its graphs.  The floats
@@ -193,14 +299,16 @@ def arm_sampler(state, d_stop_ids, stop_ids, do_sample, temperature, top_k, top_
 # ---------------------------------------------------------------------- step graphs
 class StepGraphs:
     """mixin over `self.lib`: the captured plain step (`_graph`, None when there is none), the guided step beside it and the step with the
-    log-probability recorder behind it (LOGP_SLOT, whatever its guide or share table), each with its key -- everything its capture holds
-    by value."""
+    log-probability recorder behind it (LOGP_SLOT, whatever its guide or share table), and the step with the logit rules in front of its
+    tail (RULED_SLOT, whatever its guide, share table or recorder), each with its key -- everything its capture holds by value."""
     LOGP_SLOT = ("_logp_graph", "_logp_key")
+    RULED_SLOT = ("_ruled_graph", "_ruled_key")
 
     def __init__(self):
         self._graph, self._graph_ws = None, None
         self._guided_graph, self._guided_key = None, None
         self._logp_graph, self._logp_key = None, None
+        self._ruled_graph, self._ruled_key = None, None
 
     def replay_or_step(self, stream, key, n, use_graph, create, step, guided=False, slot=None):
         """n decode steps on the engine's `stream`: plain launches (step()), or replays of the plain (or the guided) graph, captured again
@@ -230,6 +338,7 @@ class StepGraphs:
         self._destroy_graph("_graph")
         self._destroy_graph("_guided_graph")
         self._destroy_graph("_logp_graph")
+        self._destroy_graph("_ruled_graph")
 
     def __del__(self):
         try:

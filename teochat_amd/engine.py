@@ -20,8 +20,8 @@ import warnings
 import torch
 
 from . import _lib as L
-from .decode_host import (LINEAR_KINDS, PROF_CLASSES, SEED_MASK, HookList, LogprobRecorder, PtrArrays, StepGraphs, _p, alloc_loop_state, arm_sampler,
-                          logprob_graph_key, profile_steps, run_prefill, sync_desc_options)
+from .decode_host import (LINEAR_KINDS, PROF_CLASSES, SEED_MASK, HookList, LogitRules, LogprobRecorder, PtrArrays, StepGraphs, _p, alloc_loop_state,
+                          arm_sampler, logprob_graph_key, profile_steps, rules_graph_key, run_prefill, sync_desc_options)
 
 _ACT = {"quick_gelu": L.ACT_QUICK_GELU, "gelu": L.ACT_GELU_ERF}
 VIT_PREFIX = "model.image_tower.image_tower."
@@ -281,7 +281,7 @@ def guide_graph_key(gd, ws):
     return (gd.d_next, gd.n_states, gd.vocab, gd.d_state, gd.fallback_token, ws.data_ptr())
 
 
-class TeoEngine(StepGraphs, PtrArrays, LogprobRecorder):
+class TeoEngine(StepGraphs, PtrArrays, LogprobRecorder, LogitRules):
     def __init__(self, state_dict, config, dtype=torch.bfloat16, device="cuda:0", max_seq=None, weight_format=None, mxfp4_only=False,
                  decode_pack=True):
         self.lib = L.load()                       # raises TeoLibraryError when the HIP library is missing
@@ -1011,7 +1011,19 @@ class TeoEngine(StepGraphs, PtrArrays, LogprobRecorder):
         d, s_ = C.byref(self.llama_desc), C.byref(self.decode_state)
         gd = self._guide
         with self.phase() as st:
-            if self._rec is not None:
+            if self._rules is not None:
+                # the step (plain or guided, with or without the recorder) with the rules launch in front of its tail
+                # (include/teo_hip_rules.h), a graph of its own
+                lr, rec = self._rules, self._rec
+                g_, r_, l_ = (C.byref(gd) if gd is not None else None), (C.byref(rec) if rec is not None else None), C.byref(lr)
+                key = rules_graph_key(lr, logprob_graph_key(rec) if rec is not None else None,
+                                      guide_graph_key(gd, ws) if gd is not None else ws.data_ptr())
+                self.replay_or_step(self.stream, key, n, use_graph,
+                                    lambda out: L.check(self.lib.teo_llama_decode_graph_create_ruled(d, s_, g_, r_, l_, _p(ws), ws.numel(), st, out),
+                                                        "teo_llama_decode_graph_create_ruled"),
+                                    lambda: L.check(self.lib.teo_llama_decode_step_ruled(d, s_, g_, r_, l_, _p(ws), ws.numel(), st),
+                                                    "teo_llama_decode_step_ruled"), slot=self.RULED_SLOT)
+            elif self._rec is not None:
                 # the step (plain or guided) with the recorder behind it (include/teo_hip_logprob.h), a graph of its own
                 g_, r_ = (C.byref(gd) if gd is not None else None), C.byref(self._rec)
                 self.replay_or_step(self.stream, logprob_graph_key(self._rec, guide_graph_key(gd, ws) if gd is not None else ws.data_ptr()), n,

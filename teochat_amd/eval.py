@@ -53,7 +53,8 @@ def output_path(dataset_name, model_path, out_name=None, out_dir=None, prompt_st
 def eval(dataset_name, model_path, model_base, load_8bit=False, load_4bit=False, cache_dir=None, data_cache_dir=None,
          out_name=None, out_dir=None, prompt_strategy=None, chronological_prefix=True, conv_mode="v1", device="cuda",
          force_rerun=False, temperature=0.2, max_new_tokens=256, dataset=None, model_bundle=None, batch_size=1,
-         continuous=False, prefix_cache=False, guide=None, share_prefix=False, logprobs=False):
+         continuous=False, prefix_cache=False, guide=None, share_prefix=False, logprobs=False, repetition_penalty=None,
+         no_repeat_ngram_size=None):
     """Run (or re-use) the model's answers on one TEOChatlas evaluation split and print / return its task metrics.
     Extra keywords (not in the reference): `dataset` = examples to use instead of the hub download, `model_bundle` =
     (tokenizer, model, processor) already loaded, `batch_size` = examples answered per generation (1 = the reference's loop;
@@ -63,7 +64,9 @@ def eval(dataset_name, model_path, model_base, load_8bit=False, load_4bit=False,
     `share_prefix` (with prefix_cache) = the decode step reads the shared rows once per group of slots (same answers),
     `guide` = "boxes": every answer is generated under the automaton of guide.BOX_LIST_PATTERN over the tokenizer's vocabulary
     (guide.named_guide; batch_size 1 or continuous), so that it parses as a list of boxes,
-    `logprobs` = every record gains `confidence` and `box_confidences` (inference.run_inference(logprobs=True)); no metric reads them."""
+    `logprobs` = every record gains `confidence` and `box_confidences` (inference.run_inference(logprobs=True)); no metric reads them,
+    `repetition_penalty` / `no_repeat_ngram_size` = the logit rules of generate() / generate_stream() (include/teo_hip_rules.h; batch_size 1
+    or continuous)."""
     print("Arguments passed to eval:")
     for k, v in (("dataset_name", dataset_name), ("model_path", model_path), ("model_base", model_base), ("out_name", out_name),
                  ("out_dir", out_dir), ("prompt_strategy", prompt_strategy), ("chronological_prefix", chronological_prefix),
@@ -95,7 +98,9 @@ def eval(dataset_name, model_path, model_base, load_8bit=False, load_4bit=False,
         outputs = run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronological_prefix, conv_mode,
                                 temperature, max_new_tokens, **({"batch_size": batch_size} if batch_size != 1 else {}),
                                 **({"continuous": True} if continuous else {}), **({"prefix_cache": True} if prefix_cache else {}),
-                                **({"share_prefix": True} if share_prefix else {}), **({"logprobs": True} if logprobs else {}), **extra)
+                                **({"share_prefix": True} if share_prefix else {}), **({"logprobs": True} if logprobs else {}),
+                                **({"repetition_penalty": repetition_penalty} if repetition_penalty is not None else {}),
+                                **({"no_repeat_ngram_size": no_repeat_ngram_size} if no_repeat_ngram_size is not None else {}), **extra)
         print(f"Saving outputs to {out_path}")
         with open(out_path, "w") as f:
             json.dump(outputs, f, indent=4)
@@ -143,6 +148,9 @@ _CLI = (
     ("guide", dict(type=str, choices=["boxes"], default=argparse.SUPPRESS)),
     # not in the reference: token log-probabilities (include/teo_hip_logprob.h) -- the records gain confidence and box_confidences
     ("logprobs", dict(action="store_true", default=argparse.SUPPRESS)),
+    # not in the reference: logit rules inside the device decode loop (include/teo_hip_rules.h), HF's keywords of the same names
+    ("repetition_penalty", dict(type=float, default=argparse.SUPPRESS)),
+    ("no_repeat_ngram_size", dict(type=int, default=argparse.SUPPRESS)),
 )
 
 

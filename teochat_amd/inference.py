@@ -37,11 +37,14 @@ def build_prompt(inp, image_paths, conv_mode="v1", prompt_strategy="interleave",
 
 def run_inference_single(model, processor, tokenizer, inp, image_paths, conv_mode="v1", timestamps=[],
                          prompt_strategy="interleave", chronological_prefix=True, temperature=0.2, max_new_tokens=256,
-                         do_sample=True, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, guide=None, return_logprobs=False):
+                         do_sample=True, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, guide=None, repetition_penalty=None,
+                         no_repeat_ngram_size=None, return_logprobs=False):
     """guide (extra trailing keyword): a teochat_amd.guide.TokenGuide over the tokenizer's vocabulary -- the answer is generated under it
     (model.generate(guide=...)); None: the keyword is not passed on.
     return_logprobs=True (extra trailing keyword): returns (text, {"logprobs": [...], "confidence": float, "box_confidences": [...]}) --
-    model.generate(logprobs=True) and teochat_amd/confidence.py over the generated tokens, the stop token included."""
+    model.generate(logprobs=True) and teochat_amd/confidence.py over the generated tokens, the stop token included.
+    repetition_penalty / no_repeat_ngram_size (extra trailing keywords): model.generate's logit rules (include/teo_hip_rules.h); None: the
+    keyword is not passed on."""
     if len(timestamps) > 0:
         order = sorted(range(len(image_paths)), key=lambda i: datetime.strptime(timestamps[i], "%Y-%m-%d"))
         image_paths = [image_paths[i] for i in order]
@@ -61,6 +64,10 @@ def run_inference_single(model, processor, tokenizer, inp, image_paths, conv_mod
             spec["guide"] = guide
         if return_logprobs:
             spec["logprobs"] = True
+        if repetition_penalty is not None:
+            spec["repetition_penalty"] = repetition_penalty
+        if no_repeat_ngram_size is not None:
+            spec["no_repeat_ngram_size"] = no_repeat_ngram_size
         output_ids = model.generate(input_ids=input_ids, images=frames, do_sample=do_sample, temperature=temperature,
                                     max_new_tokens=max_new_tokens, use_cache=True, stopping_criteria=[stopping], **spec)
     if return_logprobs:
@@ -124,7 +131,8 @@ def run_inference_options(model, processor, tokenizer, inp, image_paths, options
 
 def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, conv_mode="v1", timestamps_list=None,
                         prompt_strategy="interleave", chronological_prefix=True, temperature=0.2, max_new_tokens=256,
-                        do_sample=True, continuous=False, slots=None, prefix_cache=False, guides=None, share_prefix=False, logprobs=False):
+                        do_sample=True, continuous=False, slots=None, prefix_cache=False, guides=None, share_prefix=False, logprobs=False,
+                        repetition_penalty=None, no_repeat_ngram_size=None):
     """run_inference_single for up to 16 examples at once (not in the reference, whose loop is one example at a time,
     inference.py:100-113): the same prompt construction, frame order, tokenisation and stop keyword per example, then ONE
     batched generation -- every frame of every example through the tower together, one prefill per example, and a decode loop
@@ -149,8 +157,14 @@ def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, con
     forked from once per group of slots; the answers are the same.
 
     logprobs=True: every entry of the returned list is (text, confidence record) as run_inference_single(return_logprobs=True) returns
-    them (generate_batch / generate_stream with logprobs=True)."""
+    them (generate_batch / generate_stream with logprobs=True).
+
+    repetition_penalty / no_repeat_ngram_size (with continuous=True only): generate_stream's logit rules, one setting for all examples."""
     B = len(inps)
+    rule_kw = {k: v for k, v in (("repetition_penalty", repetition_penalty), ("no_repeat_ngram_size", no_repeat_ngram_size)) if v is not None}
+    if rule_kw and not continuous:
+        raise ValueError("repetition_penalty / no_repeat_ngram_size need continuous=True (generate_stream applies the rules per slot; the "
+                         "fixed-group batched step has no form with them)")
     if share_prefix and not prefix_cache:
         raise ValueError("share_prefix needs prefix_cache=True (only forked rows are known to be shared)")
     if prefix_cache and not continuous:
@@ -160,7 +174,7 @@ def run_inference_batch(model, processor, tokenizer, inps, image_paths_list, con
     if continuous:
         return _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, conv_mode, timestamps_list, prompt_strategy,
                                      chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache, guides, share_prefix,
-                                     logprobs)
+                                     logprobs, rule_kw)
     if timestamps_list is None:
         timestamps_list = [[] for _ in range(B)]
     if len(image_paths_list) != B or len(timestamps_list) != B:
@@ -217,7 +231,7 @@ class _Prepared:
 
 def _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, conv_mode, timestamps_list, prompt_strategy,
                           chronological_prefix, temperature, max_new_tokens, do_sample, slots, prefix_cache=False, guides=None,
-                          share_prefix=False, logprobs=False):
+                          share_prefix=False, logprobs=False, rule_kw=None):
     N = len(inps)
     if N == 0:
         return []
@@ -259,7 +273,8 @@ def _run_inference_stream(model, processor, tokenizer, inps, image_paths_list, c
         outs = model.generate_stream(prepared.column(0), prepared.column(1), slots=slots, do_sample=do_sample, temperature=temperature,
                                      max_new_tokens=max_new_tokens, stopping_criteria=prepared.column(2),
                                      **({"prefix_keys": Keys()} if prefix_cache else {}), **({"guides": guides} if guides is not None else {}),
-                                     **({"share_prefix": True} if share_prefix else {}), **({"logprobs": True} if logprobs else {}))
+                                     **({"share_prefix": True} if share_prefix else {}), **({"logprobs": True} if logprobs else {}),
+                                     **(rule_kw or {}))
     if logprobs:
         return [(_text(tokenizer, o[0][n_prompt[i]:]), _confidence(model, tokenizer, o[0][n_prompt[i]:], o[1])) for i, o in enumerate(outs)]
     return [tokenizer.decode(o[n_prompt[i]:]).replace("</s>", "").strip() for i, o in enumerate(outs)]
@@ -292,7 +307,8 @@ def _record(example, response, dataset):
 
 
 def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronological_prefix, conv_mode, temperature,
-                  max_new_tokens, batch_size=1, continuous=False, prefix_cache=False, guide=None, share_prefix=False, logprobs=False):
+                  max_new_tokens, batch_size=1, continuous=False, prefix_cache=False, guide=None, share_prefix=False, logprobs=False,
+                  repetition_penalty=None, no_repeat_ngram_size=None):
     """Dataset loop with the bookkeeping the metrics need (inference.py:88-137): response / ground truth / task per example,
     the example's polygon when it has one, and the integer boxes quoted in the question and in the reference answer.
     batch_size (extra trailing keyword, default 1 = the reference's loop): answer that many consecutive examples per
@@ -308,8 +324,13 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
     batch_size > 1 take no guide (ValueError).
     logprobs=True (extra trailing keyword): every record gains `confidence` (exp of the mean token log-probability of the answer) and
     `box_confidences` ([[box, score], ...] for the boxes of the response; teochat_amd/confidence.py), at batch_size 1, in groups and
-    continuous alike.  The metrics functions do not read the two keys."""
+    continuous alike.  The metrics functions do not read the two keys.
+    repetition_penalty / no_repeat_ngram_size (extra trailing keywords): the logit rules of generate() (batch_size 1) or of
+    generate_stream() (continuous=True); groups of a fixed batch_size > 1 take none (ValueError)."""
     lp_kw = {"logprobs": True} if logprobs else {}
+    rule_kw = {k: v for k, v in (("repetition_penalty", repetition_penalty), ("no_repeat_ngram_size", no_repeat_ngram_size)) if v is not None}
+    if rule_kw and not continuous and batch_size != 1:
+        raise ValueError("repetition_penalty / no_repeat_ngram_size need batch_size=1 or continuous=True")
 
     def record(example, response):
         if not logprobs:
@@ -345,7 +366,7 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
                                         max_new_tokens=max_new_tokens, continuous=True, slots=int(batch_size),
                                         **({"prefix_cache": True} if prefix_cache else {}),
                                         **({"share_prefix": True} if share_prefix else {}),
-                                        **({"guides": Field(guide_of)} if guide is not None else {}), **lp_kw)
+                                        **({"guides": Field(guide_of)} if guide is not None else {}), **lp_kw, **rule_kw)
         return [record(dataset[i], r) for i, r in enumerate(responses)]
     if batch_size == 1:
         for example in dataset:
@@ -353,7 +374,7 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
                                             conv_mode=conv_mode, timestamps=example["timestamp"], prompt_strategy=prompt_strategy,
                                             chronological_prefix=chronological_prefix, temperature=temperature,
                                             max_new_tokens=max_new_tokens, **({"guide": guide_of(example)} if guide is not None else {}),
-                                            **({"return_logprobs": True} if logprobs else {}))
+                                            **({"return_logprobs": True} if logprobs else {}), **rule_kw)
             outputs.append(record(example, response))
         return outputs
     group = []

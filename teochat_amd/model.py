@@ -53,6 +53,29 @@ def check_logprob_args(logprobs, top_logprobs, prompt_lookup_num_tokens=None):
     return k
 
 
+RULE_KEYWORDS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "suppress_tokens")
+
+
+def check_rule_kwargs(kwargs, vocab=None, batch=False):
+    """The logit rules of a generate() / generate_batch() / generate_stream() call (include/teo_hip_rules.h): check_rule_args' tuple, or
+    None when the four keywords are unset or neutral.  Refuses, before the engine is touched, what has no ruled form."""
+    from .decode_host import check_rule_args, rule_args_ban
+    rules = check_rule_args(*(kwargs.get(k) for k in RULE_KEYWORDS), vocab=vocab)
+    if rules is None:
+        return None
+    named = ", ".join(k for k in RULE_KEYWORDS if kwargs.get(k) is not None)
+    if kwargs.get("prompt_lookup_num_tokens"):
+        raise ValueError(f"{named} is not combined with prompt_lookup_num_tokens: the speculative verify step has no form with logit rules")
+    if batch:
+        raise ValueError(f"{named} applies to one conversation in generate() and not to generate_batch(): generate_stream() applies the "
+                         f"rules to any number of requests")
+    if rule_args_ban(rules) and (kwargs.get("guide") is not None or kwargs.get("guides") is not None):
+        raise ValueError("no_repeat_ngram_size, min_new_tokens and suppress_tokens are not combined with a guide: together they can leave "
+                         "a state without an allowed token, which the guide's fallback does not see (repetition_penalty removes no token "
+                         "and is allowed)")
+    return rules
+
+
 def _pack_logprobs(entries, k):
     """[(logprobs [n_b], top ids [n_b, k] or None, top logprobs or None)] -> padded [B, n], [B, n, k], [B, n, k] (NaN / -1 behind a row's end)"""
     n = max(int(e[0].numel()) for e in entries)
@@ -538,17 +561,20 @@ class LlavaLlamaForCausalLM:
         # one engine phase around the whole call: tower, projector, splice, prefill and the decode chunks run back to back on the
         # engine stream with a single hand-over to the caller's stream at the end (no stream edges between the pieces)
         check_logprob_args(kwargs.get("logprobs"), kwargs.get("top_logprobs"), kwargs.get("prompt_lookup_num_tokens"))
+        ids = args[0] if args else kwargs.get("input_ids")
+        check_rule_kwargs(kwargs, batch=ids is not None and ids.dim() == 2 and ids.shape[0] != 1)
         with self.engine.phase():
             try:
                 return self._generate(*args, **kwargs)
             finally:
-                self.engine.guide_end()           # a guide and the recorder arm the engine's steps for this call only
+                self.engine.guide_end()           # a guide, the recorder and the rules arm the engine's steps for this call only
                 self.engine.logprobs_end()
+                self.engine.rules_end()
 
     def _generate(self, input_ids=None, images=None, do_sample=None, temperature=None, top_k=None, top_p=None,
                   max_new_tokens=20, use_cache=True, stopping_criteria=None, eos_token_id="config", attention_mask=None,
                   generator=None, chunk=16, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, prefix_key=None, guide=None, logprobs=False,
-                  top_logprobs=0, **kwargs):
+                  top_logprobs=0, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, suppress_tokens=None, **kwargs):
         """Greedy or sampled (temperature / top-k, device sampler) decoding of ONE sequence; the loop is device-resident
         and replayed from a hipGraph.
 
@@ -581,6 +607,15 @@ class LlavaLlamaForCausalLM:
         device (include/teo_hip_logprob.h); the first token's entry comes from the prefill logits.  Under a guide the row is the masked
         one, so the value is the probability AMONG THE TOKENS THE GUIDE ALLOWED.  With the keyword unset nothing changes.
 
+        repetition_penalty=p, no_repeat_ngram_size=n, min_new_tokens=m, suppress_tokens=[ids] (HF's keywords and semantics; one
+        conversation, not with prompt_lookup_num_tokens; None / 1.0 / 0 / [] = off): logit rules over the prompt ids as passed (a -200
+        sentinel is an ordinary id that addresses no logit) followed by the tokens emitted so far, applied by one more launch between each
+        step's lm_head and its tail (include/teo_hip_rules.h) -- before the guide's mask, argmax or the sampler, and before the recorder,
+        so engine.d_logits and `logprobs` hold the processed row.  The first token goes through the same kernel on the prefill row.
+        min_new_tokens bans `eos_token_id` only.  The three banning rules are not combined with a guide; repetition_penalty is.  A row
+        left without a finite logit selects what the tail selects there (greedy: token 0).  `last_generation_stats` gains the rules in
+        force.  With the four keywords unset nothing is allocated and the existing graphs replay.
+
         Returns int64 [1, n_prompt + n_generated]; the prompt part still contains the -200 sentinels, as with the
         reference (eval/inference.py:75 slices at input_ids.shape[1]).  `eos_token_id=None` disables EOS stopping.
         """
@@ -593,6 +628,9 @@ class LlavaLlamaForCausalLM:
         self.last_generation_stats = None
         K = int(prompt_lookup_num_tokens or 0)
         top_n = check_logprob_args(logprobs, top_logprobs, K)
+        rules = check_rule_kwargs(dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                       min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, prompt_lookup_num_tokens=K, guide=guide),
+                                  vocab=self.engine.cfg.vocab_size, batch=input_ids.shape[0] != 1)
         if K and prefix_key is not None:
             raise ValueError("prefix_key is not combined with prompt_lookup_num_tokens")
         record, self._prefix_record = getattr(self, "_prefix_record", None), None          # any generate() call forgets it
@@ -682,6 +720,13 @@ class LlavaLlamaForCausalLM:
                 self.last_generation_stats = dict(prefix_rows_reused=reuse[1], prefill_rows=int(embeds.shape[1]))
                 if row_map is not None:             # (key, ids, rows per id, rows written by prefill, the cache's epoch)
                     self._prefix_record = (prefix_key, ids_t, row_map, eng.cache_len, eng.cache_epoch)
+        if rules is not None:
+            # the rules' state starts from the prompt ids as passed; the first token comes from the prefill row through the same kernel
+            eng.rules_begin(1, rules, eos_ids=[eos_token_id] if eos_token_id is not None else [])
+            eng.rules_seed(0, input_ids[0])
+            logits = logits.contiguous()
+            eng.rules_first(logits[0])
+            self.last_generation_stats = dict(self.last_generation_stats or {}, **eng.rules_in_force(), suppress_tokens=len(rules[3]))
         if guide is not None:
             eng.guide_begin(guide)
             logits = logits.contiguous()
@@ -851,6 +896,8 @@ class LlavaLlamaForCausalLM:
     @torch.no_grad()
     def generate_batch(self, *args, **kwargs):
         check_logprob_args(kwargs.get("logprobs"), kwargs.get("top_logprobs"))
+        check_rule_kwargs(kwargs, batch=True)     # (any rule is refused here; neutral values pass and are dropped)
+        kwargs = {k: v for k, v in kwargs.items() if k not in RULE_KEYWORDS}
         with self.engine.phase():
             return self._generate_batch(*args, **kwargs)
 
@@ -984,12 +1031,14 @@ class LlavaLlamaForCausalLM:
     @torch.no_grad()
     def generate_stream(self, *args, **kwargs):
         check_logprob_args(kwargs.get("logprobs"), kwargs.get("top_logprobs"))
+        check_rule_kwargs(kwargs)
         with self.engine.phase():
             return self._generate_stream(*args, **kwargs)
 
     def _generate_stream(self, input_ids_list, images_list=None, slots=8, max_new_tokens=20, do_sample=False, temperature=None,
                          top_k=None, top_p=None, stopping_criteria=None, eos_token_id="config", generator=None, chunk=16, prefix_keys=None,
-                         min_prefix_rows=64, guides=None, share_prefix=False, logprobs=False, top_logprobs=0):
+                         min_prefix_rows=64, guides=None, share_prefix=False, logprobs=False, top_logprobs=0, repetition_penalty=None,
+                         no_repeat_ngram_size=None, min_new_tokens=None, suppress_tokens=None):
         """Answer N requests (any N >= 1) over `slots` <= 16 conversation slots of the batched decode step: a slot whose request has
         finished parks -- the attention kernels skip it -- and is refilled with the next request, so a step's work follows the requests
         that are still being answered instead of the longest answer of a fixed group (teochat_amd/stream.py).
@@ -1029,7 +1078,13 @@ class LlavaLlamaForCausalLM:
 
         logprobs=True, top_logprobs=k (0..8): returns per request (ids, logprobs [n_new], top ids [n_new, k] or None, top logprobs or None)
         instead of the ids tensor; the values are generate()'s (log softmax of the row each token was selected from, the masked row under
-        a guide), recorded by one more launch behind each stream step, plain, guided or shared (include/teo_hip_logprob.h)."""
+        a guide), recorded by one more launch behind each stream step, plain, guided or shared (include/teo_hip_logprob.h).
+
+        repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens: generate()'s logit rules, ONE setting for every request
+        of the call (as the sampler's); each slot keeps its own seen-flags and history, seeded with its request's ids whenever it is
+        refilled, so a request's answer does not depend on the slot it landed in or on that slot's earlier occupant.  One more launch in
+        front of each stream step's tail, plain, guided, shared or recorded (include/teo_hip_rules.h).  The banning rules are not combined
+        with `guides`.  The stats gain the rules in force."""
         from .decode_host import logprob_rows
         from .stream import request_seed, run_stream
         top_n = check_logprob_args(logprobs, top_logprobs)
@@ -1041,6 +1096,9 @@ class LlavaLlamaForCausalLM:
             raise ValueError(f"slots {slots} outside 1..{L.MAX_DECODE_BATCH}")
         if share_prefix and prefix_keys is None:
             raise ValueError("share_prefix needs prefix_keys (only forked rows are known to be shared)")
+        rules = check_rule_kwargs(dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                       min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, guides=guides),
+                                  vocab=self.engine.cfg.vocab_size)
         if eos_token_id == "config":
             eos_token_id = self._config_eos()
         max_new = [int(max_new_tokens)] * N if isinstance(max_new_tokens, int) else [int(m) for m in max_new_tokens]
@@ -1071,6 +1129,7 @@ class LlavaLlamaForCausalLM:
         dec.share_prefix(bool(share_prefix))
         if logprobs:
             dec.logprobs_begin(top_n)
+        dec.rules_begin(slots, rules, eos_ids=[eos_token_id] if eos_token_id is not None else [])
         first_lp = {}                             # request -> its first token's entry (from the prefill logits)
         ids_of, crits_of = {}, {}                 # the requests in flight (and, for ids, the finished ones: a few integers each)
         dev_stop = {"ids": None, "off": False}    # the device stop: one id sequence shared by every request admitted so far, or off
@@ -1127,6 +1186,12 @@ class LlavaLlamaForCausalLM:
 
         def first_tokens(reqs, logits, lens, slot_list):
             out = []
+            if rules is not None:
+                # a refilled slot starts from its request's ids and inherits nothing; the first token takes the rules on its prefill row
+                logits = logits.contiguous()
+                for b, r in enumerate(reqs):
+                    dec.rules_seed(slot_list[b], ids_of[r])
+                    dec.rules_first(logits[b], slot_list[b])
             if gset is not None:
                 # the first token of a request comes from its prefill logits: masked by its guide's start state, and the slot starts
                 # from the successor (a slot's earlier occupant left its own last state behind)
@@ -1218,8 +1283,11 @@ class LlavaLlamaForCausalLM:
             stats.update(guide_states=int(gset.n_states), guide_table_bytes=int(gset.table_bytes))
         if share_prefix:
             stats.update({k: int(dec.stats()[k]) for k in ("shared_steps", "shared_rows_skipped")})
+        if rules is not None:
+            stats.update(dec.rules_in_force(), suppress_tokens=len(rules[3]))
         dec.set_guide(None)
         dec.share_prefix(False)
+        dec.rules_end()
         self.last_generation_stats = stats
         if logprobs:
             dec.logprobs_end()

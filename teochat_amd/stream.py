@@ -18,7 +18,7 @@ import torch
 
 from . import _lib as L
 from .batch import BatchDecoder
-from .decode_host import SEED_MASK, StepGraphs, _p, arm_sampler, logprob_graph_key, run_prefill
+from .decode_host import SEED_MASK, LogitRules, StepGraphs, _p, arm_sampler, logprob_graph_key, rules_graph_key, run_prefill
 from .engine import guide_graph_key
 
 SEED_STRIDE = 0x9E3779B97F4A7C15              # request i draws from the Philox stream seeded (base + i * SEED_STRIDE) mod 2^63
@@ -105,7 +105,7 @@ class ShareTable:
             assert self.rows[s] >= 0 and (top != s or self.rows[s] == 0) and (top == s or self.rows[s] > 0), (s, self.lead, self.rows)
 
 
-class StreamDecoder(StepGraphs):
+class StreamDecoder(StepGraphs, LogitRules):
     """`slots` conversation slots over one engine.  batch_decoder: a BatchDecoder of that engine with B == slots whose caches, per-slot
     descriptors and tiled weight copies are borrowed (no second copy of the weights; its own begin()/steps() state is invalidated by a
     refill here); left out, one is created and owned."""
@@ -351,7 +351,29 @@ class StreamDecoder(StepGraphs):
             skip = self.share.skipped(chunk, self.live)
         rec = bd._rec
         with eng.phase() as st:
-            if rec is not None:
+            if self._rules is not None:
+                # whichever step the branches below would run -- plain, guided, shared, with or without the recorder -- with the rules
+                # launch in front of its tail (include/teo_hip_rules.h): one entry point, one graph of its own
+                if skip and self.share.dirty:
+                    self.d_share_lead.copy_(torch.tensor(self.share.lead, dtype=torch.int32))
+                    self.d_share_rows.copy_(torch.tensor(self.share.rows, dtype=torch.int32))
+                    self.share.dirty = False
+                lr = self._rules
+                g_ = C.byref(gd) if gd is not None else None
+                sh_ = C.byref(self._share) if skip else None
+                r_, l_ = (C.byref(rec) if rec is not None else None), C.byref(lr)
+                key = rules_graph_key(lr, logprob_graph_key(rec) if rec is not None else None, ws.data_ptr(),
+                                      guide_graph_key(gd, ws) if gd is not None else None, bool(skip))
+                self.replay_or_step(eng.stream, key, n, use_graph,
+                                    lambda out: L.check(self.lib.teo_llama_decode_stream_graph_create_ruled(d, s_, sh_, g_, r_, l_, _p(ws), ws.numel(),
+                                                                                                            st, out),
+                                                        "teo_llama_decode_stream_graph_create_ruled"),
+                                    lambda: L.check(self.lib.teo_llama_decode_stream_step_ruled(d, s_, sh_, g_, r_, l_, _p(ws), ws.numel(), st),
+                                                    "teo_llama_decode_stream_step_ruled"), slot=self.RULED_SLOT)
+                if skip:
+                    self._stats["shared_steps"] += n
+                    self._stats["shared_rows_skipped"] += n * skip
+            elif rec is not None:
                 # whichever step the branches below would run -- plain, guided, shared -- with the recorder behind it
                 # (include/teo_hip_logprob.h): one entry point, one graph of its own whose key says which step it holds
                 if skip and self.share.dirty:
