@@ -338,6 +338,29 @@ _SIGS_RULES = {
                                                              C.POINTER(C.c_void_p)]),
 }
 EXPORTS_RULES = tuple(_SIGS_RULES.keys())
+
+
+# include/teo_hip_beam.h: beam search for one conversation in the device decode loop, an eighth header of the same library
+class BeamState(C.Structure):
+    _fields_ = [("num_beams", C.c_int), ("max_new", C.c_int), ("eos", C.c_longlong), ("early_stopping", C.c_int),
+                ("length_penalty", C.c_float), ("d_len_norm", C.c_void_p), ("d_scores", C.c_void_p), ("d_parent", C.c_void_p),
+                ("d_token", C.c_void_p), ("d_pos", C.c_void_p), ("d_hist_token", C.c_void_p), ("d_hist_parent", C.c_void_p),
+                ("d_fin_score", C.c_void_p), ("d_fin_step", C.c_void_p), ("d_fin_parent", C.c_void_p), ("d_fin_token", C.c_void_p),
+                ("d_fin_count", C.c_void_p), ("d_step", C.c_void_p), ("d_done", C.c_void_p), ("d_cand_score", C.c_void_p),
+                ("d_cand_token", C.c_void_p), ("d_best_score", C.c_void_p), ("d_best_flat", C.c_void_p)]
+
+
+_SIGS_BEAM = {
+    "teo_beam_state_sizeof": (C.c_size_t, []),
+    "teo_beam_select": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.POINTER(BeamState), C.c_void_p]),
+    "teo_kv_reorder_tail": (C.c_int, [C.POINTER(LlamaDesc), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "teo_llama_decode_beam_step": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeStreamState), C.POINTER(Share), C.POINTER(BeamState),
+                                             C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "teo_llama_decode_beam_graph_create": (C.c_int, [C.POINTER(LlamaDesc), C.POINTER(DecodeStreamState), C.POINTER(Share),
+                                                     C.POINTER(BeamState), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                     C.POINTER(C.c_void_p)]),
+}
+EXPORTS_BEAM = tuple(_SIGS_BEAM.keys())
 _lib = None
 
 
@@ -359,7 +382,7 @@ def load():
     except OSError as e:
         raise TeoLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_PREFIX.items()) + list(_SIGS_SCORE.items()) + list(_SIGS_GUIDE.items()) \
-            + list(_SIGS_SHARE.items()) + list(_SIGS_LOGPROB.items()) + list(_SIGS_RULES.items()):
+            + list(_SIGS_SHARE.items()) + list(_SIGS_LOGPROB.items()) + list(_SIGS_RULES.items()) + list(_SIGS_BEAM.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -385,6 +408,9 @@ def load():
     if lib.teo_logit_rules_sizeof() != C.sizeof(LogitRules):
         raise TeoLibraryError(f"struct layout mismatch: teo_logit_rules is {lib.teo_logit_rules_sizeof()} bytes in {LIB_PATH}, "
                               f"{C.sizeof(LogitRules)} in this binding; rebuild")
+    if lib.teo_beam_state_sizeof() != C.sizeof(BeamState):
+        raise TeoLibraryError(f"struct layout mismatch: teo_beam_state is {lib.teo_beam_state_sizeof()} bytes in {LIB_PATH}, "
+                              f"{C.sizeof(BeamState)} in this binding; rebuild")
     _lib = lib
     return lib
 

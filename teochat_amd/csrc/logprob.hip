@@ -1,82 +1,25 @@
 // Token log-probabilities (include/teo_hip_logprob.h): one device body over a row of fp32 logits, its two launches (explicit rows, and
 // the recorder over a decode loop's state) and the entry points of the sixth header.  The steps themselves are runtime.hip's, untouched:
 // a _logp step enqueues the step it stands in for and then the recorder.
-#include <limits.h>
-
 #include "ops.h"
 #include "runtime.h"
 #include "logprob_dev.h"
+#include "logprob_body.h"
 
 namespace teo {
 
-// Every entry of the row, NaN read as -inf, handed to f(value, index).  Thread t takes the quads t, t + 1024, ... (four consecutive
-// entries each) by ascending index and then the entries behind the last whole quad: one 16-byte load per quad where the row is aligned
-// for it, four scalar loads elsewhere -- the SAME entries in the SAME order in both forms, so a row's results do not depend on where
-// it lies.
-template <typename F>
-__device__ __forceinline__ void logprob_visit(const float* __restrict__ row, int vocab, F f) {
-    const int nq = vocab >> 2;
-    auto take = [&](float v, int i) { f(v == v ? v : -INFINITY, i); };
-    if ((reinterpret_cast<uintptr_t>(row) & 15) == 0) {
-        for (int q = threadIdx.x; q < nq; q += 1024) {
-            const float4 v = *reinterpret_cast<const float4*>(row + 4 * q);
-            take(v.x, 4 * q); take(v.y, 4 * q + 1); take(v.z, 4 * q + 2); take(v.w, 4 * q + 3);
-        }
-    } else {
-        for (int q = threadIdx.x; q < nq; q += 1024) {
-            const float a = row[4 * q], b = row[4 * q + 1], c = row[4 * q + 2], d = row[4 * q + 3];
-            take(a, 4 * q); take(b, 4 * q + 1); take(c, 4 * q + 2); take(d, 4 * q + 3);
-        }
-    }
-    for (int i = (nq << 2) + threadIdx.x; i < vocab; i += 1024) take(row[i], i);
-}
-
-// The best entry by (value descending, index ascending) among those BEHIND (pv, pi) in that order (first: among all), for every thread of
-// the 1024-thread workgroup.  Exact comparisons only, so the result does not depend on the reduction's shape.  (-inf, INT_MAX): none left.
-__device__ __forceinline__ void logprob_next_best(const float* __restrict__ row, int vocab, bool first, float pv, int pi, float* red_v,
-                                                  int* red_i, float& best, int& bi) {
-    best = -INFINITY; bi = INT_MAX;
-    logprob_visit(row, vocab, [&](float v, int i) {
-        const bool behind = first || v < pv || (v == pv && i > pi);
-        if (behind && (v > best || (v == best && i < bi))) { best = v; bi = i; }
-    });
-    wave_argmax(best, bi);
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    __syncthreads();                                // (the previous pass's readers are done with red_v / red_i)
-    if (l == 0) { red_v[w] = best; red_i[w] = bi; }
-    __syncthreads();
-    best = red_v[0]; bi = red_i[0];
-#pragma unroll
-    for (int j = 1; j < 16; ++j) {
-        const float ov = red_v[j];
-        const int oi = red_i[j];
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-}
-
 // The device body, called by a whole 1024-thread workgroup: *out_lp = log softmax(row)[tok]; the k best entries into top_ids / top_lp
 // [0, k).  Thread 0 stores (plain vector stores).
-//   pass 1   m and its index: the first of the top entries
-//   pass 2   S = sum exp(x_i - m): per thread by ascending index, wave butterfly (6 levels), tree over the 16 wave sums (4 levels)
-//   pass 3.. the remaining top entries, one pass each
-// expf / logf, no fast forms.  Error: include/teo_hip_logprob.h.
+//   pass 1, 2  logprob_norm (logprob_body.h): m and its index -- the first of the top entries -- and log S
+//   pass 3..   the remaining top entries, one pass each
+// Error: include/teo_hip_logprob.h.
 __device__ __forceinline__ void logprob_row(const float* __restrict__ row, int vocab, long long tok, int k, float* out_lp,
                                             long long* top_ids, float* top_lp) {
     __shared__ float red_v[16];
     __shared__ int red_i[16];
     __shared__ float red_s[16];
-    float m; int mi;
-    logprob_next_best(row, vocab, true, 0.f, 0, red_v, red_i, m, mi);
-    const bool finite = m > -INFINITY && m < INFINITY;          // uniform over the workgroup
-    float logS = 0.f;
-    if (finite) {
-        float s = 0.f;
-        logprob_visit(row, vocab, [&](float v, int) { s += expf(v - m); });
-        s = wave_sum(s);
-        if ((threadIdx.x & 63) == 0) red_s[threadIdx.x >> 6] = s;
-        __syncthreads();
-        logS = logf(group_sum<16>(red_s[threadIdx.x & 15]));
-    }
+    float m, logS; int mi; bool finite;                          // finite: uniform over the workgroup
+    logprob_norm(row, vocab, red_v, red_i, red_s, m, mi, logS, finite);
     if (threadIdx.x == 0) {
         float lp = -INFINITY;
         if (finite && tok >= 0 && tok < vocab) {
@@ -89,7 +32,7 @@ __device__ __forceinline__ void logprob_row(const float* __restrict__ row, int v
     for (int j = 0; j < k; ++j) {
         if (j > 0) {
             float nv; int ni;
-            logprob_next_best(row, vocab, false, pv, pi, red_v, red_i, nv, ni);
+            logprob_next_best(row, vocab, false, pv, pi, red_v, red_i, nv, ni, [](float x) { return x; });
             pv = nv; pi = ni;
         }
         if (threadIdx.x == 0) {

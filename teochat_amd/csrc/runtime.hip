@@ -9,6 +9,7 @@
 #include "share_dev.h"
 #include "logprob_dev.h"
 #include "rules_dev.h"
+#include "beam_dev.h"
 
 namespace teo {
 struct Carver {
@@ -703,6 +704,36 @@ int llama_decode_stream_step(const teo_llama_desc* d, const teo_decode_stream_st
     return llama_decode_stream_step(d, s, ws, ws_bytes, st, nullptr);
 }
 
+// ---- beam step (include/teo_hip_beam.h): the stream step's layers under the share table, then the selection, the reorder of the KV
+// tails behind the prompt and the embedding of the B new tokens.  The selection advances (or parks) d_pos, so the reorder's rows end at
+// the advanced position it reads from d_pos[0], and a parked state moves nothing.
+int llama_decode_beam_step(const teo_llama_desc* d, const teo_decode_stream_state* s, const teo_share* sh, const teo_beam_state* bm,
+                           int prompt_rows, void* ws, size_t ws_bytes, hipStream_t st) {
+    const char* who = "teo_llama_decode_beam_step";
+    const int B = s->batch;
+    const DecodeBatchWs w = decode_batch_carve(d, B, ws, ws_bytes);
+    if (w.total > ws_bytes) {
+        set_error("%s: workspace %zu < %zu", who, ws_bytes, w.total);
+        return TEO_ERR_WORKSPACE;
+    }
+    const int dt = d->dtype;
+    const int H = d->heads, Hk = d->kv_heads, hd = d->head_dim;
+    AttnBatch bt;
+    bt.batch = B; bt.q_stride = (H + 2 * Hk) * hd; bt.cache_stride = s->cache_stride; bt.o_stride = (long long)H * hd;
+    auto attend = [&](int l) {
+        return attn_decode_shared(w.qkv, d->k_cache[l], d->v_cache[l], d->vt_cache[l], d->rope_cos, d->rope_sin, w.attn, w.part, s->d_pos,
+                                  d->max_seq, H, Hk, hd, 1.0f / sqrtf((float)hd), dt, st, bt, sh->d_lead, sh->d_rows);
+    };
+    bool skinny = false;
+    const BatchLoopOpts o = {B, s->w_tiled != 0, s->gateup_block8 != 0, s->w_mxfp4 != 0};
+    TEO_TRY(decode_batch_layers(d, o, w, s->d_logits, attend, &skinny, who, st));
+    prof_class(TEO_PROF_TAIL);
+    TEO_TRY(beam_select(s->d_logits, d->vocab, B, d->vocab, bm, st));
+    TEO_TRY(kv_reorder_tail(d, bm->d_parent, B, prompt_rows, prompt_rows + bm->max_new, s->d_pos, s->cache_stride, st));
+    if (skinny) return embed_token_emit(s->d_token, d->embed, w.h, d->hidden, dt, st, B, d->in_norm_w[0], w.hg, w.ssq, w.nparts);
+    return embed_token(s->d_token, d->embed, w.h, d->hidden, dt, st, B);
+}
+
 // row `slot` of the residual stream <- embed[d_token[slot]] (skinny path: also layer 0's norm inputs for that row).  No other row is
 // touched: the previous step's tail has prepared theirs.
 int llama_decode_stream_arm(const teo_llama_desc* d, const teo_decode_stream_state* s, int slot, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -945,6 +976,11 @@ int decode_stream_graph_create_ruled(const teo_llama_desc* d, const teo_decode_s
         if (!rec) return (int)TEO_OK;
         return logprob_record(s->d_logits, d->vocab, s->batch, d->vocab, s->d_out_tokens, s->out_stride, s->d_out_count, rec, st);
     }, out);
+}
+
+int decode_beam_graph_create(const teo_llama_desc* d, const teo_decode_stream_state* s, const teo_share* sh, const teo_beam_state* bm,
+                             int prompt_rows, void* ws, size_t ws_bytes, hipStream_t st, teo_graph** out) {
+    return capture_graph(st, [&]() { return llama_decode_beam_step(d, s, sh, bm, prompt_rows, ws, ws_bytes, st); }, out);
 }
 
 int llama_verify_step_profile(const teo_llama_desc* d, const teo_verify_state* s, void* ws, size_t ws_bytes, float* ms_out, int* count_out,

@@ -54,7 +54,7 @@ def eval(dataset_name, model_path, model_base, load_8bit=False, load_4bit=False,
          out_name=None, out_dir=None, prompt_strategy=None, chronological_prefix=True, conv_mode="v1", device="cuda",
          force_rerun=False, temperature=0.2, max_new_tokens=256, dataset=None, model_bundle=None, batch_size=1,
          continuous=False, prefix_cache=False, guide=None, share_prefix=False, logprobs=False, repetition_penalty=None,
-         no_repeat_ngram_size=None):
+         no_repeat_ngram_size=None, num_beams=None):
     """Run (or re-use) the model's answers on one TEOChatlas evaluation split and print / return its task metrics.
     Extra keywords (not in the reference): `dataset` = examples to use instead of the hub download, `model_bundle` =
     (tokenizer, model, processor) already loaded, `batch_size` = examples answered per generation (1 = the reference's loop;
@@ -66,7 +66,8 @@ def eval(dataset_name, model_path, model_base, load_8bit=False, load_4bit=False,
     (guide.named_guide; batch_size 1 or continuous), so that it parses as a list of boxes,
     `logprobs` = every record gains `confidence` and `box_confidences` (inference.run_inference(logprobs=True)); no metric reads them,
     `repetition_penalty` / `no_repeat_ngram_size` = the logit rules of generate() / generate_stream() (include/teo_hip_rules.h; batch_size 1
-    or continuous)."""
+    or continuous),
+    `num_beams` = beam search of generate() (include/teo_hip_beam.h; batch_size 1 without continuous)."""
     print("Arguments passed to eval:")
     for k, v in (("dataset_name", dataset_name), ("model_path", model_path), ("model_base", model_base), ("out_name", out_name),
                  ("out_dir", out_dir), ("prompt_strategy", prompt_strategy), ("chronological_prefix", chronological_prefix),
@@ -100,7 +101,8 @@ def eval(dataset_name, model_path, model_base, load_8bit=False, load_4bit=False,
                                 **({"continuous": True} if continuous else {}), **({"prefix_cache": True} if prefix_cache else {}),
                                 **({"share_prefix": True} if share_prefix else {}), **({"logprobs": True} if logprobs else {}),
                                 **({"repetition_penalty": repetition_penalty} if repetition_penalty is not None else {}),
-                                **({"no_repeat_ngram_size": no_repeat_ngram_size} if no_repeat_ngram_size is not None else {}), **extra)
+                                **({"no_repeat_ngram_size": no_repeat_ngram_size} if no_repeat_ngram_size is not None else {}),
+                                **({"num_beams": num_beams} if num_beams is not None else {}), **extra)
         print(f"Saving outputs to {out_path}")
         with open(out_path, "w") as f:
             json.dump(outputs, f, indent=4)
@@ -151,6 +153,8 @@ _CLI = (
     # not in the reference: logit rules inside the device decode loop (include/teo_hip_rules.h), HF's keywords of the same names
     ("repetition_penalty", dict(type=float, default=argparse.SUPPRESS)),
     ("no_repeat_ngram_size", dict(type=int, default=argparse.SUPPRESS)),
+    # not in the reference: beam search inside the device decode loop (include/teo_hip_beam.h), HF's keyword of the same name
+    ("num_beams", dict(type=int, default=argparse.SUPPRESS)),
 )
 
 

@@ -38,13 +38,15 @@ def build_prompt(inp, image_paths, conv_mode="v1", prompt_strategy="interleave",
 def run_inference_single(model, processor, tokenizer, inp, image_paths, conv_mode="v1", timestamps=[],
                          prompt_strategy="interleave", chronological_prefix=True, temperature=0.2, max_new_tokens=256,
                          do_sample=True, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, guide=None, repetition_penalty=None,
-                         no_repeat_ngram_size=None, return_logprobs=False):
+                         no_repeat_ngram_size=None, num_beams=None, return_logprobs=False):
     """guide (extra trailing keyword): a teochat_amd.guide.TokenGuide over the tokenizer's vocabulary -- the answer is generated under it
     (model.generate(guide=...)); None: the keyword is not passed on.
     return_logprobs=True (extra trailing keyword): returns (text, {"logprobs": [...], "confidence": float, "box_confidences": [...]}) --
     model.generate(logprobs=True) and teochat_amd/confidence.py over the generated tokens, the stop token included.
     repetition_penalty / no_repeat_ngram_size (extra trailing keywords): model.generate's logit rules (include/teo_hip_rules.h); None: the
-    keyword is not passed on."""
+    keyword is not passed on.
+    num_beams (extra keyword in front of return_logprobs): model.generate's beam search (include/teo_hip_beam.h); above 1 it forces do_sample=False, None:
+    the keyword is not passed on."""
     if len(timestamps) > 0:
         order = sorted(range(len(image_paths)), key=lambda i: datetime.strptime(timestamps[i], "%Y-%m-%d"))
         image_paths = [image_paths[i] for i in order]
@@ -68,6 +70,10 @@ def run_inference_single(model, processor, tokenizer, inp, image_paths, conv_mod
             spec["repetition_penalty"] = repetition_penalty
         if no_repeat_ngram_size is not None:
             spec["no_repeat_ngram_size"] = no_repeat_ngram_size
+        if num_beams is not None:
+            spec["num_beams"] = num_beams
+            if int(num_beams) > 1:
+                do_sample = False
         output_ids = model.generate(input_ids=input_ids, images=frames, do_sample=do_sample, temperature=temperature,
                                     max_new_tokens=max_new_tokens, use_cache=True, stopping_criteria=[stopping], **spec)
     if return_logprobs:
@@ -308,7 +314,7 @@ def _record(example, response, dataset):
 
 def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronological_prefix, conv_mode, temperature,
                   max_new_tokens, batch_size=1, continuous=False, prefix_cache=False, guide=None, share_prefix=False, logprobs=False,
-                  repetition_penalty=None, no_repeat_ngram_size=None):
+                  repetition_penalty=None, no_repeat_ngram_size=None, num_beams=None):
     """Dataset loop with the bookkeeping the metrics need (inference.py:88-137): response / ground truth / task per example,
     the example's polygon when it has one, and the integer boxes quoted in the question and in the reference answer.
     batch_size (extra trailing keyword, default 1 = the reference's loop): answer that many consecutive examples per
@@ -326,7 +332,10 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
     `box_confidences` ([[box, score], ...] for the boxes of the response; teochat_amd/confidence.py), at batch_size 1, in groups and
     continuous alike.  The metrics functions do not read the two keys.
     repetition_penalty / no_repeat_ngram_size (extra trailing keywords): the logit rules of generate() (batch_size 1) or of
-    generate_stream() (continuous=True); groups of a fixed batch_size > 1 take none (ValueError)."""
+    generate_stream() (continuous=True); groups of a fixed batch_size > 1 take none (ValueError).
+    num_beams (extra trailing keyword): beam search of generate() (include/teo_hip_beam.h), batch_size 1 without continuous only."""
+    if num_beams is not None and int(num_beams) > 1 and (continuous or batch_size != 1):
+        raise ValueError("num_beams needs batch_size=1 without continuous (beam search runs one conversation over the batched step's slots)")
     lp_kw = {"logprobs": True} if logprobs else {}
     rule_kw = {k: v for k, v in (("repetition_penalty", repetition_penalty), ("no_repeat_ngram_size", no_repeat_ngram_size)) if v is not None}
     if rule_kw and not continuous and batch_size != 1:
@@ -374,7 +383,8 @@ def run_inference(dataset, model, tokenizer, processor, prompt_strategy, chronol
                                             conv_mode=conv_mode, timestamps=example["timestamp"], prompt_strategy=prompt_strategy,
                                             chronological_prefix=chronological_prefix, temperature=temperature,
                                             max_new_tokens=max_new_tokens, **({"guide": guide_of(example)} if guide is not None else {}),
-                                            **({"return_logprobs": True} if logprobs else {}), **rule_kw)
+                                            **({"return_logprobs": True} if logprobs else {}), **rule_kw,
+                                            **({"num_beams": num_beams} if num_beams is not None else {}))
             outputs.append(record(example, response))
         return outputs
     group = []

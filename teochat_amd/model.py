@@ -574,9 +574,19 @@ class LlavaLlamaForCausalLM:
     def _generate(self, input_ids=None, images=None, do_sample=None, temperature=None, top_k=None, top_p=None,
                   max_new_tokens=20, use_cache=True, stopping_criteria=None, eos_token_id="config", attention_mask=None,
                   generator=None, chunk=16, prompt_lookup_num_tokens=None, max_matching_ngram_size=2, prefix_key=None, guide=None, logprobs=False,
-                  top_logprobs=0, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, suppress_tokens=None, **kwargs):
+                  top_logprobs=0, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, suppress_tokens=None, num_beams=None,
+                  num_return_sequences=None, length_penalty=None, early_stopping=None, return_dict_in_generate=False, **kwargs):
         """Greedy or sampled (temperature / top-k, device sampler) decoding of ONE sequence; the loop is device-resident
         and replayed from a hipGraph.
+
+        num_beams=B (2..16; HF's keyword and semantics, one conversation), num_return_sequences=n <= B, length_penalty (1.0),
+        early_stopping (False / True / "never"): greedy beam search inside the device loop (include/teo_hip_beam.h, teochat_amd/beam.py).
+        The beams are the slots of the batched decode step; each step selects the next beams over B x V accumulated scores and makes
+        every beam's KV tail the tail of the beam it descends from, on the device; the host looks at one flag per chunk of replays.
+        Returns int64 [n, prompt + longest], best first, shorter rows filled with pad_token_id (else EOS); with
+        return_dict_in_generate=True a BeamOutput(sequences, sequences_scores).  `last_generation_stats` = {beam_steps, finished,
+        reorder_rows}.  Not combined with do_sample, a batch, prompt_lookup_num_tokens, guide, logprobs, prefix_key, the logit rules, custom
+        stopping criteria or several distinct stop sequences.  Unset or 1: nothing changes and nothing is allocated.
 
         prompt_lookup_num_tokens=K (1..15; HF's keyword, one conversation only): prompt-lookup speculative decoding -- every pass over the
         weights verifies the pending token and up to K drafts copied from behind the most recent earlier occurrence of the last
@@ -631,6 +641,21 @@ class LlavaLlamaForCausalLM:
         rules = check_rule_kwargs(dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                                        min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, prompt_lookup_num_tokens=K, guide=guide),
                                   vocab=self.engine.cfg.vocab_size, batch=input_ids.shape[0] != 1)
+        from .beam import check_beam_args
+        beam = check_beam_args(getattr(gc, "num_beams", 1) if num_beams is None else num_beams,
+                               getattr(gc, "num_return_sequences", 1) if num_return_sequences is None else num_return_sequences,
+                               getattr(gc, "length_penalty", 1.0) if length_penalty is None else length_penalty,
+                               getattr(gc, "early_stopping", False) if early_stopping is None else early_stopping, do_sample=do_sample)
+        if beam is not None:
+            self._prefix_record = None
+            for given, name in ((input_ids.shape[0] != 1, "a batch of conversations (num_beams applies to one conversation)"),
+                                (K, "prompt_lookup_num_tokens"), (guide is not None, "guide"), (logprobs, "logprobs"),
+                                (prefix_key is not None, "prefix_key"), (rules is not None, "the logit rules (repetition_penalty, "
+                                 "no_repeat_ngram_size, min_new_tokens, suppress_tokens)")):
+                if given:
+                    raise ValueError(f"num_beams is not combined with {name}")
+            return self._generate_beam(input_ids, images, attention_mask, max_new_tokens, eos_token_id, stopping_criteria, chunk, beam,
+                                       return_dict_in_generate)
         if K and prefix_key is not None:
             raise ValueError("prefix_key is not combined with prompt_lookup_num_tokens")
         record, self._prefix_record = getattr(self, "_prefix_record", None), None          # any generate() call forgets it
@@ -819,6 +844,70 @@ class LlavaLlamaForCausalLM:
             if stop_here:
                 break
         return finish(new_tokens)
+
+    def beam_decoder(self, num_beams, max_new=1024):
+        """the beam state over the model's B-slot stream decoder (its caches and weight copies: no second set)"""
+        from .beam import BeamDecoder
+        dec = self.stream_decoder(num_beams, max_new)
+        cur = getattr(self, "_beam_decoder", None)
+        if cur is None or cur.dec is not dec or cur.cap < max_new:
+            self._beam_decoder = None
+            cur = BeamDecoder(dec, max(int(max_new), dec.max_new))
+            self._beam_decoder = cur
+        return cur
+
+    def _generate_beam(self, input_ids, images, attention_mask, max_new_tokens, eos_token_id, stopping_criteria, chunk, beam,
+                       return_dict):
+        """generate(num_beams=B): see _generate"""
+        from .beam import BeamOutput
+        B, n_ret, lp, es = beam
+        eng = self.engine
+        if eos_token_id == "config":
+            eos_token_id = self._config_eos()
+        # the stop: EOS and the reference's default keyword "</s>" are the same single id; anything else has no form in the device loop
+        cands = []
+        for c in list(stopping_criteria or []):
+            lists = [ids for ids in getattr(c, "keyword_id_lists", []) if ids]
+            if not lists:
+                raise ValueError("num_beams is not combined with custom stopping_criteria: the search stops on one EOS id")
+            cands += lists
+        if eos_token_id is not None:
+            cands.append([int(eos_token_id)])
+        uniq = []
+        for ids in cands:
+            ids = [int(t) for t in ids]
+            if ids not in uniq:
+                uniq.append(ids)
+        if len(uniq) > 1 or (uniq and len(uniq[0]) != 1):
+            raise ValueError(f"num_beams is not combined with several distinct stop sequences or a stop of several ids: {uniq}")
+        eos = uniq[0][0] if uniq else None
+        if max_new_tokens <= 0:
+            return BeamOutput(input_ids, torch.zeros(1)) if return_dict else input_ids
+        if input_ids.shape[1] + max_new_tokens > eng.max_seq:
+            raise ValueError(f"prompt ({input_ids.shape[1]} ids) + max_new_tokens ({max_new_tokens}) exceeds max_seq {eng.max_seq}")
+        (_, _, _, _, embeds, _) = self.prepare_inputs_labels_for_multimodal(input_ids, None, attention_mask, None, None, images)
+        if embeds is None:
+            embeds = self.get_model().embed_tokens(input_ids)
+        if embeds.shape[1] + max_new_tokens > eng.max_seq:
+            raise ValueError(f"prompt ({embeds.shape[1]}) + max_new_tokens ({max_new_tokens}) exceeds max_seq {eng.max_seq}")
+        bm = self.beam_decoder(B, max_new_tokens)
+        try:
+            bm.begin(embeds[0], eos=eos, max_new=max_new_tokens, length_penalty=lp, early_stopping=es)
+            bm.run(chunk)
+            hyps, stats = bm.finish(n_ret)
+        finally:
+            bm.end()
+        self.last_generation_stats = stats
+        pad = getattr(self.config, "pad_token_id", None)
+        fill = (pad or eos) if eos is not None else -1            # HF's fill rule
+        longest = max(len(h) for _, h in hyps)
+        tail = torch.full((len(hyps), longest), int(fill), dtype=input_ids.dtype)
+        for i, (_, h) in enumerate(hyps):
+            tail[i, :len(h)] = torch.tensor(h, dtype=input_ids.dtype)
+        seqs = torch.cat([input_ids.expand(len(hyps), -1), tail.to(input_ids.device)], dim=1)
+        if not return_dict:
+            return seqs
+        return BeamOutput(seqs, torch.stack([s for s, _ in hyps]).to(torch.float32))
 
     # --- closed-set answers: log p(option | frames, question) of every option, the options packed into one pass over the weights
     @torch.no_grad()
